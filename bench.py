@@ -10,6 +10,8 @@ rank 0 de-interleaves into the image. Scene/camera are resident on the
 device before timing. Launch:
 
     python bench.py [--gpus 1] [--steps 10] [--warmup 2]
+    python bench.py --full ...          (plus every other leg, below)
+    python bench.py --dump-outputs DIR  (the last timed frame -> DIR/image.npy)
     python bench.py --gpus N ...        (N > 1: launches its N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
@@ -26,8 +28,15 @@ per step is fixed as N grows ("scaling": "strong"). An N > 1
 line also carries `dist` (the process group's backend and size as
 torch.distributed saw them, the RCCL version, each rank's device and its
 per-step render / gather / de-interleave times from HIP events on the
-step's stream) and `parity` (rows of the gathered frame, two from every
-rank's share, bit for bit against the fp32 oracle after timing).
+step's stream).
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and
+prints the line; the legs that take runs of their own are null in it.
+`--full` adds them after the timed steps: the rocprofv3 PMC passes (HBM
+traffic, executed FLOPs, stall breakdown, the issue ceiling), the CPU
+baseline with its bit-for-bit row check, the 2/4/8-way part scaling, the
+per-sample-RNG kernel, and for a gathered frame `parity` (rows of it, two
+from every rank's share, bit for bit against the fp32 oracle).
 """
 from __future__ import annotations
 
@@ -80,6 +89,13 @@ def parse():
     p.add_argument("--spawn", action="store_true",
                    help="launch the ranks through torch.distributed.run as a child process even for N=1 "
                         "(N>1 outside torch.distributed.run always does)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every other leg (each has its own switch: --pmc, "
+                        "--cpu-seconds, --parts, --per-sample) and the gathered frame's parity check; a plain run "
+                        "sets up, warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="rank 0 writes the frame of the last timed step to DIR/image.npy (float32, HxWx4; a frame "
+                        "over 64 MB: a fixed seeded choice of its rows, their indices in DIR/image_rows.npy)")
     p.add_argument("--dump-image", default="", help=argparse.SUPPRESS)  # rank 0 saves the last frame (.npy)
     p.add_argument("--probe", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--probe-parts", type=int, default=0, help=argparse.SUPPRESS)  # --probe: an R-way split
@@ -615,6 +631,27 @@ def gathered_parity(world, frame, image, H, T, R, per_part=2):
             "bit_exact": bool(same.all()), "checker": "fp32 oracle (oracle/rtx_oracle.c), after timing"}
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, image, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the timed path handed its caller in the last timed
+    step — the frame, HxWx4 float32 — as out_dir/image.npy. A frame over
+    `limit` bytes is cut to whole rows chosen by a fixed seed (ascending), and
+    their indices go to out_dir/image_rows.npy (float64), so two builds
+    write the same rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    H = image.shape[0]
+    row_bytes = int(image[0].numel()) * 4 + 8  # the row and its index
+    if H * row_bytes > limit:
+        keep = max(1, limit // row_bytes - 1)  # room for the two .npy headers
+        rows = np.sort(np.random.default_rng(20240229).choice(H, size=keep, replace=False))
+        np.save(os.path.join(out_dir, "image_rows.npy"), rows.astype(np.float64))
+        image = image[rows.tolist()]
+    np.save(os.path.join(out_dir, "image.npy"), image.cpu().numpy().astype(np.float32, copy=False))
+
+
 def main():
     args = parse()
     if args.probe:
@@ -738,6 +775,8 @@ def main():
                              "each the mean over the timed steps of HIP events on the step's stream"}
     if args.dump_image and rank == 0:
         np.save(args.dump_image, image.cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, image)
 
     if rank == 0:
         samples = W * H * args.spp * args.steps
@@ -747,22 +786,26 @@ def main():
         rows0 = rtx.part_rows(H, T, 0, R) if R > 1 else H
         alg_bytes = rows0 * W * 16 + world.count * 32  # framebuffer + scene
         n_cu = torch.cuda.get_device_properties(local_rank).multi_processor_count
-        traffic, pmc_note, executed = (None, "skipped (PMC passes run at N=1 with --pmc auto)", None)
+        # Everything from here to the line is a leg of its own (child
+        # processes under rocprofv3, the CPU oracle, further renders): --full
+        # only. A plain run prints the line from the timed steps alone.
+        full = args.full
+        traffic, pmc_note, executed = (None, "skipped (PMC passes run at N=1 with --full and --pmc auto)", None)
         ceiling = None
-        if args.pmc == "auto" and R == 1:
+        if full and args.pmc == "auto" and R == 1:
             traffic, pmc_note = pmc_traffic(args)
             executed = pmc_valu(args, n_cu, launch_ms)
             ceiling = issue_ceiling(args, executed, n_cu)
-        host_img = image.cpu().numpy()
+        host_img = image.cpu().numpy() if full else None
         cpu, parity = (None, None)
-        if R == 1 and args.cpu_seconds > 0:
+        if full and R == 1 and args.cpu_seconds > 0:
             cpu, parity = cpu_baseline(args, world, frame, host_img, args.cpu_seconds)
-        if collective and parity is None:  # the gathered frame: rows of every rank's share
+        if full and collective and parity is None:  # the gathered frame: rows of every rank's share
             parity = gathered_parity(world, frame, host_img, H, T, R)
         # the 1/2/4/8-GPU split rehearsed on this device (BASELINE.json metric:
         # "1/2/4/8-GPU scaling"); the real N-GPU runs are the driver's
         parts = None
-        if R == 1 and args.parts:
+        if full and R == 1 and args.parts:
             parts = part_scaling(ctx, args, world, frame, launch_ms, dev,
                                  parts=[int(x) for x in args.parts.split(",") if x])
         # The north star's kernel shape — one lane per (pixel, sample) — on the
@@ -770,7 +813,7 @@ def main():
         # DESIGN.md §3a): reported beside the headline, which stays the
         # reference's chain RNG. N = 1 only.
         per_sample = None
-        if R == 1 and args.rng == "chain" and args.per_sample:
+        if full and R == 1 and args.rng == "chain" and args.per_sample:
             frame.rng_mode = 1
             ctx.set_frame(frame)
             ctx.render_rows(1, 0, 1, image.data_ptr())
@@ -811,6 +854,7 @@ def main():
             "n_gpus": R,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "strong",

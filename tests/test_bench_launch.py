@@ -9,7 +9,8 @@ outside torch.distributed.run starts its N ranks itself, as a fresh
 * the launcher itself, end to end, on 2 and 3 gloo ranks with the oracle
   standing in for the kernel (tests/dist_rank_helper.py): every rank sees
   the world size and env it should, runs FrameGather's phases in order, and
-  the gathered frame equals the single-process oracle frame bit for bit.
+  the gathered frame equals the single-process oracle frame bit for bit;
+* `--dump-outputs`: the frame as float32, a large one as seeded whole rows.
 The GPU side (`bench.py --gpus 1 --spawn`, the one-rank RCCL line) is
 tests/test_gpu_multirank.py::test_bench_spawn_one_rank.
 """
@@ -91,3 +92,25 @@ def test_kernel_class_names_every_render_instance(bench):
         assert bench.kernel_class(f"void rtx::k_render<false, true, {', '.join(['true'] * (n - 2))}>(x)") == "prepass"
     assert bench.kernel_class("void rtx::k_render_ps<true, false, false>(rtx::KParams)") == "k_render_ps"
     assert bench.kernel_class("__amd_rocclr_fillBufferAligned") is None
+
+
+def test_dump_outputs_whole_frame_and_seeded_rows(tmp_path, bench):
+    """--dump-outputs: a frame under the size limit is written whole as
+    float32; a larger one as the same seeded choice of whole rows on every
+    call (ascending, indices beside it), within the limit."""
+    import torch
+    img = torch.arange(40 * 6 * 4, dtype=torch.float32).reshape(40, 6, 4)
+    bench.dump_outputs(str(tmp_path / "a"), img)
+    a = np.load(tmp_path / "a" / "image.npy")
+    assert a.dtype == np.float32 and not (tmp_path / "a" / "image_rows.npy").exists()
+    np.testing.assert_array_equal(a, img.numpy())
+    limit = 1500  # a row is 96 B + its 8 B index: room for 13 rows and the two headers
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), img, limit=limit)
+    rows = np.load(tmp_path / "b" / "image_rows.npy")
+    b = np.load(tmp_path / "b" / "image.npy")
+    assert rows.dtype == np.float64 and b.dtype == np.float32
+    assert 1 <= len(rows) < 40 and (np.diff(rows) > 0).all() and b.nbytes + rows.nbytes <= limit
+    np.testing.assert_array_equal(b, img.numpy()[rows.astype(int)])
+    np.testing.assert_array_equal(rows, np.load(tmp_path / "c" / "image_rows.npy"))
+    np.testing.assert_array_equal(b, np.load(tmp_path / "c" / "image.npy"))

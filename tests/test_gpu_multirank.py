@@ -113,13 +113,18 @@ def test_bench_rccl_path_one_rank(tmp_path, oracle, rtx):
     img_path = str(tmp_path / "img.npy")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--gather", "--width", str(W),
            "--height", str(H), "--spp", str(spp), "--steps", "2", "--warmup", "1", "--pmc", "off",
-           "--cpu-seconds", "0", "--parts", "", "--per-sample", "0", "--dump-image", img_path]
+           "--cpu-seconds", "0", "--parts", "", "--per-sample", "0", "--dump-image", img_path,
+           "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=150)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
-    assert line["n_gpus"] == 1 and line["value"] > 0
+    assert line["n_gpus"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
     assert line["config"]["parallelism"] == "row-tiles x1 + RCCL gather"
+    assert line["full"] is False and line["parity"] is None  # a plain run: no leg of its own after the steps
     got = np.load(img_path)
+    dumped = np.load(tmp_path / "out" / "image.npy")  # --dump-outputs: the same last frame, float32
+    assert dumped.dtype == np.float32 and sorted(os.listdir(tmp_path / "out")) == ["image.npy"]
+    np.testing.assert_array_equal(dumped.view(np.uint32), got.view(np.uint32))
     world = rtx.random_world(11, depth=50, spp=spp)
     frame = rtx.camera_look_at(W, H, aspect=W / H)
     rows = np.linspace(1, H - 2, 8).astype(np.uint32)
@@ -133,12 +138,13 @@ def test_bench_spawn_one_rank(tmp_path, oracle, rtx):
     child, the rank runs the RCCL path — and the N-rank line's schema: the
     process group as torch.distributed saw it, the RCCL version, the rank's
     device and per-step render / gather / de-interleave times, and the
-    gathered frame's rows bit-exact against the oracle."""
+    gathered frame's rows bit-exact against the oracle (`--full`: the line's
+    own `parity` check is a leg of the full run)."""
     import json
     import subprocess
     W, H, spp = 320, 180, 16
     img_path = str(tmp_path / "img.npy")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--width", str(W),
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--full", "--width", str(W),
            "--height", str(H), "--spp", str(spp), "--steps", "3", "--warmup", "1", "--pmc", "off",
            "--cpu-seconds", "0", "--parts", "", "--per-sample", "0", "--dump-image", img_path]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=200)

@@ -33,7 +33,7 @@ for s in $STEPS; do
     issue)  run issue 600 python tools/issue_probe.py ;;
     tests)  run tests 900 python -u -m pytest tests -m gpu -x -v -rA --timeout 300 --timeout-method thread ;;
     smoke)  run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)  run bench 600 python bench.py --steps 10 --warmup 2 ;;
+    bench)  run bench 600 python bench.py --full --steps 10 --warmup 2 ;;
     prof)   run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
                 python3 bench.py --steps 5 --warmup 1 --cpu-seconds 0 --pmc off --parts '' --per-sample 0 ;;
     prof8)  run prof8 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof8" -o run -- \
@@ -44,15 +44,15 @@ for s in $STEPS; do
                 python3 bench.py --probe --rng per-sample --probe-frames 3 ;;
     gtest)  run gtest 600 python -u -m pytest ${GTESTS:-tests/test_gpu_parity.py} -m gpu -x -q --timeout 120 \
                 --timeout-method thread ;;
-    c3b)    run c3b 900 python bench.py --width 3840 --height 2160 --spp 1024 --steps 2 --warmup 1 --cpu-seconds 10 --parts '' ;;
-    c5b)    run c5b 900 python bench.py --spp 16 --grid 159 --max-spheres 100000 --steps 3 --warmup 1 --cpu-seconds 10 --parts '' --per-sample ${C5PS:-0} ;;
-    c3ps)   run c3ps 900 python bench.py --rng per-sample --width 3840 --height 2160 --spp 1024 --steps 2 --warmup 1 --cpu-seconds 10 --parts '' ;;
-    c5lin)  run c5lin 900 python bench.py --spp 16 --grid 159 --max-spheres 100000 --scan linear --steps 1 --warmup 1 --cpu-seconds 10 --parts '' --per-sample 0 ;;
-    c2lin)  run c2lin 600 python bench.py --scan linear --steps 5 --warmup 1 --cpu-seconds 10 --parts '' --per-sample 0 ;;
-    c5ps)   run c5ps 900 python bench.py --rng per-sample --spp 16 --grid 159 --max-spheres 100000 --steps 3 --warmup 1 --cpu-seconds 10 --parts '' ;;
+    c3b)    run c3b 900 python bench.py --full --width 3840 --height 2160 --spp 1024 --steps 2 --warmup 1 --cpu-seconds 10 --parts '' ;;
+    c5b)    run c5b 900 python bench.py --full --spp 16 --grid 159 --max-spheres 100000 --steps 3 --warmup 1 --cpu-seconds 10 --parts '' --per-sample ${C5PS:-0} ;;
+    c3ps)   run c3ps 900 python bench.py --full --rng per-sample --width 3840 --height 2160 --spp 1024 --steps 2 --warmup 1 --cpu-seconds 10 --parts '' ;;
+    c5lin)  run c5lin 900 python bench.py --full --spp 16 --grid 159 --max-spheres 100000 --scan linear --steps 1 --warmup 1 --cpu-seconds 10 --parts '' --per-sample 0 ;;
+    c2lin)  run c2lin 600 python bench.py --full --scan linear --steps 5 --warmup 1 --cpu-seconds 10 --parts '' --per-sample 0 ;;
+    c5ps)   run c5ps 900 python bench.py --full --rng per-sample --spp 16 --grid 159 --max-spheres 100000 --steps 3 --warmup 1 --cpu-seconds 10 --parts '' ;;
     variants) run variants 900 python tools/variant_bench.py --rounds ${VROUNDS:-5} --frames 2 ${VARGS:-} ${VNAMES:-} ;;
     ctrlist) run ctrlist 120 rocprofv3 -L ;;
-    c2ps)   run c2ps 600 python bench.py --rng per-sample --steps 5 --warmup 1 --cpu-seconds 10 --parts '' ;;
+    c2ps)   run c2ps 600 python bench.py --full --rng per-sample --steps 5 --warmup 1 --cpu-seconds 10 --parts '' ;;
     timeline) run timeline 300 python tools/wave_timeline.py ;;
     vtimeline) for v in ${VTL:-blk64 lpt lpt_blk64}; do
               run timeline_$v 300 python tools/wave_timeline.py raytrace-we-gpu_amd/lib/variants/librtx_$v.so; done ;;
