@@ -41,8 +41,48 @@ __device__ __forceinline__ void diag_add(int k, uint32_t v) {
     if ((int)(threadIdx.x & 63u) == __ffsll((long long)m) - 1) diag_slots()[k] += v;
 }
 #define RTX_DIAG_ADD(k, v) diag_add(k, v)
+// hit_world's parts, one set per wave in LDS (64-bit): clocks of [0] line
+// set-up + grid walk [1] scan [2] resolve, [3] the running timestamp; the
+// walk's balance: [4] walks (wave calls) [5] steps of the wave's slowest lane,
+// summed over walks [6] steps summed over the lanes [7] rounds the wave ran
+// (the per-lane walk: [5] again). RTX_DIAG_HW_BEGIN() starts the clock,
+// RTX_DIAG_HW(k) closes part k; called by the lanes that reach hit_world.
+__device__ __forceinline__ unsigned long long *diag_hw() {
+    __shared__ unsigned long long s[4][8];
+    return s[(threadIdx.x / 64) & 3u];
+}
+__device__ __forceinline__ void diag_hw_clock(int k) {
+    const uint64_t m = __ballot(1);
+    if ((int)(threadIdx.x & 63u) == __ffsll((long long)m) - 1) {
+        const unsigned long long tn = __builtin_readcyclecounter();
+        if (k >= 0) diag_hw()[k] += tn - diag_hw()[3];
+        diag_hw()[3] = tn;
+    }
+}
+// one walk of the wave: `steps` this lane's cells (or items, < 256); `rounds`
+// the rounds the wave ran (0: the per-lane walk, which runs its slowest lane's steps)
+__device__ __forceinline__ void diag_hw_walk(uint32_t steps, uint32_t rounds) {
+    uint32_t mx = 0;  // the wave's maximum, bit by bit (any set of active lanes)
+    for (int b = 7; b >= 0; --b) {
+        const uint32_t t = mx | (1u << b);
+        if (__ballot(min(steps, 255u) >= t) != 0ull) mx = t;
+    }
+    const uint64_t m = __ballot(1);
+    if ((int)(threadIdx.x & 63u) == __ffsll((long long)m) - 1) {
+        diag_hw()[4] += 1ull;
+        diag_hw()[5] += mx;
+        diag_hw()[7] += rounds ? rounds : mx;
+    }
+    atomicAdd(&diag_hw()[6], (unsigned long long)steps);
+}
+#define RTX_DIAG_HW_BEGIN() diag_hw_clock(-1)
+#define RTX_DIAG_HW(k) diag_hw_clock(k)
+#define RTX_DIAG_WALK(steps, rounds) diag_hw_walk(steps, rounds)
 #else
 #define RTX_DIAG_ADD(k, v)
+#define RTX_DIAG_HW_BEGIN()
+#define RTX_DIAG_HW(k)
+#define RTX_DIAG_WALK(steps, rounds)
 #endif
 
 // Coop section clocks (groups_impl / groups_sm): cp = the wave's tier-N
@@ -75,7 +115,7 @@ struct Diag {
     __device__ __forceinline__ void begin() {
 #if RTX_DIAG_PROF
         if ((threadIdx.x & 63u) == 0u)
-            for (int k = 0; k < 8; ++k) diag_slots()[k] = 0u;
+            for (int k = 0; k < 8; ++k) diag_slots()[k] = 0u, diag_hw()[k] = 0ull;
         tq = __builtin_readcyclecounter();
 #endif
 #if RTX_DIAG_COOP
@@ -166,6 +206,8 @@ struct Diag {
         if (P.wave_times && (threadIdx.x & 63u) == 0u) {
             for (int k = 0; k < 7; ++k) atomicAdd(&P.wave_times[k], pr[k]);
             for (int k = 0; k < 7; ++k) atomicAdd(&P.wave_times[8 + k], (unsigned long long)diag_slots()[k]);
+            if (P.wave_cap >= 12u)  // hit_world's parts (diag_hw): armed with 12 pairs or more
+                for (int k = 0; k < 8; ++k) atomicAdd(&P.wave_times[16 + k], diag_hw()[k]);
         }
 #endif
 #if RTX_DIAG_COOP

@@ -155,6 +155,155 @@ RTX_GD uint64_t grid_mask(const LayerGrid &G, Cell cell, float ox, float oy, flo
     return done ? m : ~0ull;
 }
 
+// The wave-cooperative walk (rtx_kernels.hip grid_wave_mask). The wave needs
+// only the union of its lanes' masks, and a union does not care which lane
+// visits which cell: each lane cuts its stretch into independent items, one
+// per column of cells along the major axis of its (x, z) direction (the axis
+// of the larger |d| component, so the minor coordinate moves at most one
+// cell per column), and the wave's lanes share all items evenly. An item ORs
+// the 1-3 cells of its column that the stretch's minor interval, padded by
+// kGridCoopEps cells, meets. The DDA above stays the specification.
+//
+// Superset. Work in cell units, (p - (x0, z0)) / h, and let S be the true
+// stretch {o + t d : t0 <= t <= t1} of the fp32 (t0, t1) both walks compute
+// with the same ops. Every cell the DDA visits lies within r_D of S (the
+// argument at the top: a start cell from a rounded point, crossings ordered
+// on rounded times, an end decided on a rounded time: r_D <= 4u |p - o| / h,
+// < 1e-3 cells at |p|, |o| <= 64, h >= 1/8). A cell (c, j) within r of S has
+// a point of S with major coordinate in [c - r, c + 1 + r]; moving that point
+// to the column's clamped range [max(c, lo), min(c + 1, hi)] moves its minor
+// coordinate by at most r |s| <= r, so the cell's minor range is within 2r of
+// the line over that range. The item evaluates the line there with an error
+// r_M <= 8u (|p| + |o|) / h + 8u n_cells (the two rounded end points, the
+// slope's two roundings over at most kGridMaxSteps columns, A's rounding:
+// < 3e-3 cells) and pads by kGridCoopEps, and the column range is padded
+// likewise; so every cell within (kGridCoopEps - r_M) / 2 of S is in some
+// item: with kGridCoopEps = 2^-6 that is > 6e-3 > r_D, and the items' cells
+// contain the DDA's. A stretch of more than kGridMaxSteps columns, one that
+// has no end (t1 = inf) or a slope that is not a number gives up (every
+// block), as do the DDA's far and non-finite rays. Where the DDA itself gives
+// up on its step limit the items may not: they still cover every cell near
+// S, which is what the sufficiency argument needs.
+// tests/grid_coop_check.cpp checks the superset on the adversarial rays of
+// grid_check.cpp, its failure at an epsilon of 0, and the wave's sharing.
+#ifndef RTX_GRID_COOP_EPS  // (tests: 0 must fail the superset check)
+#define RTX_GRID_COOP_EPS (1.0f / 64.0f)
+#endif
+constexpr float kGridCoopEps = RTX_GRID_COOP_EPS;
+
+// x clamped to [lo, hi] (lo <= hi, no NaN: one v_med3_f32 on the device, the same value)
+RTX_GD float grid_clampf(float x, float lo, float hi) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_fmed3f(x, lo, hi);
+#else
+    return fminf(fmaxf(x, lo), hi);
+#endif
+}
+
+// A lane's stretch cut into items: item i < n is column c0 + i of the major
+// axis (zmajor: z, else x). In cell units the stretch spans [lo, hi] along
+// the major axis and its minor coordinate is A + s * major.
+struct GridStretch {
+    float lo, hi, A, s;
+    uint32_t c0, n, zmajor;
+};
+
+// The items of the ray (o, d): false when the lane gives up (the caller scans
+// every block). n = 0: the ray's t >= 0 part never enters the slab inside the
+// grid's box.
+RTX_GD bool grid_stretch(const LayerGrid &G, float ox, float oy, float oz, float dx, float dy, float dz,
+                         GridStretch &R) {
+    R.lo = R.hi = R.A = R.s = 0.0f;
+    R.c0 = R.n = R.zmajor = 0u;
+    const float o2 = fmaf(ox, ox, fmaf(oy, oy, oz * oz));
+    const float d2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+    if (!(o2 <= kGridOMax * kGridOMax) || !(d2 <= 3.0e38f)) return false;  // far or non-finite
+    const float inf = INFINITY;
+    float t0 = 0.0f, t1 = inf;
+    // grid_walk's clips, op for op (the same t0, t1); returns 1 / d (0 for d = 0)
+    auto clip = [&](float o, float d, float lo, float hi) {
+        if (d == 0.0f) {
+            if (!(o >= lo && o <= hi)) t1 = -inf;
+            return 0.0f;
+        }
+        const float inv = 1.0f / d;
+        const float ta = (lo - o) * inv, tb = (hi - o) * inv;
+        t0 = fmaxf(t0, fminf(ta, tb));
+        t1 = fminf(t1, fmaxf(ta, tb));
+        return inv;
+    };
+    clip(oy, dy, G.ylo, G.yhi);
+    const float ivx = clip(ox, dx, G.x0, G.x0 + (float)G.nx * G.h);
+    const float ivz = clip(oz, dz, G.z0, G.z0 + (float)G.nz * G.h);
+    if (!(t0 <= t1)) return true;
+    if (!(t1 <= 3.0e38f)) return false;  // no end: d = 0 along x and z, or overflow
+    const bool zm = fabsf(dz) > fabsf(dx);
+    const float om = zm ? oz : ox, dm = zm ? dz : dx, on = zm ? ox : oz, dn = zm ? dx : dz;
+    const float M0 = zm ? G.z0 : G.x0, N0 = zm ? G.x0 : G.z0;
+    const float nM = (float)(zm ? G.nz : G.nx);
+    const float s = dn * (zm ? ivz : ivx);  // |dn| <= |dm|: |s| <= 1 + 2u, or 0 (dm = 0), or not a number (1 / dm overflowed)
+    if (!(fabsf(s) <= 2.0f)) return false;
+    const float a0 = (fmaf(t0, dm, om) - M0) * G.inv_h, a1 = (fmaf(t1, dm, om) - M0) * G.inv_h;
+    const float b0 = (fmaf(t0, dn, on) - N0) * G.inv_h;
+    R.lo = fminf(a0, a1), R.hi = fmaxf(a0, a1);
+    R.s = s;
+    R.A = fmaf(-a0, s, b0);
+    const float c0 = grid_clampf(floorf(R.lo - kGridCoopEps), 0.0f, nM - 1.0f);
+    const float c1 = grid_clampf(floorf(R.hi + kGridCoopEps), 0.0f, nM - 1.0f);
+    R.c0 = (uint32_t)c0;
+    R.zmajor = zm ? 1u : 0u;
+    const uint32_t n = (uint32_t)c1 - (uint32_t)c0 + 1u;
+    if (n > kGridMaxSteps) return false;
+    R.n = n;
+    return true;
+}
+
+// The cells of the item at column c of a stretch (lo, hi, A, s, zmajor):
+// cells k0 + q * stride, q < cnt, 1 <= cnt <= 3 (the padded minor interval is
+// shorter than 2 cells).
+RTX_GD void grid_item_cells(const LayerGrid &G, float lo, float hi, float A, float s, uint32_t zmajor, uint32_t c,
+                            uint32_t &k0, uint32_t &stride, uint32_t &cnt) {
+    const float ma = grid_clampf((float)c, lo, hi), mb = grid_clampf((float)(c + 1u), lo, hi);
+    const float na = fmaf(ma, s, A), nb = fmaf(mb, s, A);
+    const float nN = (float)(zmajor ? G.nx : G.nz);
+    const float j0 = grid_clampf(floorf(fminf(na, nb) - kGridCoopEps), 0.0f, nN - 1.0f);
+    const float j1 = grid_clampf(floorf(fmaxf(na, nb) + kGridCoopEps), 0.0f, nN - 1.0f);
+    const uint32_t j = (uint32_t)j0;
+    const uint32_t w = (uint32_t)j1 - j + 1u;
+    cnt = w < 3u ? w : 3u;
+    k0 = zmajor ? j * G.nz + c : c * G.nz + j;
+    stride = zmajor ? G.nz : 1u;
+}
+
+// The mask of one ray by its items (what the wave's lanes compute together):
+// ~0 when the lane gives up.
+template <typename Cell>
+RTX_GD uint64_t grid_mask_items(const LayerGrid &G, Cell cell, float ox, float oy, float oz, float dx, float dy,
+                                float dz) {
+    GridStretch R;
+    if (!grid_stretch(G, ox, oy, oz, dx, dy, dz, R)) return ~0ull;
+    uint64_t m = 0ull;
+    for (uint32_t i = 0; i < R.n; ++i) {
+        uint32_t k0, stride, cnt;
+        grid_item_cells(G, R.lo, R.hi, R.A, R.s, R.zmajor, R.c0 + i, k0, stride, cnt);
+        for (uint32_t q = 0; q < cnt; ++q) m |= cell(k0 + q * stride);
+    }
+    return m;
+}
+
+// How the wave shares its items, as the kernel runs it (grid_wave_mask) and
+// the CPU checker emulates it: the `nact` active lanes hold slots 0 .. nact - 1
+// in lane order; lane l's items are start_l .. start_l + n_l - 1 (start: the
+// exclusive prefix sum of n over the active lanes); round r serves items
+// r nact .. r nact + nact - 1, slot q taking item r nact + q. grid_share_mark
+// returns the slot of round r (base = r nact) at which lane l writes its id:
+// the first of its items in the round, or -1 when it has none there. A slot's
+// owner is then the id at the nearest marked slot at or before it.
+RTX_GD int grid_share_mark(uint32_t start, uint32_t n, uint32_t base, uint32_t nact) {
+    if (n == 0u || start + n <= base || start >= base + nact) return -1;
+    return (int)(start > base ? start - base : 0u);
+}
+
 // Host: the geometry of a layer grid over `m` spheres sph[4 j] = (cx, cy,
 // cz, r) (every cy equal: y0) and, for each, every cell its disc of radius
 // rho_j + kGridFat meets: add(cell, j). Returns false (no grid) past

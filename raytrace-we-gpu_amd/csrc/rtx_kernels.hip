@@ -967,20 +967,108 @@ __device__ __forceinline__ int hit_world_culled(const KScene &S, f3 o, f3 d, flo
 }
 
 // The layer grid (rtx_grid.h): the blocks of the flat run some
-// lane of the wave may need — the OR of the lanes' walks. Only the lanes that
-// reach hit_world take part (an inactive lane needs nothing); the OR goes
-// through one LDS word per wave, the list's spare row at the wave's first two
-// lanes (`spare`: the list's row `cap`, never a list entry). A lane outside
-// the prefilter's safe range marks every block.
-__device__ __forceinline__ uint64_t grid_wave_mask(const KScene &S, f3 o, f3 d, const LineTest &T, uint32_t *spare) {
-    const LayerGrid G = *S.grid;  // wave-uniform: scalar loads
-    const uint64_t *gc = reinterpret_cast<const uint64_t *>(S.grid + 1);
-    const uint64_t mine = T.thr == -__uint_as_float(0x7f800000u)
-                              ? ~0ull
-                              : grid_mask(G, [gc](uint32_t k) { return gc[k]; }, o.x, o.y, o.z, d.x, d.y, d.z);
+// lane of the wave may need — the OR of the lanes' masks. Only the lanes that
+// reach hit_world take part (an inactive lane needs nothing and serves no
+// item). The wave computes the union directly (rtx_grid.h "the
+// wave-cooperative walk"): every lane cuts its stretch of the slab into items
+// (grid_stretch), a prefix sum over the active lanes numbers them, and round r
+// hands item r nact + q to the q-th active lane, so the rounds are
+// ceil(items / nact) whatever lane the items came from. A slot finds its
+// owner through the wave's own columns of the candidate list's row 0 (idle
+// until the scan starts): the owners write their lane at their first slot of
+// the round (grid_share_mark), and the nearest mark at or before a slot is its
+// owner; the owner's stretch arrives by ds_bpermute. Every lane ORs its items'
+// cells into a register; one LDS word per wave (`spare`: the list's row
+// `cap`, never a list entry, at the wave's first two lanes) makes the union.
+// A lane outside the prefilter's safe range, or one that gives up, makes the
+// wave's mask ~0 at once.
+// The grid's header and cell pointer are read here, through a pointer the
+// compiler cannot follow (as frame_vals): held across the kernel they were
+// spilled to VGPR lanes and restored on every step of the walk.
+__device__ __forceinline__ uint64_t grid_wave_mask(const KScene &S, f3 o, f3 d, const LineTest &T, uint32_t *list,
+                                                   uint32_t *spare) {
+    typedef const __attribute__((address_space(4))) LayerGrid *grid_cp;
+    typedef const __attribute__((address_space(1))) uint64_t *cell_gp;
+    const uint64_t ga = (uint64_t)(uintptr_t)S.grid;
+    uint32_t alo = (uint32_t)ga, ahi = (uint32_t)(ga >> 32);
+    asm volatile("" : "+v"(alo), "+v"(ahi));
+    alo = (uint32_t)__builtin_amdgcn_readfirstlane((int)alo);
+    ahi = (uint32_t)__builtin_amdgcn_readfirstlane((int)ahi);
+    const uint64_t gaddr = ((uint64_t)ahi << 32) | alo;
+    const grid_cp gp = (grid_cp)(uintptr_t)gaddr;
+    LayerGrid G;  // wave-uniform: scalar loads
+    G.x0 = gp->x0, G.z0 = gp->z0, G.h = gp->h, G.inv_h = gp->inv_h, G.ylo = gp->ylo, G.yhi = gp->yhi;
+    G.nx = gp->nx, G.nz = gp->nz, G.far_m = 0.0f, G.nblk = 0u;
+    const cell_gp gc = (cell_gp)(uintptr_t)(gaddr + sizeof(LayerGrid));
+    GridStretch R;
+    const bool mine_ok =
+        T.thr != -__uint_as_float(0x7f800000u) && grid_stretch(G, o.x, o.y, o.z, d.x, d.y, d.z, R);
+    if (__ballot(!mine_ok) != 0ull) {  // some lane scans every block: so does the wave
+        RTX_DIAG_WALK(0u, 1u);
+        return ~0ull;
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t act = __ballot(1);
+    auto below = [](uint64_t m) {  // bits of m below this lane
+        return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    };
+    const uint32_t nact = (uint32_t)__popcll(act), slot = below(act);
+    // the items before this lane's and the wave's total: n <= kGridMaxSteps < 64, one ballot per bit
+    static_assert(kGridMaxSteps < 64u, "grid_wave_mask: item counts of 6 bits");
+    uint32_t start = 0, total = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 6u; ++b) {
+        const uint64_t mb = __ballot(((R.n >> b) & 1u) != 0u);
+        start += below(mb) << b;
+        total += (uint32_t)__popcll(mb) << b;
+    }
+    const uint32_t pack = start | (R.c0 << 12) | (R.zmajor << 24);  // start <= 63 * 48, c0 < kGridMaxCells
+    static_assert(63u * kGridMaxSteps < 4096u && kGridMaxCells <= 4096u, "grid_wave_mask: packed owner word");
+    const uint32_t last_cell = G.nx * G.nz - 1u;
+    // the wave's columns of row 0. (Held as LDS byte addresses in SGPRs, so
+    // that no round reloads an address from scratch, the C2 frame measured
+    // 37.1 ms against 31.8 ms: RESULTS.md S8b.)
+    uint32_t *marks = list + (threadIdx.x & ~63u);
+    uint32_t *my_mark = marks + slot;
+    auto from = [](uint32_t lane4, uint32_t v) {  // v of lane lane4 / 4
+        return (uint32_t)__builtin_amdgcn_ds_bpermute((int)lane4, (int)v);
+    };
+    uint64_t mine = 0ull;
+    uint32_t rounds = 0;
+    for (uint32_t base = 0; base < total; base += nact) {
+        ++rounds;
+        __hip_atomic_store(my_mark, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        const int ms = grid_share_mark(start, R.n, base, nact);
+        if (ms >= 0)
+            __hip_atomic_store(marks + ms, lane + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        const uint32_t v = __hip_atomic_load(my_mark, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        // the nearest mark at or before this slot (slots ascend with the lanes)
+        const uint64_t le = __ballot(v != 0u) & ((2ull << lane) - 1ull);
+        const bool valid = base + slot < total;  // (then le != 0: item 0 of the round is marked)
+        const uint32_t at = le != 0ull ? 63u - (uint32_t)__clzll((long long)le) : lane;
+        const uint32_t own4 = ((from(4u * at, v) - 1u) & 63u) * 4u;
+        const uint32_t opack = from(own4, pack);
+        const float olo = __uint_as_float(from(own4, __float_as_uint(R.lo)));
+        const float ohi = __uint_as_float(from(own4, __float_as_uint(R.hi)));
+        const float oA = __uint_as_float(from(own4, __float_as_uint(R.A)));
+        const float os = __uint_as_float(from(own4, __float_as_uint(R.s)));
+        if (valid) {
+            const uint32_t c = ((opack >> 12) & 0xfffu) + (base + slot - (opack & 0xfffu));
+            uint32_t k0, stride, cnt;
+            grid_item_cells(G, olo, ohi, oA, os, opack >> 24, c, k0, stride, cnt);
+            const uint64_t m0 = gc[min(k0, last_cell)];
+            const uint64_t m1 = gc[min(k0 + (cnt > 1u ? stride : 0u), last_cell)];
+            mine |= m0 | m1;
+            if (cnt > 2u) mine |= gc[min(k0 + 2u * stride, last_cell)];
+        }
+    }
+    RTX_DIAG_WALK(R.n, rounds);
+    (void)rounds;
     unsigned long long *w = reinterpret_cast<unsigned long long *>(spare + (threadIdx.x & ~63u));
-    const uint32_t lead = (uint32_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x);
-    if (threadIdx.x == lead) __hip_atomic_store(w, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (slot == 0u) __hip_atomic_store(w, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
     __hip_atomic_fetch_or(w, (unsigned long long)mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
@@ -1013,6 +1101,7 @@ __device__ __forceinline__ int hit_world_pre_ld(const KScene &S, Ld ld, f3 o, f3
                                                 bool live = true) {
     const cfloat_p pre = (cfloat_p)S.pre;
     const uint32_t nblk = S.n_pad / 8;
+    RTX_DIAG_HW_BEGIN();
     LineTest T = line_test_setup(o.x, o.y, o.z, d.x, d.y, d.z, a, S.smag);
     if (!live) {  // a lane without a ray (RTX_PF_LDS: every lane fills the tile): nothing is flagged
         T.ux = T.uy = T.uz = T.vy = T.vz = T.nou = T.nov = 0.0f;
@@ -1021,8 +1110,9 @@ __device__ __forceinline__ int hit_world_pre_ld(const KScene &S, Ld ld, f3 o, f3
     // the layer grid (small scenes, rtx_grid.h): the flat run's blocks some lane of the wave needs
     uint64_t gm = ~0ull;
     if constexpr (!kPF && kGridOk) {
-        if (RTX_GRID && S.grid != nullptr) gm = grid_wave_mask(S, o, d, T, list + cand_of<kPF>() * kRB);
+        if (RTX_GRID && S.grid != nullptr) gm = grid_wave_mask(S, o, d, T, list, list + cand_of<kPF>() * kRB);
     }
+    RTX_DIAG_HW(0);
     const float best0 = best;
     int idx = -1;
     bool ok = true;
@@ -1035,7 +1125,9 @@ __device__ __forceinline__ int hit_world_pre_ld(const KScene &S, Ld ld, f3 o, f3
     for (;;) {
         uint32_t cnt;
         b = scan_prefilter<kPF, kTile>(pre, b, end, T, S, list, cnt, pack, lds_pr, gm);
+        RTX_DIAG_HW(1);
         ok = resolve_pre_t(ld, S.n, list, cnt, o, d, a, inv_a, t_min, best, idx, cand_of<kPF>()) && ok;
+        RTX_DIAG_HW(2);
         if (b < end) continue;
         if (end == nblk && b0 != 0u) {  // wrap round to the start
             b = 0;

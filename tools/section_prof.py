@@ -30,12 +30,12 @@ for path in libs:
     c.set_frame(frame)
     c.render()
     c.sync()
-    c.arm_wave_times(8)
+    c.arm_wave_times(12)
     c.stats_reset()
     c.render()
     c.sync()
     st = c.stats()
-    v = c.wave_times(8).reshape(-1).astype(np.float64)
+    v = c.wave_times(12).reshape(-1).astype(np.float64)
     names = ["refill", "hit_world", "shade", "tail", "iters", "tail_iters", "active_lanes"]
     clocks = v[:4].sum()
     rep = {"lib": os.path.basename(path), "kernel_ms": st.kernel_ms / max(st.launches, 1),
@@ -60,4 +60,17 @@ for path in libs:
     rep["compacted_rounds_per_iter"] = round(v[13] / seg_iters / 64.0, 3)
     # culled scan: blocks whose bound some lane's line passed (they are scanned; the others skipped)
     rep["cull_pass_blocks_per_iter"] = round(v[14] / seg_iters, 2)
+    # hit_world's parts (lane-mode calls: diag_hw of rtx_diag.h), shares of the four section clocks
+    hw = v[16:19].sum()
+    for k, nm in enumerate(["walk", "scan", "resolve"]):
+        rep[f"hw_{nm}_share"] = round(v[16 + k] / clocks, 4)
+        rep[f"hw_{nm}_of_hit_world"] = round(v[16 + k] / max(hw, 1), 4)
+    # the layer-grid walk's balance, per walk of a wave: the slowest lane's
+    # steps, the steps of all lanes, the rounds the wave ran
+    walks = max(v[20], 1)
+    rep["walks"] = int(v[20])
+    rep["walk_max_steps"] = round(v[21] / walks, 3)
+    rep["walk_sum_steps"] = round(v[22] / walks, 2)
+    rep["walk_rounds"] = round(v[23] / walks, 3)
+    rep["walk_lane_util"] = round(v[22] / max(64 * v[23], 1), 4)
     print(json.dumps(rep), flush=True)
