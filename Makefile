@@ -37,7 +37,11 @@ $(LIBDIR)/rtx_api.o: $(SRC)/rtx_api.hip $(LIBSRCS) | $(LIBDIR)
 $(LIBDIR)/rtx_host.o: $(SRC)/rtx_host.cpp include/rtx.h | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(LIBDIR)/rtx_kernels.o $(LIBDIR)/rtx_api.o $(LIBDIR)/rtx_host.o
+# the group layer (several devices, one frame): host code only, no kernels
+$(LIBDIR)/rtx_group.o: $(SRC)/rtx_group.hip $(SRC)/rtx_group_plan.h $(HDRS) | $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(LIB): $(LIBDIR)/rtx_kernels.o $(LIBDIR)/rtx_api.o $(LIBDIR)/rtx_host.o $(LIBDIR)/rtx_group.o
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^
 
 $(CLI): $(SRC)/rtx_cli.cpp $(SRC)/rtx_app.cpp include/rtx.h include/rtx_app.hpp $(LIB) | $(BINDIR)
@@ -82,12 +86,13 @@ VDIR := $(LIBDIR)/variants
 
 variants: $(foreach v,$(VARIANTS),$(VDIR)/librtx_$(v).so)
 
-$(VDIR)/librtx_%.so: $(SRC)/rtx_kernels.hip $(SRC)/rtx_api.hip $(SRC)/rtx_host.cpp $(HDRS) Makefile
+$(VDIR)/librtx_%.so: $(SRC)/rtx_kernels.hip $(SRC)/rtx_api.hip $(SRC)/rtx_host.cpp $(SRC)/rtx_group.hip $(SRC)/rtx_group_plan.h $(HDRS) Makefile
 	mkdir -p $(VDIR)/$*
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS_$*) -c $(SRC)/rtx_kernels.hip -o $(VDIR)/$*/k.o
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS_$*) -DRTX_SRC_SHA='"$(SRC_SHA)"' -DRTX_VARIANT='"$*"' -c $(SRC)/rtx_api.hip -o $(VDIR)/$*/a.o
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS_$*) -c $(SRC)/rtx_host.cpp -o $(VDIR)/$*/h.o
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(VDIR)/$*/k.o $(VDIR)/$*/a.o $(VDIR)/$*/h.o
+	$(HIPCC) $(HIPFLAGS) $(VFLAGS_$*) -c $(SRC)/rtx_group.hip -o $(VDIR)/$*/g.o
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(VDIR)/$*/k.o $(VDIR)/$*/a.o $(VDIR)/$*/h.o $(VDIR)/$*/g.o
 
 adhoc:
 	@test -n "$(V)" || (echo "usage: make adhoc V=name VFLAGS=..." && false)
@@ -95,6 +100,7 @@ adhoc:
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $(SRC)/rtx_kernels.hip -o $(VDIR)/$(V)/k.o
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -DRTX_VARIANT='"$(V)"' -c $(SRC)/rtx_api.hip -o $(VDIR)/$(V)/a.o
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $(SRC)/rtx_host.cpp -o $(VDIR)/$(V)/h.o
-	$(HIPCC) $(HIPFLAGS) -shared -o $(VDIR)/librtx_$(V).so $(VDIR)/$(V)/k.o $(VDIR)/$(V)/a.o $(VDIR)/$(V)/h.o
+	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $(SRC)/rtx_group.hip -o $(VDIR)/$(V)/g.o
+	$(HIPCC) $(HIPFLAGS) -shared -o $(VDIR)/librtx_$(V).so $(VDIR)/$(V)/k.o $(VDIR)/$(V)/a.o $(VDIR)/$(V)/h.o $(VDIR)/$(V)/g.o
 
 .PHONY: variants adhoc

@@ -40,6 +40,10 @@ extern "C" {
 
 #define RTX_VERSION 145 /* 1.4.5 */
 /* ABI notes.
+ *  1.4.5 (later builds, no version bump): the rtx_group entry points (one
+ *         frame across several devices); purely additive — no struct and no
+ *         earlier entry point changed — so a caller probes for the symbol
+ *         (dlsym "rtx_group_create") rather than for a version.
  *  1.4.5: schedule defaults tier1_bar_low 2.0 -> 1.8, promote_low 300 ->
  *         500 (the R = 4 share with the layer grid, S6k-S6l) and
  *         refill_chunk 16 -> 64 (the queue in pixel tiles, S6t-S6u); private
@@ -349,6 +353,72 @@ RTX_API void *rtx_framebuffer(rtx_ctx *ctx);
 /* Copy the context framebuffer to host memory (synchronous). The reference
  * never reads results back; this is the image-output contract (§8f-1). */
 RTX_API int rtx_download(rtx_ctx *ctx, float *host_rgba, size_t bytes);
+
+/* ---- one frame across several devices -------------------
+ * A group owns n contexts ("members"), their buffers and the gather, in one
+ * process driven by one host thread. Member i renders part i of n of
+ * rtx_render_rows' partition; member 0 is the root: it holds the gathered
+ * buffer [n][max_rows][width] and the image [height][width] on its device.
+ * `devices` is either all distinct (one member per GPU) or all equal (a
+ * rehearsal of the same partition, buffers and assembly on one GPU: the
+ * members then share the root member's stream, so their renders run one after
+ * another — the render is a persistent kernel sized to the device's resident
+ * waves and two of them must not compete for it). Anything else, n == 0,
+ * n > RTX_GROUP_MAX, a null pointer, a negative device or an unknown mode is
+ * RTX_ERR_INVALID, decided before any HIP call.
+ * Transport of the gather:
+ *   RTX_GATHER_COPY  the root's stream waits for each member's "rendered"
+ *                    event and pulls its rows (hipMemcpyPeerAsync; a
+ *                    device-to-device copy on one device). Any valid list.
+ *   RTX_GATHER_RCCL  one ncclGroupStart/End of every other member's ncclSend
+ *                    (on its own stream) and the root's ncclRecv into the
+ *                    gathered slots. Needs distinct devices. RCCL is loaded at
+ *                    run time (dlopen "librccl.so.1": the library itself does
+ *                    not link it); a failed load is RTX_ERR_STATE with the
+ *                    loader's message.
+ *   RTX_GATHER_AUTO  RCCL for members on more than one device, else copies
+ *                    (one member: it renders straight into the image).
+ * The image equals the one-context frame bit for bit (the seed depends only
+ * on the global pixel). Not thread-safe, like a context. */
+typedef struct rtx_group rtx_group;
+enum { RTX_GATHER_AUTO = 0, RTX_GATHER_RCCL = 1, RTX_GATHER_COPY = 2 };
+#define RTX_GROUP_MAX 64
+
+RTX_API int rtx_group_create(const int *devices, uint32_t n, int gather_mode, rtx_group **out);
+RTX_API void rtx_group_destroy(rtx_group *g);
+/* Members (0 for NULL). */
+RTX_API uint32_t rtx_group_size(rtx_group *g);
+/* Member's context, borrowed: for its schedule, scan mode (before
+ * rtx_group_upload_world) and stats. Its stream, world and frame belong to
+ * the group. NULL if out of range. */
+RTX_API rtx_ctx *rtx_group_ctx(rtx_group *g, uint32_t member);
+/* The transport in use: RTX_GATHER_RCCL or RTX_GATHER_COPY (AUTO resolved). */
+RTX_API int rtx_group_gather_mode(rtx_group *g);
+/* ncclGetVersion's code of the RCCL the group loaded, 0 if it loaded none. */
+RTX_API int rtx_group_rccl_version(rtx_group *g);
+/* rtx_upload_world / rtx_set_frame on every member. */
+RTX_API int rtx_group_upload_world(rtx_group *g, const rtx_world *w);
+RTX_API int rtx_group_set_frame(rtx_group *g, const rtx_frame *f);
+/* Every member's rows (tiles of tile_rows rows; a member that owns none
+ * launches nothing), the gather, then the de-interleave on the root's
+ * stream. Asynchronous: no host wait once the buffers fit the frame size and
+ * tile_rows (they are resized like the context framebuffer when those change). */
+RTX_API int rtx_group_render(rtx_group *g, uint32_t tile_rows);
+/* Wait for every member. The first failing member's error (RTX_ERR_INCOMPLETE
+ * included) is returned, its index in rtx_last_error(). */
+RTX_API int rtx_group_sync(rtx_group *g);
+/* Device pointer of the image (width*height float4) on member 0's device, or
+ * NULL before the first rtx_group_render. */
+RTX_API void *rtx_group_image(rtx_group *g);
+/* rtx_group_sync, then the image to host memory. */
+RTX_API int rtx_group_download(rtx_group *g, float *host_rgba, size_t bytes);
+/* HIP-event times of the last frame, after rtx_group_sync / _download:
+ * render_ms[n] each member's render (0 for a member without rows), the gather
+ * and the de-interleave on the root's stream. NULL outputs are skipped.
+ * Members sharing a device run one after another: their times add up and say
+ * nothing about scaling. */
+RTX_API int rtx_group_get_times(rtx_group *g, double *render_ms, double *gather_ms,
+                                double *deinterleave_ms);
 
 /* ---- device buffers (for callers without their own allocator) ----------
  * Ordered on the context stream; copies are synchronous. d_ptr from

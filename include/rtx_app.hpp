@@ -29,6 +29,10 @@ public:
     // ~ CDx11Base::Initialize(HWND, HINSTANCE) (CSVersion/Dx11Base.cpp:23-132):
     // creates the device context, then calls LoadContent.
     bool Initialize(int hip_device);
+    // One frame across several devices (rtx_group, include/rtx.h): member i of
+    // `devices` renders part i; all distinct devices, or all equal for the
+    // one-GPU rehearsal. LoadContent / Update / Render then go through the group.
+    bool Initialize(const std::vector<int> &devices, int gather_mode = RTX_GATHER_AUTO);
     // ~ CDx11Base::Terminate (CSVersion/Dx11Base.cpp:134-152).
     void Terminate();
 
@@ -37,11 +41,15 @@ public:
     virtual void Update() = 0;
     virtual void Render() = 0;
 
+    // The context; with a group, member 0's (the root).
     rtx_ctx *context() const { return m_ctx; }
+    // The group, or null for a single context.
+    rtx_group *group() const { return m_group; }
     const std::string &last_error() const { return m_error; }
 
 protected:
-    rtx_ctx *m_ctx = nullptr;
+    rtx_ctx *m_ctx = nullptr;      // owned, or borrowed from m_group
+    rtx_group *m_group = nullptr;
     std::string m_error;
 };
 
@@ -68,6 +76,8 @@ struct AppConfig {
     // rtx_world_from_worlddef; Update fills a PerFrame and hands it to
     // rtx_frame_from_perframe — DxCSApp's data path byte for byte.
     bool cbuffers = false;
+    // With a group (RtxBase::Initialize(devices)): rows per interleaved tile.
+    uint32_t tile_rows = 5;
 };
 
 // The reference's constant-buffer byte layouts (HLSL packing: float4 rows).

@@ -236,6 +236,11 @@ rtx::KScene scene_of(const rtx_ctx *c) {
 
 }  // namespace
 
+namespace rtx {  // for rtx_group.hip (rtx_internal.h)
+int api_fail(int code, const char *msg) { return fail(code, msg); }
+hipStream_t ctx_stream(const ::rtx_ctx *c) { return c->stream; }
+}  // namespace rtx
+
 extern "C" {
 
 int rtx_version(void) { return RTX_VERSION; }

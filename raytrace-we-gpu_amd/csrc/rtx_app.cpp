@@ -13,7 +13,8 @@ namespace rtx {
 // Derived classes call Terminate() in their own destructor (UnloadContent
 // is virtual); the base only releases a context still held.
 RtxBase::~RtxBase() {
-    if (m_ctx) rtx_destroy(m_ctx);
+    if (m_group) rtx_group_destroy(m_group);
+    else if (m_ctx) rtx_destroy(m_ctx);
 }
 
 bool RtxBase::Initialize(int hip_device) {
@@ -26,10 +27,23 @@ bool RtxBase::Initialize(int hip_device) {
     return LoadContent();
 }
 
+bool RtxBase::Initialize(const std::vector<int> &devices, int gather_mode) {
+    if (m_ctx) return true;
+    if (rtx_group_create(devices.data(), (uint32_t)devices.size(), gather_mode, &m_group) != RTX_OK) {
+        m_error = rtx_last_error();
+        m_group = nullptr;
+        return false;
+    }
+    m_ctx = rtx_group_ctx(m_group, 0);
+    return LoadContent();
+}
+
 void RtxBase::Terminate() {
     if (!m_ctx) return;
     UnloadContent();
-    rtx_destroy(m_ctx);
+    if (m_group) rtx_group_destroy(m_group);  // its members' contexts with it
+    else rtx_destroy(m_ctx);
+    m_group = nullptr;
     m_ctx = nullptr;
 }
 
@@ -88,7 +102,8 @@ bool RtxCSApp::LoadContent() {
             return m_ok = false;
         }
         m_count = w.count;
-        if (rtx_upload_world(m_ctx, &w) != RTX_OK) {  // CreateBuffer(WorldDef, IMMUTABLE) (:393-413)
+        // CreateBuffer(WorldDef, IMMUTABLE) (:393-413)
+        if ((m_group ? rtx_group_upload_world(m_group, &w) : rtx_upload_world(m_ctx, &w)) != RTX_OK) {
             m_error = rtx_last_error();
             return m_ok = false;
         }
@@ -122,7 +137,7 @@ bool RtxCSApp::LoadContent() {
     w.mat_types = m_mat_types.data();
     w.mat_values = m_mat_values.data();
     // CreateBuffer(WorldDef, IMMUTABLE)  (DxCSApp.cpp:393-413)
-    if (rtx_upload_world(m_ctx, &w) != RTX_OK) {
+    if ((m_group ? rtx_group_upload_world(m_group, &w) : rtx_upload_world(m_ctx, &w)) != RTX_OK) {
         m_error = rtx_last_error();
         return m_ok = false;
     }
@@ -154,7 +169,7 @@ void RtxCSApp::Update() {
     m_frame.flags = m_cfg.lambert_guard ? RTX_FRAME_LAMBERT_GUARD : 0u;
     if (rc == RTX_OK && m_cfg.lens_aperture > 0.0f) rc = rtx_camera_set_aperture(&m_frame, m_cfg.lens_aperture);
     ++m_frame_count;
-    if (rc != RTX_OK || rtx_set_frame(m_ctx, &m_frame) != RTX_OK) {
+    if (rc != RTX_OK || (m_group ? rtx_group_set_frame(m_group, &m_frame) : rtx_set_frame(m_ctx, &m_frame)) != RTX_OK) {
         m_error = rtx_last_error();
         m_ok = false;
     }
@@ -163,7 +178,7 @@ void RtxCSApp::Update() {
 void RtxCSApp::Render() {
     // Dispatch(32,32,1)  (DxCSApp.cpp:524)
     if (!m_ok) return;
-    if (rtx_render(m_ctx) != RTX_OK) {
+    if ((m_group ? rtx_group_render(m_group, m_cfg.tile_rows) : rtx_render(m_ctx)) != RTX_OK) {
         m_error = rtx_last_error();
         m_ok = false;
     }
@@ -171,7 +186,8 @@ void RtxCSApp::Render() {
 
 bool RtxCSApp::Download(std::vector<float> &rgba) {
     rgba.resize(4 * (size_t)m_cfg.width * m_cfg.height);
-    if (rtx_download(m_ctx, rgba.data(), rgba.size() * sizeof(float)) != RTX_OK) {
+    const size_t bytes = rgba.size() * sizeof(float);
+    if ((m_group ? rtx_group_download(m_group, rgba.data(), bytes) : rtx_download(m_ctx, rgba.data(), bytes)) != RTX_OK) {
         m_error = rtx_last_error();
         return false;
     }

@@ -8,6 +8,13 @@
 //           [--rng chain|per-sample] [--frames K] [--device N]
 //           [--aperture A] [--accumulate] [--lambert-guard]
 //           [--reference-frame] [--pfm out.pfm] [--ppm out.ppm]
+//           [--gpus N | --devices a,b,c] [--gather auto|rccl|copy] [--tile-rows T]
+// --gpus N renders each frame across devices 0..N-1 (rtx_group: interleaved
+// tiles of T rows, default 5, one gather to device 0); --devices names them,
+// and a repeated device (0,0,0) rehearses the same split on one GPU, its
+// members one after another. The JSON line then also carries n_gpus, devices,
+// gather, rccl_version, per_member (rows, render_ms of the last frame),
+// gather_ms and deinterleave_ms, and its counters are summed over the members.
 // --accumulate renders the K frames progressively (rtx_accumulate) instead
 // of K independent frames; --aperture enables the thin lens;
 // --lambert-guard the near-zero diffuse guard (RTX_FRAME_LAMBERT_GUARD).
@@ -17,6 +24,7 @@
 // own WorldDef and PerFrame cbuffer bytes through rtx_world_from_worlddef /
 // rtx_frame_from_perframe; a preset: every other option, before or after
 // it, overrides its values.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -32,7 +40,8 @@ static void usage() {
                  "               [--scene rtiow9|rtiow11|test|ps|random:EXT[:MAX]] [--simple-camera]\n"
                  "               [--rng chain|per-sample] [--frames K] [--device N]\n"
                  "               [--aperture A] [--accumulate] [--lambert-guard] [--reference-frame]\n"
-                 "               [--pfm FILE] [--ppm FILE]\n");
+                 "               [--pfm FILE] [--ppm FILE]\n"
+                 "               [--gpus N | --devices a,b,c] [--gather auto|rccl|copy] [--tile-rows T]\n");
 }
 
 int main(int argc, char **argv) {
@@ -53,6 +62,9 @@ int main(int argc, char **argv) {
     int frames = 1, device = 0;
     bool accumulate = false;
     std::string pfm, ppm;
+    std::vector<int> devices;  // non-empty: a group
+    int gather = RTX_GATHER_AUTO;
+    bool group_opts = false;   // --gather / --tile-rows given
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * {
@@ -74,6 +86,41 @@ int main(int argc, char **argv) {
         else if (a == "--aperture") cfg.lens_aperture = (float)std::atof(next());
         else if (a == "--accumulate") accumulate = true;
         else if (a == "--lambert-guard") cfg.lambert_guard = true;
+        else if (a == "--gpus") {
+            const int n = std::atoi(next());
+            if (n < 1 || n > RTX_GROUP_MAX) {
+                usage();
+                return 2;
+            }
+            devices.clear();
+            for (int d = 0; d < n; ++d) devices.push_back(d);
+        } else if (a == "--devices") {
+            devices.clear();
+            const std::string list = next();
+            for (size_t pos = 0; pos <= list.size();) {
+                const size_t comma = std::min(list.find(',', pos), list.size());
+                const std::string item = list.substr(pos, comma - pos);
+                if (item.empty() || item.find_first_not_of("0123456789") != std::string::npos) {
+                    usage();
+                    return 2;
+                }
+                devices.push_back(std::atoi(item.c_str()));
+                pos = comma + 1;
+            }
+        } else if (a == "--gather") {
+            const std::string m = next();
+            group_opts = true;
+            if (m == "auto") gather = RTX_GATHER_AUTO;
+            else if (m == "rccl") gather = RTX_GATHER_RCCL;
+            else if (m == "copy") gather = RTX_GATHER_COPY;
+            else {
+                usage();
+                return 2;
+            }
+        } else if (a == "--tile-rows") {
+            cfg.tile_rows = (uint32_t)std::atoi(next());
+            group_opts = true;
+        }
         else if (a == "--reference-frame") {
             // a preset, applied before the loop (below): here it only keeps its place
         }
@@ -107,16 +154,37 @@ int main(int argc, char **argv) {
         usage();
         return 2;
     }
+    const bool grouped = !devices.empty();
+    if (group_opts && !grouped) {
+        std::fprintf(stderr, "rtx_cli: --gather and --tile-rows need --gpus or --devices\n");
+        return 2;
+    }
+    if (grouped && accumulate) {
+        std::fprintf(stderr, "rtx_cli: --accumulate with --gpus / --devices is not supported "
+                             "(a group has no progressive accumulation)\n");
+        return 2;
+    }
+    if (grouped && cfg.tile_rows == 0) {
+        usage();
+        return 2;
+    }
     cfg.aspect = (float)cfg.width / (float)cfg.height;
     rtx::RtxCSApp app(cfg);
-    if (!app.Initialize(device)) {
+    if (!(grouped ? app.Initialize(devices, gather) : app.Initialize(device))) {
         std::fprintf(stderr, "rtx_cli: initialize failed: %s\n", app.last_error().c_str());
         return 1;
     }
     app.Update();
     app.Render();  // warm-up frame (also the reference's single frame, main.cpp:38-39)
-    rtx_sync(app.context());
-    rtx_stats_reset(app.context());
+    rtx_group *grp = app.group();
+    const uint32_t members = grp ? rtx_group_size(grp) : 0;
+    if (grp) {
+        rtx_group_sync(grp);
+        for (uint32_t m = 0; m < members; ++m) rtx_stats_reset(rtx_group_ctx(grp, m));
+    } else {
+        rtx_sync(app.context());
+        rtx_stats_reset(app.context());
+    }
     const auto t0 = std::chrono::steady_clock::now();
     for (int k = 0; k < frames; ++k) {
         app.Update();
@@ -129,21 +197,66 @@ int main(int argc, char **argv) {
             app.Render();
         }
     }
-    rtx_sync(app.context());
+    const int sync_rc = grp ? rtx_group_sync(grp) : rtx_sync(app.context());
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (!app.ok()) {
         std::fprintf(stderr, "rtx_cli: render failed: %s\n", app.last_error().c_str());
         return 1;
     }
     rtx_stats st{};
-    rtx_get_stats(app.context(), &st);
-    std::printf("{\"width\": %u, \"height\": %u, \"spp\": %u, \"depth\": %u, \"spheres\": %u, "
-                "\"cbuffers\": %s, \"frames\": %d, \"wall_s\": %.6f, \"kernel_ms\": %.4f, \"msamples_per_s\": %.3f, "
-                "\"segments\": %llu, \"sphere_tests\": %llu}\n",
-                cfg.width, cfg.height, cfg.spp, cfg.depth, app.sphere_count(), cfg.cbuffers ? "true" : "false",
-                frames, wall,
-                st.kernel_ms, (double)st.samples / wall / 1e6, (unsigned long long)st.segments,
-                (unsigned long long)st.sphere_tests);
+    if (grp) {
+        if (sync_rc != RTX_OK) {
+            std::fprintf(stderr, "rtx_cli: render failed: %s\n", rtx_last_error());
+            return 1;
+        }
+        for (uint32_t m = 0; m < members; ++m) {  // the counters, summed over the members
+            rtx_stats s{};
+            if (rtx_get_stats(rtx_group_ctx(grp, m), &s) != RTX_OK) {
+                std::fprintf(stderr, "rtx_cli: member %u stats failed: %s\n", m, rtx_last_error());
+                return 1;
+            }
+            st.kernel_ms += s.kernel_ms;
+            st.launches += s.launches;
+            st.samples += s.samples;
+            st.segments += s.segments;
+            st.sphere_tests += s.sphere_tests;
+        }
+        std::vector<double> render_ms(members, 0.0);
+        double gather_ms = 0.0, deint_ms = 0.0;
+        if (rtx_group_get_times(grp, render_ms.data(), &gather_ms, &deint_ms) != RTX_OK) {
+            std::fprintf(stderr, "rtx_cli: times failed: %s\n", rtx_last_error());
+            return 1;
+        }
+        std::string devs, per;
+        char buf[96];
+        for (uint32_t m = 0; m < members; ++m) {
+            devs += (m ? ", " : "") + std::to_string(devices[m]);
+            std::snprintf(buf, sizeof buf, "%s{\"rows\": %u, \"render_ms\": %.4f}", m ? ", " : "",
+                          rtx_part_rows(cfg.height, cfg.tile_rows, m, members), render_ms[m]);
+            per += buf;
+        }
+        const int ver = rtx_group_rccl_version(grp);
+        const std::string rccl = ver ? "\"" + std::to_string(ver) + "\"" : "null";
+        std::printf("{\"width\": %u, \"height\": %u, \"spp\": %u, \"depth\": %u, \"spheres\": %u, "
+                    "\"cbuffers\": %s, \"frames\": %d, \"wall_s\": %.6f, \"kernel_ms\": %.4f, "
+                    "\"msamples_per_s\": %.3f, \"segments\": %llu, \"sphere_tests\": %llu, "
+                    "\"n_gpus\": %u, \"devices\": [%s], \"gather\": \"%s\", \"rccl_version\": %s, "
+                    "\"tile_rows\": %u, \"per_member\": [%s], \"gather_ms\": %.4f, \"deinterleave_ms\": %.4f}\n",
+                    cfg.width, cfg.height, cfg.spp, cfg.depth, app.sphere_count(), cfg.cbuffers ? "true" : "false",
+                    frames, wall, st.kernel_ms, (double)st.samples / wall / 1e6, (unsigned long long)st.segments,
+                    (unsigned long long)st.sphere_tests, members, devs.c_str(),
+                    rtx_group_gather_mode(grp) == RTX_GATHER_RCCL ? "rccl" : "copy", rccl.c_str(), cfg.tile_rows,
+                    per.c_str(), gather_ms, deint_ms);
+    } else {
+        rtx_get_stats(app.context(), &st);
+        std::printf("{\"width\": %u, \"height\": %u, \"spp\": %u, \"depth\": %u, \"spheres\": %u, "
+                    "\"cbuffers\": %s, \"frames\": %d, \"wall_s\": %.6f, \"kernel_ms\": %.4f, \"msamples_per_s\": %.3f, "
+                    "\"segments\": %llu, \"sphere_tests\": %llu}\n",
+                    cfg.width, cfg.height, cfg.spp, cfg.depth, app.sphere_count(), cfg.cbuffers ? "true" : "false",
+                    frames, wall,
+                    st.kernel_ms, (double)st.samples / wall / 1e6, (unsigned long long)st.segments,
+                    (unsigned long long)st.sphere_tests);
+    }
     if (!pfm.empty() || !ppm.empty()) {
         std::vector<float> img;
         if (!app.Download(img)) {

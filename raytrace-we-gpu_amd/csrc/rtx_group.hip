@@ -1,0 +1,484 @@
+// rtx_group.hip — one frame across several devices through the C-ABI
+// (include/rtx.h rtx_group): n contexts, their buffers and the gather, driven
+// by one host thread. The partition and buffer arithmetic is
+// rtx_group_plan.h's; this file executes that plan on device memory with the
+// single-context entry points (rtx_render_rows, rtx_deinterleave_rows).
+//
+// RCCL is loaded at run time (dlopen), so librtx.so carries no link
+// dependency on it: a single-GPU user pays nothing, and a process that has
+// another RCCL loaded already (torch's) gets that one.
+#include <hip/hip_runtime.h>
+
+#include <dlfcn.h>
+
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/rtx.h"
+#include "rtx_group_plan.h"
+#include "rtx_internal.h"
+
+namespace {
+
+int fail(int code, const std::string &msg) { return rtx::api_fail(code, msg.c_str()); }
+
+int hip_fail(hipError_t e, const char *what) {
+    return fail(RTX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+#define RTXG_HIP(call)                                    \
+    do {                                                  \
+        hipError_t e_ = (call);                           \
+        if (e_ != hipSuccess) return hip_fail(e_, #call); \
+    } while (0)
+
+// The part of RCCL's C interface the gather uses, declared here so that the
+// build needs no RCCL header (rccl.h: ncclResult_t 0 = ncclSuccess,
+// ncclFloat = 7, ncclComm_t an opaque pointer).
+typedef void *nccl_comm;
+constexpr int kNcclFloat = 7;
+struct Rccl {
+    void *handle = nullptr;
+    int (*CommInitAll)(nccl_comm *, int, const int *) = nullptr;
+    int (*CommDestroy)(nccl_comm) = nullptr;
+    int (*GroupStart)() = nullptr;
+    int (*GroupEnd)() = nullptr;
+    int (*Send)(const void *, size_t, int, int, nccl_comm, hipStream_t) = nullptr;
+    int (*Recv)(void *, size_t, int, int, nccl_comm, hipStream_t) = nullptr;
+    int (*GetVersion)(int *) = nullptr;
+    const char *(*GetErrorString)(int) = nullptr;
+};
+
+// dlopen by soname; when the loader's search path does not reach it, beside
+// the HIP runtime this library is already linked to.
+int load_rccl(Rccl &r) {
+    const char *soname = "librccl.so.1";
+    void *h = dlopen(soname, RTLD_NOW | RTLD_LOCAL);
+    std::string why;
+    if (!h) {
+        const char *e = dlerror();
+        why = e ? e : "dlopen failed";
+        Dl_info info;
+        if (dladdr(reinterpret_cast<void *>(&hipGetDeviceCount), &info) && info.dli_fname) {
+            std::string p(info.dli_fname);
+            const size_t slash = p.rfind('/');
+            if (slash != std::string::npos) {
+                p = p.substr(0, slash + 1) + soname;
+                h = dlopen(p.c_str(), RTLD_NOW | RTLD_LOCAL);
+            }
+        }
+    }
+    if (!h) return fail(RTX_ERR_STATE, "rtx_group_create: RCCL not loaded: " + why);
+    const struct {
+        const char *name;
+        void **slot;
+    } syms[] = {{"ncclCommInitAll", reinterpret_cast<void **>(&r.CommInitAll)},
+                {"ncclCommDestroy", reinterpret_cast<void **>(&r.CommDestroy)},
+                {"ncclGroupStart", reinterpret_cast<void **>(&r.GroupStart)},
+                {"ncclGroupEnd", reinterpret_cast<void **>(&r.GroupEnd)},
+                {"ncclSend", reinterpret_cast<void **>(&r.Send)},
+                {"ncclRecv", reinterpret_cast<void **>(&r.Recv)},
+                {"ncclGetVersion", reinterpret_cast<void **>(&r.GetVersion)},
+                {"ncclGetErrorString", reinterpret_cast<void **>(&r.GetErrorString)}};
+    for (const auto &s : syms) {
+        *s.slot = dlsym(h, s.name);
+        if (!*s.slot) {
+            const char *e = dlerror();
+            const std::string msg = std::string("rtx_group_create: RCCL lacks ") + s.name + ": " + (e ? e : "");
+            dlclose(h);
+            return fail(RTX_ERR_STATE, msg);
+        }
+    }
+    r.handle = h;
+    return RTX_OK;
+}
+
+struct Member {
+    int device = 0;
+    rtx_ctx *ctx = nullptr;
+    hipStream_t stream = nullptr;  // the context's; members on one device share the root member's
+    void *d_send = nullptr;        // its rows (members 1 .. n-1)
+    size_t send_bytes = 0;
+    hipEvent_t ev_start = nullptr, ev_rendered = nullptr;
+    bool rendered = false;         // the last frame launched a render for it
+    nccl_comm comm = nullptr;
+};
+
+}  // namespace
+
+struct rtx_group {
+    std::vector<Member> m;
+    bool one_device = false;  // every member on the root's device (the rehearsal)
+    int mode = RTX_GATHER_COPY;
+    Rccl rccl;
+    int rccl_version = 0;
+    rtx_frame frame{};
+    bool have_frame = false;
+    rtx::GroupPlan plan;      // of the buffers below (n == 0: none yet)
+    bool direct = false;      // one member, copies: it renders straight into the image
+    void *d_gathered = nullptr;
+    void *d_image = nullptr;
+    hipEvent_t ev_g0 = nullptr, ev_g1 = nullptr, ev_d0 = nullptr, ev_d1 = nullptr;
+    bool launched = false;    // a frame's events are recorded
+    bool gathered_once = false;
+    bool have_times = false;
+    std::vector<double> render_ms;
+    double gather_ms = 0.0, deint_ms = 0.0;
+};
+
+namespace {
+
+int nccl_fail(const rtx_group *g, int rc, const char *what) {
+    return fail(RTX_ERR_HIP, std::string(what) + ": " + g->rccl.GetErrorString(rc));
+}
+
+void free_buffers(rtx_group *g) {
+    for (Member &mb : g->m) {
+        if (mb.d_send) {
+            (void)hipSetDevice(mb.device);
+            (void)hipFree(mb.d_send);
+        }
+        mb.d_send = nullptr;
+        mb.send_bytes = 0;
+    }
+    if (!g->m.empty()) (void)hipSetDevice(g->m[0].device);
+    (void)hipFree(g->d_gathered);
+    (void)hipFree(g->d_image);
+    g->d_gathered = g->d_image = nullptr;
+    g->plan = rtx::GroupPlan();
+}
+
+// Every member's stream drained (before buffers are replaced).
+int drain(rtx_group *g) {
+    for (Member &mb : g->m) {
+        RTXG_HIP(hipSetDevice(mb.device));
+        RTXG_HIP(hipStreamSynchronize(mb.stream));
+    }
+    return RTX_OK;
+}
+
+// Buffers for this frame size and tile_rows (render_impl's treatment of d_fb:
+// another size drains the streams and replaces them).
+int ensure_buffers(rtx_group *g, uint32_t tile_rows) {
+    const uint32_t n = (uint32_t)g->m.size();
+    if (g->plan.same(n, g->frame.width, g->frame.height, tile_rows)) return RTX_OK;
+    int rc = drain(g);
+    if (rc) return rc;
+    free_buffers(g);
+    g->gathered_once = false;
+    const rtx::GroupPlan plan = rtx::make_group_plan(n, g->frame.width, g->frame.height, tile_rows);
+    g->direct = n == 1 && g->mode == RTX_GATHER_COPY;
+    RTXG_HIP(hipSetDevice(g->m[0].device));
+    RTXG_HIP(hipMalloc(&g->d_image, plan.image_bytes));
+    if (!g->direct) RTXG_HIP(hipMalloc(&g->d_gathered, plan.gathered_bytes));
+    for (uint32_t i = 1; i < n; ++i) {
+        Member &mb = g->m[i];
+        RTXG_HIP(hipSetDevice(mb.device));
+        // a member without rows keeps a (small) buffer: the collective names it
+        RTXG_HIP(hipMalloc(&mb.d_send, plan.send_bytes[i] ? plan.send_bytes[i] : rtx::kGroupPixelBytes));
+        mb.send_bytes = plan.send_bytes[i];
+    }
+    g->plan = plan;
+    return RTX_OK;
+}
+
+void destroy_group(rtx_group *g) {
+    for (Member &mb : g->m) {
+        if (!mb.ctx) continue;
+        (void)hipSetDevice(mb.device);
+        (void)hipStreamSynchronize(mb.stream);
+    }
+    for (Member &mb : g->m)
+        if (mb.comm) (void)g->rccl.CommDestroy(mb.comm);
+    free_buffers(g);
+    if (!g->m.empty() && g->m[0].ctx) (void)hipSetDevice(g->m[0].device);
+    for (hipEvent_t e : {g->ev_g0, g->ev_g1, g->ev_d0, g->ev_d1})
+        if (e) (void)hipEventDestroy(e);
+    // the root last: the members on its device launch on its stream
+    for (size_t i = g->m.size(); i-- > 0;) {
+        Member &mb = g->m[i];
+        if (!mb.ctx) continue;
+        (void)hipSetDevice(mb.device);
+        if (mb.ev_start) (void)hipEventDestroy(mb.ev_start);
+        if (mb.ev_rendered) (void)hipEventDestroy(mb.ev_rendered);
+        (void)rtx_use_own_stream(mb.ctx);
+        rtx_destroy(mb.ctx);
+    }
+    // the RCCL handle stays loaded: its communicators' teardown may outlive this call
+    delete g;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rtx_group_create(const int *devices, uint32_t n, int gather_mode, rtx_group **out) {
+    // arguments first: nothing below this block runs for a bad one, and
+    // nothing in it touches HIP
+    if (!out) return fail(RTX_ERR_INVALID, "rtx_group_create: null out");
+    *out = nullptr;
+    if (!devices) return fail(RTX_ERR_INVALID, "rtx_group_create: null devices");
+    if (n == 0) return fail(RTX_ERR_INVALID, "rtx_group_create: n is 0");
+    if (n > RTX_GROUP_MAX)
+        return fail(RTX_ERR_INVALID, "rtx_group_create: n " + std::to_string(n) + " above RTX_GROUP_MAX (" +
+                                         std::to_string(RTX_GROUP_MAX) + ")");
+    if (gather_mode != RTX_GATHER_AUTO && gather_mode != RTX_GATHER_RCCL && gather_mode != RTX_GATHER_COPY)
+        return fail(RTX_ERR_INVALID, "rtx_group_create: unknown gather_mode " + std::to_string(gather_mode));
+    bool all_equal = true, all_distinct = true;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (devices[i] < 0)
+            return fail(RTX_ERR_INVALID, "rtx_group_create: devices[" + std::to_string(i) + "] is negative");
+        if (devices[i] != devices[0]) all_equal = false;
+        for (uint32_t j = 0; j < i; ++j)
+            if (devices[j] == devices[i]) all_distinct = false;
+    }
+    if (!all_equal && !all_distinct)
+        return fail(RTX_ERR_INVALID, "rtx_group_create: devices must be all distinct or all equal (the one-GPU "
+                                     "rehearsal)");
+    if (gather_mode == RTX_GATHER_RCCL && !all_distinct)
+        return fail(RTX_ERR_INVALID, "rtx_group_create: gather_mode RTX_GATHER_RCCL needs distinct devices");
+
+    rtx_group *g = new (std::nothrow) rtx_group();
+    if (!g) return fail(RTX_ERR_NOMEM, "rtx_group_create: out of host memory");
+    g->one_device = all_equal;
+    g->mode = gather_mode == RTX_GATHER_AUTO ? (all_equal ? RTX_GATHER_COPY : RTX_GATHER_RCCL) : gather_mode;
+    g->m.resize(n);
+    g->render_ms.assign(n, 0.0);
+    int rc = RTX_OK;
+    hipError_t e = hipSuccess;
+    for (uint32_t i = 0; i < n && rc == RTX_OK; ++i) {
+        Member &mb = g->m[i];
+        mb.device = devices[i];
+        rc = rtx_create(mb.device, &mb.ctx);
+        if (rc != RTX_OK) {
+            mb.ctx = nullptr;
+            const std::string why = rtx_last_error();
+            fail(rc, "rtx_group_create: member " + std::to_string(i) + ": " + why);
+            break;
+        }
+        // one stream per device: two persistent renders must not compete for
+        // one device's resident waves, so the rehearsal's members queue up
+        if (i > 0 && all_equal) rc = rtx_set_stream(mb.ctx, g->m[0].stream);
+        mb.stream = rtx::ctx_stream(mb.ctx);
+        e = hipSetDevice(mb.device);
+        if (e == hipSuccess) e = hipEventCreate(&mb.ev_start);
+        if (e == hipSuccess) e = hipEventCreate(&mb.ev_rendered);
+        if (e != hipSuccess) rc = hip_fail(e, "rtx_group_create: hipEventCreate");
+    }
+    if (rc == RTX_OK) {
+        e = hipSetDevice(g->m[0].device);
+        for (hipEvent_t *ev : {&g->ev_g0, &g->ev_g1, &g->ev_d0, &g->ev_d1})
+            if (e == hipSuccess) e = hipEventCreate(ev);
+        if (e != hipSuccess) rc = hip_fail(e, "rtx_group_create: hipEventCreate");
+    }
+    if (rc == RTX_OK && g->mode == RTX_GATHER_COPY && !all_equal) {
+        // direct peer copies where the devices allow them (hipMemcpyPeerAsync
+        // stages through the host otherwise)
+        for (uint32_t i = 1; i < n; ++i) {
+            int can = 0;
+            if (hipDeviceCanAccessPeer(&can, g->m[0].device, g->m[i].device) == hipSuccess && can)
+                (void)hipDeviceEnablePeerAccess(g->m[i].device, 0);
+            (void)hipGetLastError();  // "already enabled" is no failure
+        }
+    }
+    if (rc == RTX_OK && g->mode == RTX_GATHER_RCCL) {
+        rc = load_rccl(g->rccl);
+        if (rc == RTX_OK) {
+            (void)g->rccl.GetVersion(&g->rccl_version);
+            std::vector<nccl_comm> comms(n, nullptr);
+            const int nrc = g->rccl.CommInitAll(comms.data(), (int)n, devices);
+            if (nrc != 0) rc = nccl_fail(g, nrc, "rtx_group_create: ncclCommInitAll");
+            else
+                for (uint32_t i = 0; i < n; ++i) g->m[i].comm = comms[i];
+        }
+    }
+    if (rc != RTX_OK) {
+        const std::string why = rtx_last_error();
+        destroy_group(g);
+        return fail(rc, why);
+    }
+    *out = g;
+    return RTX_OK;
+}
+
+void rtx_group_destroy(rtx_group *g) {
+    if (g) destroy_group(g);
+}
+
+uint32_t rtx_group_size(rtx_group *g) { return g ? (uint32_t)g->m.size() : 0; }
+
+rtx_ctx *rtx_group_ctx(rtx_group *g, uint32_t member) {
+    return (g && member < g->m.size()) ? g->m[member].ctx : nullptr;
+}
+
+int rtx_group_gather_mode(rtx_group *g) { return g ? g->mode : RTX_GATHER_AUTO; }
+
+int rtx_group_rccl_version(rtx_group *g) { return g ? g->rccl_version : 0; }
+
+int rtx_group_upload_world(rtx_group *g, const rtx_world *w) {
+    if (!g || !w) return fail(RTX_ERR_INVALID, "rtx_group_upload_world: null argument");
+    for (size_t i = 0; i < g->m.size(); ++i) {
+        const int rc = rtx_upload_world(g->m[i].ctx, w);
+        if (rc != RTX_OK) {
+            const std::string why = rtx_last_error();
+            return fail(rc, "rtx_group_upload_world: member " + std::to_string(i) + ": " + why);
+        }
+    }
+    return RTX_OK;
+}
+
+int rtx_group_set_frame(rtx_group *g, const rtx_frame *f) {
+    if (!g || !f) return fail(RTX_ERR_INVALID, "rtx_group_set_frame: null argument");
+    for (size_t i = 0; i < g->m.size(); ++i) {
+        const int rc = rtx_set_frame(g->m[i].ctx, f);
+        if (rc != RTX_OK) {
+            const std::string why = rtx_last_error();
+            return fail(rc, "rtx_group_set_frame: member " + std::to_string(i) + ": " + why);
+        }
+    }
+    g->frame = *f;
+    g->have_frame = true;
+    return RTX_OK;
+}
+
+int rtx_group_render(rtx_group *g, uint32_t tile_rows) {
+    if (!g) return fail(RTX_ERR_INVALID, "rtx_group_render: null group");
+    if (tile_rows == 0) return fail(RTX_ERR_INVALID, "rtx_group_render: tile_rows is 0");
+    if (!g->have_frame) return fail(RTX_ERR_STATE, "rtx_group_render: no frame set");
+    int rc = ensure_buffers(g, tile_rows);
+    if (rc) return rc;
+    const rtx::GroupPlan &plan = g->plan;
+    const uint32_t n = plan.n;
+    Member &root = g->m[0];
+    g->have_times = false;
+
+    // every member's render, one after the other from this thread: each is
+    // asynchronous on its member's stream
+    for (uint32_t i = 0; i < n; ++i) {
+        Member &mb = g->m[i];
+        mb.rendered = false;
+        if (!plan.renders(i)) continue;
+        RTXG_HIP(hipSetDevice(mb.device));
+        // its send buffer is free once the root has pulled the last frame's rows
+        if (i > 0 && !g->one_device && g->mode == RTX_GATHER_COPY && g->gathered_once)
+            RTXG_HIP(hipStreamWaitEvent(mb.stream, g->ev_g1, 0));
+        void *d_out = i > 0 ? mb.d_send : (g->direct ? g->d_image : g->d_gathered);
+        RTXG_HIP(hipEventRecord(mb.ev_start, mb.stream));
+        rc = rtx_render_rows(mb.ctx, tile_rows, i, n, d_out);
+        if (rc != RTX_OK) {
+            const std::string why = rtx_last_error();
+            return fail(rc, "rtx_group_render: member " + std::to_string(i) + ": " + why);
+        }
+        RTXG_HIP(hipSetDevice(mb.device));
+        RTXG_HIP(hipEventRecord(mb.ev_rendered, mb.stream));
+        mb.rendered = true;
+    }
+
+    // the gather, on the root's stream
+    RTXG_HIP(hipSetDevice(root.device));
+    RTXG_HIP(hipEventRecord(g->ev_g0, root.stream));
+    if (g->mode == RTX_GATHER_COPY) {
+        for (const rtx::GroupOp &op : plan.ops) {
+            if (op.bytes == 0) continue;
+            Member &mb = g->m[op.member];
+            char *dst = static_cast<char *>(g->d_gathered) + op.dst_off;
+            RTXG_HIP(hipStreamWaitEvent(root.stream, mb.ev_rendered, 0));
+            if (mb.device == root.device)
+                RTXG_HIP(hipMemcpyAsync(dst, mb.d_send, op.bytes, hipMemcpyDeviceToDevice, root.stream));
+            else
+                RTXG_HIP(hipMemcpyPeerAsync(dst, root.device, mb.d_send, mb.device, op.bytes, root.stream));
+        }
+    } else {
+        // what ncclGather does inside, with the symbols every RCCL has
+        int nrc = g->rccl.GroupStart();
+        if (nrc != 0) return nccl_fail(g, nrc, "rtx_group_render: ncclGroupStart");
+        for (const rtx::GroupOp &op : plan.ops) {
+            Member &mb = g->m[op.member];
+            const size_t floats = op.bytes / sizeof(float);
+            char *dst = static_cast<char *>(g->d_gathered) + op.dst_off;
+            (void)hipSetDevice(mb.device);
+            if (nrc == 0) nrc = g->rccl.Send(mb.d_send, floats, kNcclFloat, 0, mb.comm, mb.stream);
+            (void)hipSetDevice(root.device);
+            if (nrc == 0) nrc = g->rccl.Recv(dst, floats, kNcclFloat, (int)op.member, root.comm, root.stream);
+        }
+        const int erc = g->rccl.GroupEnd();  // always closed, also after a failed call inside
+        if (nrc != 0) return nccl_fail(g, nrc, "rtx_group_render: ncclSend/ncclRecv");
+        if (erc != 0) return nccl_fail(g, erc, "rtx_group_render: ncclGroupEnd");
+        RTXG_HIP(hipSetDevice(root.device));
+    }
+    RTXG_HIP(hipEventRecord(g->ev_g1, root.stream));
+    g->gathered_once = true;
+
+    // the de-interleave, after the gather on the same stream
+    RTXG_HIP(hipEventRecord(g->ev_d0, root.stream));
+    if (!g->direct) {
+        rc = rtx_deinterleave_rows(root.ctx, g->d_gathered, plan.width, plan.height, plan.tile_rows, n, g->d_image);
+        if (rc != RTX_OK) return rc;
+        RTXG_HIP(hipSetDevice(root.device));
+    }
+    RTXG_HIP(hipEventRecord(g->ev_d1, root.stream));
+    g->launched = true;
+    return RTX_OK;
+}
+
+int rtx_group_sync(rtx_group *g) {
+    if (!g) return fail(RTX_ERR_INVALID, "rtx_group_sync: null group");
+    int first = RTX_OK;
+    std::string why;
+    for (size_t i = 0; i < g->m.size(); ++i) {  // every member, also after a failure
+        const int rc = rtx_sync(g->m[i].ctx);
+        if (rc != RTX_OK && first == RTX_OK) {
+            first = rc;
+            why = "rtx_group_sync: member " + std::to_string(i) + ": " + rtx_last_error();
+        }
+    }
+    if (first != RTX_OK) return fail(first, why);
+    if (g->launched && !g->have_times) {
+        float t = 0.0f;
+        for (size_t i = 0; i < g->m.size(); ++i) {
+            Member &mb = g->m[i];
+            g->render_ms[i] = 0.0;
+            if (!mb.rendered) continue;
+            RTXG_HIP(hipSetDevice(mb.device));
+            RTXG_HIP(hipEventElapsedTime(&t, mb.ev_start, mb.ev_rendered));
+            g->render_ms[i] = t;
+        }
+        RTXG_HIP(hipSetDevice(g->m[0].device));
+        RTXG_HIP(hipEventElapsedTime(&t, g->ev_g0, g->ev_g1));
+        g->gather_ms = t;
+        RTXG_HIP(hipEventElapsedTime(&t, g->ev_d0, g->ev_d1));
+        g->deint_ms = t;
+        g->have_times = true;
+    }
+    return RTX_OK;
+}
+
+void *rtx_group_image(rtx_group *g) { return g ? g->d_image : nullptr; }
+
+int rtx_group_download(rtx_group *g, float *host, size_t bytes) {
+    if (!g || !host) return fail(RTX_ERR_INVALID, "rtx_group_download: null argument");
+    if (!g->d_image || !g->launched) return fail(RTX_ERR_STATE, "rtx_group_download: nothing rendered yet");
+    if (bytes != g->plan.image_bytes) return fail(RTX_ERR_INVALID, "rtx_group_download: bytes != width*height*16");
+    const int rc = rtx_group_sync(g);
+    if (rc != RTX_OK) return rc;
+    Member &root = g->m[0];
+    RTXG_HIP(hipSetDevice(root.device));
+    RTXG_HIP(hipMemcpyAsync(host, g->d_image, bytes, hipMemcpyDeviceToHost, root.stream));
+    RTXG_HIP(hipStreamSynchronize(root.stream));
+    return RTX_OK;
+}
+
+int rtx_group_get_times(rtx_group *g, double *render_ms, double *gather_ms, double *deinterleave_ms) {
+    if (!g) return fail(RTX_ERR_INVALID, "rtx_group_get_times: null group");
+    if (!g->have_times) return fail(RTX_ERR_STATE, "rtx_group_get_times: no frame synced (rtx_group_sync first)");
+    if (render_ms)
+        for (size_t i = 0; i < g->m.size(); ++i) render_ms[i] = g->render_ms[i];
+    if (gather_ms) *gather_ms = g->gather_ms;
+    if (deinterleave_ms) *deinterleave_ms = g->deint_ms;
+    return RTX_OK;
+}
+
+}  // extern "C"

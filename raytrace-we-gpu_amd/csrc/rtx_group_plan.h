@@ -1,0 +1,96 @@
+// rtx_group_plan.h — the partition and buffer arithmetic of a multi-GPU frame
+// (include/rtx.h rtx_group): which rows each member renders, how large every
+// buffer is, and the transfers that bring the members' rows to the root.
+// No HIP in here: rtx_group.hip executes the plan on device memory, and
+// tests/group_plan_check.cpp executes the same plan on host memory.
+//
+// A frame of `height` rows is cut into tiles of `tile_rows` rows; tile k
+// belongs to member k % n (rtx_render_rows' partition). Member m
+// renders its rows, ascending and contiguous, into its send buffer; member 0
+// (the root) renders straight into slot 0 of the gathered buffer
+// [n][max_rows][width]; one transfer per other member moves its rows to the
+// start of slot m; rtx_deinterleave_rows turns the gathered buffer into the
+// image [height][width].
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+namespace rtx {
+
+constexpr size_t kGroupPixelBytes = 16;  // float4
+
+// rtx_part_rows (rtx_api.hip) restated: rows of `part`.
+inline uint32_t group_part_rows(uint32_t height, uint32_t tile_rows, uint32_t part, uint32_t nparts) {
+    if (tile_rows == 0 || nparts == 0 || part >= nparts) return 0;
+    const uint32_t tiles = (uint32_t)(((uint64_t)height + tile_rows - 1) / tile_rows);
+    if (part >= tiles) return 0;
+    const uint32_t my_tiles = (tiles - part + nparts - 1) / nparts;  // tiles part, part + nparts, ...
+    uint64_t rows = (uint64_t)my_tiles * tile_rows;
+    const uint32_t last_tile = part + (my_tiles - 1) * nparts;
+    if (last_tile == tiles - 1) rows -= (uint64_t)tiles * tile_rows - height;  // ragged final tile
+    return (uint32_t)rows;
+}
+
+// One transfer of the gather: `bytes` from offset 0 of member `member`'s send
+// buffer to offset `dst_off` of the root's gathered buffer. A member without
+// rows keeps its place with bytes == 0 (a copy skips it; a collective still
+// names it).
+struct GroupOp {
+    uint32_t member;
+    size_t dst_off;
+    size_t bytes;
+};
+
+struct GroupPlan {
+    uint32_t n = 0, width = 0, height = 0, tile_rows = 0;
+    uint32_t max_rows = 0;             // rows of the largest part (part 0)
+    std::vector<uint32_t> rows;        // [n] rows member m renders (0: it launches no render)
+    std::vector<size_t> send_bytes;    // [n] member m's send buffer ([0]: 0, the root has none)
+    size_t slot_bytes = 0;             // max_rows * width pixels
+    size_t gathered_bytes = 0;         // n slots
+    size_t image_bytes = 0;            // height * width pixels
+    std::vector<GroupOp> ops;          // [n - 1] members 1 .. n-1, in order
+
+    // Byte offset of member m's slot in the gathered buffer.
+    size_t slot_off(uint32_t m) const { return (size_t)m * slot_bytes; }
+    bool renders(uint32_t m) const { return rows[m] != 0; }
+    bool same(uint32_t n_, uint32_t w, uint32_t h, uint32_t t) const {
+        return n == n_ && width == w && height == h && tile_rows == t;
+    }
+};
+
+// n >= 1, tile_rows >= 1, width * height <= 2^31 (rtx_set_frame's bound).
+inline GroupPlan make_group_plan(uint32_t n, uint32_t width, uint32_t height, uint32_t tile_rows) {
+    GroupPlan p;
+    p.n = n;
+    p.width = width;
+    p.height = height;
+    p.tile_rows = tile_rows;
+    p.max_rows = group_part_rows(height, tile_rows, 0, n);
+    const size_t row_bytes = (size_t)width * kGroupPixelBytes;
+    p.slot_bytes = (size_t)p.max_rows * row_bytes;
+    p.gathered_bytes = (size_t)n * p.slot_bytes;
+    p.image_bytes = (size_t)height * row_bytes;
+    p.rows.resize(n);
+    p.send_bytes.assign(n, 0);
+    for (uint32_t m = 0; m < n; ++m) {
+        p.rows[m] = group_part_rows(height, tile_rows, m, n);
+        if (m == 0) continue;
+        p.send_bytes[m] = (size_t)p.rows[m] * row_bytes;
+        p.ops.push_back(GroupOp{m, p.slot_off(m), p.send_bytes[m]});
+    }
+    return p;
+}
+
+// rtx_deinterleave_rows (rtx_kernels.hip k_deinterleave) restated: where image
+// row y lives in the gathered buffer.
+inline void group_row_owner(const GroupPlan &p, uint32_t y, uint32_t *member, uint32_t *local_row) {
+    const uint32_t tile = y / p.tile_rows;
+    *member = tile % p.n;
+    *local_row = (tile / p.n) * p.tile_rows + (y - tile * p.tile_rows);
+}
+
+}  // namespace rtx

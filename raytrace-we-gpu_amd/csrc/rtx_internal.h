@@ -7,6 +7,8 @@
 
 #include "rtx_grid.h"
 
+struct rtx_ctx;  // include/rtx.h
+
 namespace rtx {
 
 // Device scene layout (all in HBM, read-only):
@@ -249,5 +251,10 @@ hipError_t launch_debug_scan_rate(const KParams &p, uint32_t reps, unsigned long
                                   hipStream_t stream);
 hipError_t launch_debug_math(int fn, const float *in0, const float *in1, uint32_t n,
                              float *out, hipStream_t stream);
+
+// rtx_api.hip, for rtx_group.hip: set this thread's rtx_last_error() text and
+// return `code`; the stream a context launches on at the moment.
+int api_fail(int code, const char *msg);
+hipStream_t ctx_stream(const ::rtx_ctx *c);
 
 }  // namespace rtx

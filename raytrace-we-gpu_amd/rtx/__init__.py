@@ -50,6 +50,8 @@ SCAN_MODES = {"auto": 0, "linear": 1}  # rtx_set_scan_mode (RTX_SCAN_AUTO / RTX_
 FN = dict(sqrt=0, div=1, sin=2, cos=3, log2=4, exp2=5, pow=6, basehash=7,
           hash1=8, hash2=9, hash3=10, rius=11, lambert_dir=12, lambert_dir_guard=13)
 FRAME_LAMBERT_GUARD = 1  # rtx_frame.flags bit (RTX_FRAME_LAMBERT_GUARD)
+GATHER_MODES = {"auto": 0, "rccl": 1, "copy": 2}  # rtx_group_create (RTX_GATHER_*)
+GROUP_MAX = 64  # RTX_GROUP_MAX
 
 
 class RtxError(RuntimeError):
@@ -156,11 +158,26 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_debug_wave_times": (C.c_int, [ctx, C.c_size_t, C.POINTER(C.c_uint64)]),
         "rtx_debug_pixel_cost": (C.c_int, [ctx, u32, C.POINTER(C.c_uint32)]),
         "rtx_debug_scan_rate": (C.c_int, [ctx, u32, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
+        "rtx_group_create": (C.c_int, [C.POINTER(C.c_int), u32, C.c_int, C.POINTER(C.c_void_p)]),
+        "rtx_group_destroy": (None, [vp]),
+        "rtx_group_size": (u32, [vp]),
+        "rtx_group_ctx": (ctx, [vp, u32]),
+        "rtx_group_gather_mode": (C.c_int, [vp]),
+        "rtx_group_rccl_version": (C.c_int, [vp]),
+        "rtx_group_upload_world": (C.c_int, [vp, C.POINTER(rtx_world)]),
+        "rtx_group_set_frame": (C.c_int, [vp, C.POINTER(rtx_frame)]),
+        "rtx_group_render": (C.c_int, [vp, u32]),
+        "rtx_group_sync": (C.c_int, [vp]),
+        "rtx_group_image": (vp, [vp]),
+        "rtx_group_download": (C.c_int, [vp, f, C.c_size_t]),
+        "rtx_group_get_times": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double)]),
     }
     # entry points added after 1.0 may be absent from older builds (A/B runs
     # of earlier libraries); calling one then fails with AttributeError
     optional = {"rtx_schedule_defaults", "rtx_set_schedule", "rtx_get_schedule", "rtx_debug_hit_world_from",
                 "rtx_build_info", "rtx_debug_scan_rate", "rtx_set_scan_mode"}
+    optional |= {n for n in sig if n.startswith("rtx_group_")}  # arrived without a version bump
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -501,6 +518,124 @@ class Context:
         _check(self._lib.rtx_debug_math(self._h, fn, _fptr(a), _fptr(b), a.shape[0], _fptr(out)),
                "rtx_debug_math", self._lib)
         return out
+
+
+class _MemberContext(Context):
+    """A group member's context, borrowed (rtx_group_ctx): the group owns and
+    destroys it, so close() only lets go of the handle."""
+
+    def __init__(self, lib: C.CDLL, handle: int, device: int):
+        self._lib = lib
+        self._h = C.c_void_p(handle)
+        self.device = device
+        self.frame = None
+        self.world = None
+
+    def close(self):
+        self._h = None
+
+
+class Group:
+    """One frame across several devices in one process (rtx_group, include/rtx.h):
+    member i of `devices` renders part i of the interleaved row tiles, member 0
+    gathers and assembles the image. `devices` all distinct, or all equal for
+    the one-GPU rehearsal (the members then render one after another).
+    gather: "auto", "rccl" or "copy". Mirrors :class:`Context`."""
+
+    def __init__(self, devices, gather: str = "auto", lib: Optional[C.CDLL] = None):
+        self._lib = lib or load_library()
+        if not hasattr(self._lib, "rtx_group_create"):
+            raise RtxError("this librtx.so has no rtx_group entry points")
+        if gather not in GATHER_MODES:
+            raise ValueError(f"gather must be one of {sorted(GATHER_MODES)}")
+        self.devices = [int(d) for d in devices]
+        arr = (C.c_int * max(1, len(self.devices)))(*self.devices)
+        h = C.c_void_p()
+        _check(self._lib.rtx_group_create(arr, len(self.devices), GATHER_MODES[gather], C.byref(h)),
+               "rtx_group_create", self._lib)
+        self._h = h
+        self.frame: Optional[rtx_frame] = None
+        self.world: Optional[World] = None
+        self._members = [_MemberContext(self._lib, self._lib.rtx_group_ctx(h, i), d)
+                         for i, d in enumerate(self.devices)]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            for m in self._members:
+                m.close()
+            self._lib.rtx_group_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return int(self._lib.rtx_group_size(self._h))
+
+    def ctx(self, member: int) -> Context:
+        """Member's context (borrowed): schedule, scan mode, stats."""
+        return self._members[member]
+
+    @property
+    def gather(self) -> str:
+        """The transport in use: "rccl" or "copy"."""
+        return "rccl" if self._lib.rtx_group_gather_mode(self._h) == GATHER_MODES["rccl"] else "copy"
+
+    @property
+    def rccl_version(self) -> Optional[int]:
+        return int(self._lib.rtx_group_rccl_version(self._h)) or None
+
+    def upload_world(self, world: World):
+        w = world.as_struct()
+        _check(self._lib.rtx_group_upload_world(self._h, C.byref(w)), "rtx_group_upload_world", self._lib)
+        self.world = world
+        for m in self._members:
+            m.world = world
+
+    def set_frame(self, frame: rtx_frame):
+        _check(self._lib.rtx_group_set_frame(self._h, C.byref(frame)), "rtx_group_set_frame", self._lib)
+        self.frame = frame
+        for m in self._members:
+            m.frame = frame
+
+    def render(self, tile_rows: int = 5):
+        _check(self._lib.rtx_group_render(self._h, tile_rows), "rtx_group_render", self._lib)
+
+    def sync(self):
+        _check(self._lib.rtx_group_sync(self._h), "rtx_group_sync", self._lib)
+
+    def image_ptr(self) -> int:
+        return int(self._lib.rtx_group_image(self._h) or 0)
+
+    def download(self) -> np.ndarray:
+        f = self.frame
+        out = np.empty((f.height, f.width, 4), np.float32)
+        _check(self._lib.rtx_group_download(self._h, _fptr(out), out.nbytes), "rtx_group_download", self._lib)
+        return out
+
+    def render_image(self, tile_rows: int = 5) -> np.ndarray:
+        self.render(tile_rows)
+        return self.download()
+
+    def times(self) -> dict:
+        """HIP-event times of the last synced frame: {"render_ms": [per member],
+        "gather_ms", "deinterleave_ms"}. Members on one device run one after
+        another: no scaling figure."""
+        n = len(self.devices)
+        r = (C.c_double * n)()
+        g, d = C.c_double(0.0), C.c_double(0.0)
+        _check(self._lib.rtx_group_get_times(self._h, r, C.byref(g), C.byref(d)), "rtx_group_get_times",
+               self._lib)
+        return {"render_ms": list(r), "gather_ms": g.value, "deinterleave_ms": d.value}
 
 
 class DeviceArray:
