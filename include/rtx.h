@@ -40,6 +40,11 @@ extern "C" {
 
 #define RTX_VERSION 145 /* 1.4.5 */
 /* ABI notes.
+ *  1.4.5 (later builds, no version bump): rtx_render_sum, rtx_fold_frames
+ *         (RTX_FOLD_MAX), rtx_group_accumulate, rtx_group_accumulated_frames
+ *         and rtx_group_get_accumulate_times (progressive frames dealt across
+ *         a group's members); purely additive again: probe for the symbol
+ *         (dlsym "rtx_group_accumulate").
  *  1.4.5 (later builds, no version bump): the rtx_group entry points (one
  *         frame across several devices); purely additive — no struct and no
  *         earlier entry point changed — so a caller probes for the symbol
@@ -335,6 +340,25 @@ RTX_API int rtx_render(rtx_ctx *ctx);
 RTX_API int rtx_accumulate(rtx_ctx *ctx, int reset);
 /* Frames accumulated since the last reset. */
 RTX_API uint32_t rtx_accumulated_frames(rtx_ctx *ctx);
+/* One whole frame's LINEAR per-pixel sample sums for seed offset frame_index
+ * (what rtx_accumulate adds to its accumulator for its frame number
+ * frame_index), into d_sum: width*height float4, xyz = sum, w = 0.
+ * Device pointer; asynchronous on the context stream. The context's own
+ * accumulator and rtx_accumulated_frames are untouched (its framebuffer is
+ * overwritten). frame_index <= 0x7fffffff. */
+RTX_API int rtx_render_sum(rtx_ctx *ctx, uint32_t frame_index, void *d_sum);
+/* Ordered fold. For each pixel p < pixels:
+ *   a = d_accum[p];
+ *   for k = 0 .. m-1: a.xyz = a.xyz + d_sums[k * slot_pixels + p].xyz   (this order)
+ *   d_accum[p] = a (w unchanged);
+ *   d_image[p] = (toGamma(a.x / n), toGamma(a.y / n), toGamma(a.z / n), 1), n = (float)divisor.
+ * 1 <= m <= RTX_FOLD_MAX, slot_pixels >= pixels >= 1, divisor >= 1; the three
+ * buffers must not overlap. With the sums of rtx_render_sum for frame_index
+ * F .. F+m-1 and divisor (F + m) * spp this is m calls of rtx_accumulate, bit
+ * for bit. Device pointers; asynchronous on the context stream. */
+#define RTX_FOLD_MAX 64
+RTX_API int rtx_fold_frames(rtx_ctx *ctx, void *d_accum, const void *d_sums, uint32_t m,
+                            size_t slot_pixels, size_t pixels, uint32_t divisor, void *d_image);
 /* Rows owned by `part` (host arithmetic, no GPU). */
 RTX_API uint32_t rtx_part_rows(uint32_t height, uint32_t tile_rows, uint32_t part,
                                uint32_t nparts);
@@ -419,6 +443,44 @@ RTX_API int rtx_group_download(rtx_group *g, float *host_rgba, size_t bytes);
  * nothing about scaling. */
 RTX_API int rtx_group_get_times(rtx_group *g, double *render_ms, double *gather_ms,
                                 double *deinterleave_ms);
+/* Progressive accumulation with whole frames dealt to the members (the row
+ * split above serves one frame's latency; this serves the throughput of a
+ * converged image: a frame's seeds depend on (pixel, frame_index) only, so
+ * frames are independent). Adds `frames` frames to the group's accumulator and
+ * writes the image. With F frames accumulated so far, frame j of the call
+ * (j = 0 .. frames-1) has frame_index F + j and goes to member j % n: a call
+ * always starts at member 0, so the root renders in every round. The call runs
+ * in rounds of up to n frames. In a round each taking member renders its
+ * frame's sums with rtx_render_sum — the root straight into slot 0 of a
+ * root-side buffer [n][width*height], the others into one sum buffer each,
+ * gathered into their slots by the group's transport (stream-ordered copies /
+ * hipMemcpyPeerAsync, or one ncclGroupStart/End of send/recv) — and one
+ * rtx_fold_frames of the round's m sums (member order = frame order) follows
+ * on the root's stream with divisor (frames accumulated after the round) * spp.
+ * A member past the call's last frame launches nothing in that round. A
+ * member's sum buffer is reused by the next round only after the gather that
+ * read it (copies: its stream waits for the gather's end event; RCCL: the send
+ * is ordered on its stream).
+ * Asynchronous like rtx_group_render: no host wait once the buffers fit the
+ * frame size. Afterwards rtx_group_image / rtx_group_download give the image;
+ * it equals F + frames calls of rtx_accumulate on one context bit for bit.
+ * reset != 0, a first call, or a frame size other than the accumulator's
+ * restarts at F = 0 (the accumulator is zeroed), as rtx_accumulate does.
+ * rtx_group_render between two calls overwrites the image but not the
+ * accumulator: the next call continues and rewrites the image.
+ * RTX_ERR_INVALID before any HIP call: a null group, frames == 0, spp == 0,
+ * F + frames > 0x7fffffff (the seed uses 0x80000000 | frame_index), or
+ * (F + frames) * spp not representable in uint32 (the fold's divisor). No
+ * frame set or no world uploaded is RTX_ERR_STATE. F advances by the rounds
+ * whose fold was enqueued; a failing member's error is returned with its index. */
+RTX_API int rtx_group_accumulate(rtx_group *g, uint32_t frames, int reset);
+/* Frames in the group's accumulator (0 for NULL). */
+RTX_API uint32_t rtx_group_accumulated_frames(rtx_group *g);
+/* HIP-event times of the LAST round of the last rtx_group_accumulate, after
+ * rtx_group_sync: render_ms[n] (0 for a member that rendered nothing in it),
+ * the gather and the fold on the root's stream. NULL outputs are skipped. */
+RTX_API int rtx_group_get_accumulate_times(rtx_group *g, double *render_ms, double *gather_ms,
+                                           double *fold_ms);
 
 /* ---- device buffers (for callers without their own allocator) ----------
  * Ordered on the context stream; copies are synchronous. d_ptr from

@@ -116,6 +116,11 @@ public:
     void UnloadContent() override;
     void Update() override;
     void Render() override;
+    // Progressive frames (the reference's intended interactive mode) instead of
+    // Render: `frames` more frames into the accumulator, the image rewritten.
+    // With a group the frames are dealt to its members
+    // (rtx_group_accumulate); otherwise `frames` calls of rtx_accumulate.
+    bool Accumulate(uint32_t frames, bool reset);
 
     // Image output contract (§8f-1): the framebuffer, row 0 = image bottom.
     bool Download(std::vector<float> &rgba);

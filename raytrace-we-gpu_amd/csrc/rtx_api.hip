@@ -239,6 +239,10 @@ rtx::KScene scene_of(const rtx_ctx *c) {
 namespace rtx {  // for rtx_group.hip (rtx_internal.h)
 int api_fail(int code, const char *msg) { return fail(code, msg); }
 hipStream_t ctx_stream(const ::rtx_ctx *c) { return c->stream; }
+bool ctx_world_spp(const ::rtx_ctx *c, uint32_t *spp) {
+    *spp = c->spp;
+    return c->have_world;
+}
 }  // namespace rtx
 
 extern "C" {
@@ -853,6 +857,44 @@ int rtx_accumulate(rtx_ctx *c, int reset) {
 }
 
 uint32_t rtx_accumulated_frames(rtx_ctx *c) { return c ? c->accum_frames : 0; }
+
+int rtx_render_sum(rtx_ctx *c, uint32_t frame_index, void *d_sum) {
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_render_sum: null ctx");
+    if (!d_sum) return fail(RTX_ERR_INVALID, "rtx_render_sum: null d_sum");
+    if (frame_index > 0x7fffffffu)  // the seed uses 0x80000000 | frame_index
+        return fail(RTX_ERR_INVALID, "rtx_render_sum: frame_index above 0x7fffffff");
+    if (!c->have_world) return fail(RTX_ERR_STATE, "rtx_render_sum: no world uploaded");
+    if (!c->have_frame) return fail(RTX_ERR_STATE, "rtx_render_sum: no frame set");
+    int rc = set_device(c);
+    if (rc) return rc;
+    // The accumulate launch pointed at a zeroed buffer: frame 1 of 1 into
+    // d_sum. 0 + s == s bit for bit, NaN and inf included, unless s is -0,
+    // and a pixel's sum never is: it starts at +0 and x + y is
+    // -0 only for two -0 terms. The gamma image the launch also writes lands
+    // in the context's own framebuffer and is ignored.
+    const size_t px = (size_t)c->frame.width * c->frame.height;
+    RTX_HIP(hipMemsetAsync(d_sum, 0, px * sizeof(float4), c->stream));
+    return render_impl(c, 1, 0, 1, nullptr, reinterpret_cast<float4 *>(d_sum), 1, frame_index);
+}
+
+int rtx_fold_frames(rtx_ctx *c, void *d_accum, const void *d_sums, uint32_t m, size_t slot_pixels, size_t pixels,
+                    uint32_t divisor, void *d_image) {
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_fold_frames: null ctx");
+    if (!d_accum || !d_sums || !d_image) return fail(RTX_ERR_INVALID, "rtx_fold_frames: null argument");
+    if (m == 0 || m > RTX_FOLD_MAX) return fail(RTX_ERR_INVALID, "rtx_fold_frames: m outside 1 .. RTX_FOLD_MAX");
+    if (pixels == 0 || slot_pixels < pixels)
+        return fail(RTX_ERR_INVALID, "rtx_fold_frames: needs slot_pixels >= pixels >= 1");
+    if (slot_pixels > ((size_t)1 << 40))  // m * slot_pixels * 16 stays far inside 64 bits
+        return fail(RTX_ERR_INVALID, "rtx_fold_frames: slot_pixels above 2^40");
+    if (divisor == 0) return fail(RTX_ERR_INVALID, "rtx_fold_frames: divisor is 0");
+    int rc = set_device(c);
+    if (rc) return rc;
+    hipError_t e = rtx::launch_fold_frames(reinterpret_cast<float4 *>(d_accum), reinterpret_cast<const float4 *>(d_sums),
+                                           m, slot_pixels, pixels, divisor, reinterpret_cast<float4 *>(d_image),
+                                           c->stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_fold_frames");
+    return RTX_OK;
+}
 
 static rtx::KParams make_params(const rtx_ctx *c, uint32_t rows, uint32_t tile_rows, uint32_t part,
                                 uint32_t nparts, float4 *out, float4 *accum, uint32_t accum_frames,

@@ -184,6 +184,25 @@ void RtxCSApp::Render() {
     }
 }
 
+bool RtxCSApp::Accumulate(uint32_t frames, bool reset) {
+    if (!m_ok) return false;
+    int rc = RTX_OK;
+    if (m_group) {
+        rc = rtx_group_accumulate(m_group, frames, reset ? 1 : 0);
+    } else {
+        if (frames == 0) {  // refused like the group's
+            m_error = "Accumulate: frames is 0";
+            return m_ok = false;
+        }
+        for (uint32_t k = 0; k < frames && rc == RTX_OK; ++k) rc = rtx_accumulate(m_ctx, (reset && k == 0) ? 1 : 0);
+    }
+    if (rc != RTX_OK) {
+        m_error = rtx_last_error();
+        m_ok = false;
+    }
+    return m_ok;
+}
+
 bool RtxCSApp::Download(std::vector<float> &rgba) {
     rgba.resize(4 * (size_t)m_cfg.width * m_cfg.height);
     const size_t bytes = rgba.size() * sizeof(float);

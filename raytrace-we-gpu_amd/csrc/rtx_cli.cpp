@@ -9,14 +9,23 @@
 //           [--aperture A] [--accumulate] [--lambert-guard]
 //           [--reference-frame] [--pfm out.pfm] [--ppm out.ppm]
 //           [--gpus N | --devices a,b,c] [--gather auto|rccl|copy] [--tile-rows T]
+//           [--split rows|frames]
 // --gpus N renders each frame across devices 0..N-1 (rtx_group: interleaved
 // tiles of T rows, default 5, one gather to device 0); --devices names them,
 // and a repeated device (0,0,0) rehearses the same split on one GPU, its
 // members one after another. The JSON line then also carries n_gpus, devices,
 // gather, rccl_version, per_member (rows, render_ms of the last frame),
 // gather_ms and deinterleave_ms, and its counters are summed over the members.
+// --split frames (with --gpus / --devices; the default is rows, the above)
+// renders the K frames progressively instead, whole frames dealt to the
+// members in one rtx_group_accumulate(K, reset) after the warm-up (a frame, then
+// one round of whole frames so that every member's buffers fit): the
+// image is that of --accumulate --frames K on one context. The JSON line then
+// carries "split": "frames", accumulated_frames, per_member (frames rendered,
+// render_ms of the last round), gather_ms and fold_ms of the last round.
 // --accumulate renders the K frames progressively (rtx_accumulate) instead
-// of K independent frames; --aperture enables the thin lens;
+// of K independent frames, on one context (with a group: --split frames);
+// --aperture enables the thin lens;
 // --lambert-guard the near-zero diffuse guard (RTX_FRAME_LAMBERT_GUARD).
 // --reference-frame: the reference's frame as shipped — 1024x576, spp 60,
 // depth 50, random_world with 326 spheres, camera (13,2,3) -> 0, vfov 20,
@@ -41,7 +50,8 @@ static void usage() {
                  "               [--rng chain|per-sample] [--frames K] [--device N]\n"
                  "               [--aperture A] [--accumulate] [--lambert-guard] [--reference-frame]\n"
                  "               [--pfm FILE] [--ppm FILE]\n"
-                 "               [--gpus N | --devices a,b,c] [--gather auto|rccl|copy] [--tile-rows T]\n");
+                 "               [--gpus N | --devices a,b,c] [--gather auto|rccl|copy] [--tile-rows T]\n"
+                 "               [--split rows|frames]\n");
 }
 
 int main(int argc, char **argv) {
@@ -65,6 +75,7 @@ int main(int argc, char **argv) {
     std::vector<int> devices;  // non-empty: a group
     int gather = RTX_GATHER_AUTO;
     bool group_opts = false;   // --gather / --tile-rows given
+    bool split_frames = false; // --split frames: progressive frames dealt to the members
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * {
@@ -117,6 +128,14 @@ int main(int argc, char **argv) {
                 usage();
                 return 2;
             }
+        } else if (a == "--split") {
+            const std::string m = next();
+            if (m == "frames") split_frames = true;
+            else if (m == "rows") split_frames = false;
+            else {
+                usage();
+                return 2;
+            }
         } else if (a == "--tile-rows") {
             cfg.tile_rows = (uint32_t)std::atoi(next());
             group_opts = true;
@@ -159,9 +178,13 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "rtx_cli: --gather and --tile-rows need --gpus or --devices\n");
         return 2;
     }
+    if (split_frames && !grouped) {
+        std::fprintf(stderr, "rtx_cli: --split frames needs --gpus or --devices\n");
+        return 2;
+    }
     if (grouped && accumulate) {
         std::fprintf(stderr, "rtx_cli: --accumulate with --gpus / --devices is not supported "
-                             "(a group has no progressive accumulation)\n");
+                             "(a group accumulates with --split frames)\n");
         return 2;
     }
     if (grouped && cfg.tile_rows == 0) {
@@ -176,6 +199,9 @@ int main(int argc, char **argv) {
     }
     app.Update();
     app.Render();  // warm-up frame (also the reference's single frame, main.cpp:38-39)
+    // ... and one round of whole frames: the row-split warm-up sized every member's
+    // buffers for its rows only, and the timed call is to find them fitting
+    if (split_frames) app.Accumulate((uint32_t)devices.size(), true);
     rtx_group *grp = app.group();
     const uint32_t members = grp ? rtx_group_size(grp) : 0;
     if (grp) {
@@ -186,7 +212,11 @@ int main(int argc, char **argv) {
         rtx_stats_reset(app.context());
     }
     const auto t0 = std::chrono::steady_clock::now();
-    for (int k = 0; k < frames; ++k) {
+    if (split_frames) {
+        app.Update();
+        app.Accumulate((uint32_t)frames, true);
+    }
+    for (int k = 0; k < frames && !split_frames; ++k) {
         app.Update();
         if (accumulate) {
             if (rtx_accumulate(app.context(), k == 0) != RTX_OK) {
@@ -222,8 +252,9 @@ int main(int argc, char **argv) {
             st.sphere_tests += s.sphere_tests;
         }
         std::vector<double> render_ms(members, 0.0);
-        double gather_ms = 0.0, deint_ms = 0.0;
-        if (rtx_group_get_times(grp, render_ms.data(), &gather_ms, &deint_ms) != RTX_OK) {
+        double gather_ms = 0.0, deint_ms = 0.0;  // (deint_ms: with --split frames the fold)
+        if ((split_frames ? rtx_group_get_accumulate_times(grp, render_ms.data(), &gather_ms, &deint_ms)
+                          : rtx_group_get_times(grp, render_ms.data(), &gather_ms, &deint_ms)) != RTX_OK) {
             std::fprintf(stderr, "rtx_cli: times failed: %s\n", rtx_last_error());
             return 1;
         }
@@ -231,22 +262,30 @@ int main(int argc, char **argv) {
         char buf[96];
         for (uint32_t m = 0; m < members; ++m) {
             devs += (m ? ", " : "") + std::to_string(devices[m]);
-            std::snprintf(buf, sizeof buf, "%s{\"rows\": %u, \"render_ms\": %.4f}", m ? ", " : "",
-                          rtx_part_rows(cfg.height, cfg.tile_rows, m, members), render_ms[m]);
+            if (split_frames)  // frame j goes to member j % n
+                std::snprintf(buf, sizeof buf, "%s{\"frames\": %u, \"render_ms\": %.4f}", m ? ", " : "",
+                              (uint32_t)frames / members + (m < (uint32_t)frames % members ? 1u : 0u), render_ms[m]);
+            else
+                std::snprintf(buf, sizeof buf, "%s{\"rows\": %u, \"render_ms\": %.4f}", m ? ", " : "",
+                              rtx_part_rows(cfg.height, cfg.tile_rows, m, members), render_ms[m]);
             per += buf;
         }
         const int ver = rtx_group_rccl_version(grp);
         const std::string rccl = ver ? "\"" + std::to_string(ver) + "\"" : "null";
+        // the row split names its tile_rows and the de-interleave, the frame split its frames and the fold
+        const std::string split = split_frames ? "\"split\": \"frames\", \"accumulated_frames\": " +
+                                                     std::to_string(rtx_group_accumulated_frames(grp))
+                                               : "\"tile_rows\": " + std::to_string(cfg.tile_rows);
         std::printf("{\"width\": %u, \"height\": %u, \"spp\": %u, \"depth\": %u, \"spheres\": %u, "
                     "\"cbuffers\": %s, \"frames\": %d, \"wall_s\": %.6f, \"kernel_ms\": %.4f, "
                     "\"msamples_per_s\": %.3f, \"segments\": %llu, \"sphere_tests\": %llu, "
                     "\"n_gpus\": %u, \"devices\": [%s], \"gather\": \"%s\", \"rccl_version\": %s, "
-                    "\"tile_rows\": %u, \"per_member\": [%s], \"gather_ms\": %.4f, \"deinterleave_ms\": %.4f}\n",
+                    "%s, \"per_member\": [%s], \"gather_ms\": %.4f, \"%s\": %.4f}\n",
                     cfg.width, cfg.height, cfg.spp, cfg.depth, app.sphere_count(), cfg.cbuffers ? "true" : "false",
                     frames, wall, st.kernel_ms, (double)st.samples / wall / 1e6, (unsigned long long)st.segments,
                     (unsigned long long)st.sphere_tests, members, devs.c_str(),
-                    rtx_group_gather_mode(grp) == RTX_GATHER_RCCL ? "rccl" : "copy", rccl.c_str(), cfg.tile_rows,
-                    per.c_str(), gather_ms, deint_ms);
+                    rtx_group_gather_mode(grp) == RTX_GATHER_RCCL ? "rccl" : "copy", rccl.c_str(), split.c_str(),
+                    per.c_str(), gather_ms, split_frames ? "fold_ms" : "deinterleave_ms", deint_ms);
     } else {
         rtx_get_stats(app.context(), &st);
         std::printf("{\"width\": %u, \"height\": %u, \"spp\": %u, \"depth\": %u, \"spheres\": %u, "

@@ -3,6 +3,9 @@
 // by one host thread. The partition and buffer arithmetic is
 // rtx_group_plan.h's; this file executes that plan on device memory with the
 // single-context entry points (rtx_render_rows, rtx_deinterleave_rows).
+// rtx_group_accumulate is the second split: whole progressive frames dealt to
+// the members (rtx_render_sum), their sums gathered into the root's slots and
+// folded in frame order (rtx_fold_frames); its plan is in the same header.
 //
 // RCCL is loaded at run time (dlopen), so librtx.so carries no link
 // dependency on it: a single-GPU user pays nothing, and a process that has
@@ -104,6 +107,9 @@ struct Member {
     size_t send_bytes = 0;
     hipEvent_t ev_start = nullptr, ev_rendered = nullptr;
     bool rendered = false;         // the last frame launched a render for it
+    void *d_sum = nullptr;         // rtx_group_accumulate: its frame's sums (members 1 .. n-1)
+    hipEvent_t ev_sum0 = nullptr, ev_sum1 = nullptr;
+    bool summed = false;           // the last accumulate round launched a render for it
     nccl_comm comm = nullptr;
 };
 
@@ -127,6 +133,18 @@ struct rtx_group {
     bool have_times = false;
     std::vector<double> render_ms;
     double gather_ms = 0.0, deint_ms = 0.0;
+    size_t image_pixels = 0;  // of d_image (rtx_group_render and rtx_group_accumulate share it)
+    // rtx_group_accumulate
+    rtx::AccumPlan aplan;     // of the buffers below (n == 0: none yet)
+    void *d_accum = nullptr;  // [pixels] linear sums over acc_frames frames
+    void *d_sums = nullptr;   // [n][pixels] a round's sums, slot i member i's
+    uint32_t acc_frames = 0;
+    hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr, ev_f0 = nullptr, ev_f1 = nullptr;
+    bool acc_launched = false;    // a round's events are recorded
+    bool acc_gathered = false;    // ... ev_a1 among them
+    bool have_acc_times = false;
+    std::vector<double> acc_render_ms;
+    double acc_gather_ms = 0.0, fold_ms = 0.0;
 };
 
 namespace {
@@ -146,9 +164,31 @@ void free_buffers(rtx_group *g) {
     }
     if (!g->m.empty()) (void)hipSetDevice(g->m[0].device);
     (void)hipFree(g->d_gathered);
-    (void)hipFree(g->d_image);
-    g->d_gathered = g->d_image = nullptr;
+    g->d_gathered = nullptr;
     g->plan = rtx::GroupPlan();
+}
+
+void free_accum_buffers(rtx_group *g) {
+    for (Member &mb : g->m) {
+        if (mb.d_sum) {
+            (void)hipSetDevice(mb.device);
+            (void)hipFree(mb.d_sum);
+        }
+        mb.d_sum = nullptr;
+    }
+    if (!g->m.empty()) (void)hipSetDevice(g->m[0].device);
+    (void)hipFree(g->d_accum);
+    (void)hipFree(g->d_sums);
+    g->d_accum = g->d_sums = nullptr;
+    g->aplan = rtx::AccumPlan();
+    g->acc_frames = 0;
+}
+
+void free_image(rtx_group *g) {
+    if (!g->m.empty()) (void)hipSetDevice(g->m[0].device);
+    (void)hipFree(g->d_image);
+    g->d_image = nullptr;
+    g->image_pixels = 0;
 }
 
 // Every member's stream drained (before buffers are replaced).
@@ -160,19 +200,38 @@ int drain(rtx_group *g) {
     return RTX_OK;
 }
 
+// The image, width*height pixels on the root's device, shared by
+// rtx_group_render and rtx_group_accumulate; the streams are drained before
+// another size replaces it.
+int ensure_image(rtx_group *g) {
+    const size_t px = (size_t)g->frame.width * g->frame.height;
+    if (g->d_image && g->image_pixels == px) return RTX_OK;
+    if (g->d_image) {
+        const int rc = drain(g);
+        if (rc) return rc;
+    }
+    free_image(g);
+    RTXG_HIP(hipSetDevice(g->m[0].device));
+    RTXG_HIP(hipMalloc(&g->d_image, px * rtx::kGroupPixelBytes));
+    g->image_pixels = px;
+    return RTX_OK;
+}
+
 // Buffers for this frame size and tile_rows (render_impl's treatment of d_fb:
 // another size drains the streams and replaces them).
 int ensure_buffers(rtx_group *g, uint32_t tile_rows) {
     const uint32_t n = (uint32_t)g->m.size();
+    // (the image follows the frame size on its own: rtx_group_accumulate may have replaced it)
+    int rc = ensure_image(g);
+    if (rc) return rc;
     if (g->plan.same(n, g->frame.width, g->frame.height, tile_rows)) return RTX_OK;
-    int rc = drain(g);
+    rc = drain(g);
     if (rc) return rc;
     free_buffers(g);
     g->gathered_once = false;
     const rtx::GroupPlan plan = rtx::make_group_plan(n, g->frame.width, g->frame.height, tile_rows);
     g->direct = n == 1 && g->mode == RTX_GATHER_COPY;
     RTXG_HIP(hipSetDevice(g->m[0].device));
-    RTXG_HIP(hipMalloc(&g->d_image, plan.image_bytes));
     if (!g->direct) RTXG_HIP(hipMalloc(&g->d_gathered, plan.gathered_bytes));
     for (uint32_t i = 1; i < n; ++i) {
         Member &mb = g->m[i];
@@ -185,6 +244,30 @@ int ensure_buffers(rtx_group *g, uint32_t tile_rows) {
     return RTX_OK;
 }
 
+// rtx_group_accumulate's buffers for this frame size: the accumulator, the
+// root's n sum slots and one sum buffer per other member.
+int ensure_accum_buffers(rtx_group *g) {
+    const uint32_t n = (uint32_t)g->m.size();
+    int rc = ensure_image(g);  // (rtx_group_render may have replaced it for another size)
+    if (rc) return rc;
+    if (g->aplan.same(n, g->frame.width, g->frame.height) && g->d_accum) return RTX_OK;
+    rc = drain(g);
+    if (rc) return rc;
+    free_accum_buffers(g);
+    g->acc_gathered = false;
+    const rtx::AccumPlan plan = rtx::make_accum_plan(n, g->frame.width, g->frame.height);
+    RTXG_HIP(hipSetDevice(g->m[0].device));
+    RTXG_HIP(hipMalloc(&g->d_accum, plan.slot_bytes));
+    RTXG_HIP(hipMalloc(&g->d_sums, plan.sums_bytes));
+    for (uint32_t i = 1; i < n; ++i) {
+        Member &mb = g->m[i];
+        RTXG_HIP(hipSetDevice(mb.device));
+        RTXG_HIP(hipMalloc(&mb.d_sum, plan.slot_bytes));
+    }
+    g->aplan = plan;
+    return RTX_OK;
+}
+
 void destroy_group(rtx_group *g) {
     for (Member &mb : g->m) {
         if (!mb.ctx) continue;
@@ -194,8 +277,10 @@ void destroy_group(rtx_group *g) {
     for (Member &mb : g->m)
         if (mb.comm) (void)g->rccl.CommDestroy(mb.comm);
     free_buffers(g);
+    free_accum_buffers(g);
+    free_image(g);
     if (!g->m.empty() && g->m[0].ctx) (void)hipSetDevice(g->m[0].device);
-    for (hipEvent_t e : {g->ev_g0, g->ev_g1, g->ev_d0, g->ev_d1})
+    for (hipEvent_t e : {g->ev_g0, g->ev_g1, g->ev_d0, g->ev_d1, g->ev_a0, g->ev_a1, g->ev_f0, g->ev_f1})
         if (e) (void)hipEventDestroy(e);
     // the root last: the members on its device launch on its stream
     for (size_t i = g->m.size(); i-- > 0;) {
@@ -204,6 +289,8 @@ void destroy_group(rtx_group *g) {
         (void)hipSetDevice(mb.device);
         if (mb.ev_start) (void)hipEventDestroy(mb.ev_start);
         if (mb.ev_rendered) (void)hipEventDestroy(mb.ev_rendered);
+        if (mb.ev_sum0) (void)hipEventDestroy(mb.ev_sum0);
+        if (mb.ev_sum1) (void)hipEventDestroy(mb.ev_sum1);
         (void)rtx_use_own_stream(mb.ctx);
         rtx_destroy(mb.ctx);
     }
@@ -247,6 +334,7 @@ int rtx_group_create(const int *devices, uint32_t n, int gather_mode, rtx_group 
     g->mode = gather_mode == RTX_GATHER_AUTO ? (all_equal ? RTX_GATHER_COPY : RTX_GATHER_RCCL) : gather_mode;
     g->m.resize(n);
     g->render_ms.assign(n, 0.0);
+    g->acc_render_ms.assign(n, 0.0);
     int rc = RTX_OK;
     hipError_t e = hipSuccess;
     for (uint32_t i = 0; i < n && rc == RTX_OK; ++i) {
@@ -266,11 +354,13 @@ int rtx_group_create(const int *devices, uint32_t n, int gather_mode, rtx_group 
         e = hipSetDevice(mb.device);
         if (e == hipSuccess) e = hipEventCreate(&mb.ev_start);
         if (e == hipSuccess) e = hipEventCreate(&mb.ev_rendered);
+        if (e == hipSuccess) e = hipEventCreate(&mb.ev_sum0);
+        if (e == hipSuccess) e = hipEventCreate(&mb.ev_sum1);
         if (e != hipSuccess) rc = hip_fail(e, "rtx_group_create: hipEventCreate");
     }
     if (rc == RTX_OK) {
         e = hipSetDevice(g->m[0].device);
-        for (hipEvent_t *ev : {&g->ev_g0, &g->ev_g1, &g->ev_d0, &g->ev_d1})
+        for (hipEvent_t *ev : {&g->ev_g0, &g->ev_g1, &g->ev_d0, &g->ev_d1, &g->ev_a0, &g->ev_a1, &g->ev_f0, &g->ev_f1})
             if (e == hipSuccess) e = hipEventCreate(ev);
         if (e != hipSuccess) rc = hip_fail(e, "rtx_group_create: hipEventCreate");
     }
@@ -424,6 +514,124 @@ int rtx_group_render(rtx_group *g, uint32_t tile_rows) {
     return RTX_OK;
 }
 
+int rtx_group_accumulate(rtx_group *g, uint32_t frames, int reset) {
+    // arguments and state first: nothing in this block touches HIP
+    if (!g) return fail(RTX_ERR_INVALID, "rtx_group_accumulate: null group");
+    if (frames == 0) return fail(RTX_ERR_INVALID, "rtx_group_accumulate: frames is 0");
+    if (!g->have_frame) return fail(RTX_ERR_STATE, "rtx_group_accumulate: no frame set");
+    const uint32_t n = (uint32_t)g->m.size();
+    uint32_t spp = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t s = 0;
+        if (!rtx::ctx_world_spp(g->m[i].ctx, &s))
+            return fail(RTX_ERR_STATE, "rtx_group_accumulate: member " + std::to_string(i) + ": no world uploaded");
+        if (i > 0 && s != spp)
+            return fail(RTX_ERR_STATE, "rtx_group_accumulate: member " + std::to_string(i) + ": another spp than the root's");
+        spp = s;
+    }
+    if (spp == 0) return fail(RTX_ERR_INVALID, "rtx_group_accumulate: spp is 0 (no divisor)");
+    // a frame of another size restarts the accumulation, as rtx_accumulate does
+    const bool restart = reset || g->acc_frames == 0 || !g->d_accum ||
+                         !g->aplan.same(n, g->frame.width, g->frame.height);
+    const uint32_t first = restart ? 0u : g->acc_frames;
+    if (!rtx::accum_call_valid(first, frames, spp))
+        return fail(RTX_ERR_INVALID, "rtx_group_accumulate: " + std::to_string(first) + " + " + std::to_string(frames) +
+                                         " frames of " + std::to_string(spp) +
+                                         " spp: frame_index above 0x7fffffff or frames * spp above 2^32 - 1");
+
+    int rc = ensure_accum_buffers(g);
+    if (rc) return rc;
+    const rtx::AccumPlan &plan = g->aplan;
+    Member &root = g->m[0];
+    if (restart) {
+        RTXG_HIP(hipSetDevice(root.device));
+        RTXG_HIP(hipMemsetAsync(g->d_accum, 0, plan.slot_bytes, root.stream));
+        g->acc_frames = 0;
+    }
+    g->have_acc_times = false;
+
+    const uint32_t rounds = rtx::accum_rounds(n, frames);
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const rtx::AccumRound round = rtx::accum_round(plan, first, frames, spp, r);
+        // the round's frames, one per taking member, each asynchronous on its member's stream
+        for (uint32_t i = 0; i < n; ++i) {
+            Member &mb = g->m[i];
+            mb.summed = false;
+            if (!round.takes(i)) continue;
+            RTXG_HIP(hipSetDevice(mb.device));
+            // its sum buffer is free once the root has pulled the last round's sums
+            if (i > 0 && !g->one_device && g->mode == RTX_GATHER_COPY && g->acc_gathered)
+                RTXG_HIP(hipStreamWaitEvent(mb.stream, g->ev_a1, 0));
+            void *d_out = i > 0 ? mb.d_sum : g->d_sums;  // the root: slot 0
+            RTXG_HIP(hipEventRecord(mb.ev_sum0, mb.stream));
+            rc = rtx_render_sum(mb.ctx, round.frame_index(i), d_out);
+            if (rc != RTX_OK) {
+                const std::string why = rtx_last_error();
+                return fail(rc, "rtx_group_accumulate: member " + std::to_string(i) + ": " + why);
+            }
+            RTXG_HIP(hipSetDevice(mb.device));
+            RTXG_HIP(hipEventRecord(mb.ev_sum1, mb.stream));
+            mb.summed = true;
+        }
+        // the gather into slots 1 .. m-1, on the root's stream
+        RTXG_HIP(hipSetDevice(root.device));
+        RTXG_HIP(hipEventRecord(g->ev_a0, root.stream));
+        if (g->mode == RTX_GATHER_COPY) {
+            for (const rtx::GroupOp &op : round.ops) {
+                Member &mb = g->m[op.member];
+                char *dst = static_cast<char *>(g->d_sums) + op.dst_off;
+                RTXG_HIP(hipStreamWaitEvent(root.stream, mb.ev_sum1, 0));
+                if (mb.device == root.device)
+                    RTXG_HIP(hipMemcpyAsync(dst, mb.d_sum, op.bytes, hipMemcpyDeviceToDevice, root.stream));
+                else
+                    RTXG_HIP(hipMemcpyPeerAsync(dst, root.device, mb.d_sum, mb.device, op.bytes, root.stream));
+            }
+        } else if (!round.ops.empty()) {
+            int nrc = g->rccl.GroupStart();
+            if (nrc != 0) return nccl_fail(g, nrc, "rtx_group_accumulate: ncclGroupStart");
+            for (const rtx::GroupOp &op : round.ops) {
+                Member &mb = g->m[op.member];
+                const size_t floats = op.bytes / sizeof(float);
+                char *dst = static_cast<char *>(g->d_sums) + op.dst_off;
+                (void)hipSetDevice(mb.device);
+                if (nrc == 0) nrc = g->rccl.Send(mb.d_sum, floats, kNcclFloat, 0, mb.comm, mb.stream);
+                (void)hipSetDevice(root.device);
+                if (nrc == 0) nrc = g->rccl.Recv(dst, floats, kNcclFloat, (int)op.member, root.comm, root.stream);
+            }
+            const int erc = g->rccl.GroupEnd();  // always closed, also after a failed call inside
+            if (nrc != 0) return nccl_fail(g, nrc, "rtx_group_accumulate: ncclSend/ncclRecv");
+            if (erc != 0) return nccl_fail(g, erc, "rtx_group_accumulate: ncclGroupEnd");
+            RTXG_HIP(hipSetDevice(root.device));
+        }
+        RTXG_HIP(hipEventRecord(g->ev_a1, root.stream));
+        g->acc_gathered = true;
+
+        // the fold of slots 0 .. m-1 (member order = frame order), after the gather on the same stream
+        RTXG_HIP(hipEventRecord(g->ev_f0, root.stream));
+        rc = rtx_fold_frames(root.ctx, g->d_accum, g->d_sums, round.m, plan.pixels, plan.pixels, round.divisor,
+                             g->d_image);
+        if (rc != RTX_OK) return rc;
+        RTXG_HIP(hipSetDevice(root.device));
+        RTXG_HIP(hipEventRecord(g->ev_f1, root.stream));
+        g->acc_frames = round.frames_after;
+        g->acc_launched = true;
+    }
+    return RTX_OK;
+}
+
+uint32_t rtx_group_accumulated_frames(rtx_group *g) { return g ? g->acc_frames : 0; }
+
+int rtx_group_get_accumulate_times(rtx_group *g, double *render_ms, double *gather_ms, double *fold_ms) {
+    if (!g) return fail(RTX_ERR_INVALID, "rtx_group_get_accumulate_times: null group");
+    if (!g->have_acc_times)
+        return fail(RTX_ERR_STATE, "rtx_group_get_accumulate_times: no round synced (rtx_group_sync first)");
+    if (render_ms)
+        for (size_t i = 0; i < g->m.size(); ++i) render_ms[i] = g->acc_render_ms[i];
+    if (gather_ms) *gather_ms = g->acc_gather_ms;
+    if (fold_ms) *fold_ms = g->fold_ms;
+    return RTX_OK;
+}
+
 int rtx_group_sync(rtx_group *g) {
     if (!g) return fail(RTX_ERR_INVALID, "rtx_group_sync: null group");
     int first = RTX_OK;
@@ -453,6 +661,23 @@ int rtx_group_sync(rtx_group *g) {
         g->deint_ms = t;
         g->have_times = true;
     }
+    if (g->acc_launched && !g->have_acc_times) {  // the last round of the last rtx_group_accumulate
+        float t = 0.0f;
+        for (size_t i = 0; i < g->m.size(); ++i) {
+            Member &mb = g->m[i];
+            g->acc_render_ms[i] = 0.0;
+            if (!mb.summed) continue;
+            RTXG_HIP(hipSetDevice(mb.device));
+            RTXG_HIP(hipEventElapsedTime(&t, mb.ev_sum0, mb.ev_sum1));
+            g->acc_render_ms[i] = t;
+        }
+        RTXG_HIP(hipSetDevice(g->m[0].device));
+        RTXG_HIP(hipEventElapsedTime(&t, g->ev_a0, g->ev_a1));
+        g->acc_gather_ms = t;
+        RTXG_HIP(hipEventElapsedTime(&t, g->ev_f0, g->ev_f1));
+        g->fold_ms = t;
+        g->have_acc_times = true;
+    }
     return RTX_OK;
 }
 
@@ -460,8 +685,10 @@ void *rtx_group_image(rtx_group *g) { return g ? g->d_image : nullptr; }
 
 int rtx_group_download(rtx_group *g, float *host, size_t bytes) {
     if (!g || !host) return fail(RTX_ERR_INVALID, "rtx_group_download: null argument");
-    if (!g->d_image || !g->launched) return fail(RTX_ERR_STATE, "rtx_group_download: nothing rendered yet");
-    if (bytes != g->plan.image_bytes) return fail(RTX_ERR_INVALID, "rtx_group_download: bytes != width*height*16");
+    if (!g->d_image || !(g->launched || g->acc_launched))
+        return fail(RTX_ERR_STATE, "rtx_group_download: nothing rendered yet");
+    if (bytes != g->image_pixels * rtx::kGroupPixelBytes)
+        return fail(RTX_ERR_INVALID, "rtx_group_download: bytes != width*height*16");
     const int rc = rtx_group_sync(g);
     if (rc != RTX_OK) return rc;
     Member &root = g->m[0];

@@ -11,6 +11,9 @@
 // [n][max_rows][width]; one transfer per other member moves its rows to the
 // start of slot m; rtx_deinterleave_rows turns the gathered buffer into the
 // image [height][width].
+// The second half of the file is the frame split (rtx_group_accumulate):
+// AccumPlan / accum_round, executed on host memory by
+// tests/group_accum_check.cpp.
 #pragma once
 
 #include <stddef.h>
@@ -91,6 +94,73 @@ inline void group_row_owner(const GroupPlan &p, uint32_t y, uint32_t *member, ui
     const uint32_t tile = y / p.tile_rows;
     *member = tile % p.n;
     *local_row = (tile / p.n) * p.tile_rows + (y - tile * p.tile_rows);
+}
+
+// ---- progressive frames dealt across the members (rtx_group_accumulate) ----
+// The unit is a whole frame: with F frames accumulated, frame j of a call has
+// frame_index F + j and goes to member j % n, so a call runs in rounds of up
+// to n frames and always starts at member 0. In a round each taking member
+// renders its frame's linear sums (rtx_render_sum) — the root into slot 0 of
+// its sums buffer [n][pixels], member i > 0 into its own sum buffer [pixels] —
+// one transfer per other taking member moves its sums to the start of slot i,
+// and one rtx_fold_frames adds slots 0 .. m-1 (member order = frame order)
+// into the accumulator [pixels] and writes the image [pixels].
+struct AccumPlan {
+    uint32_t n = 0, width = 0, height = 0;
+    size_t pixels = 0;
+    size_t slot_bytes = 0;   // one frame's sums: the accumulator, the image and a member's sum buffer too
+    size_t sums_bytes = 0;   // the root's n slots
+
+    size_t slot_off(uint32_t m) const { return (size_t)m * slot_bytes; }
+    bool same(uint32_t n_, uint32_t w, uint32_t h) const { return n == n_ && width == w && height == h; }
+};
+
+// n >= 1, width * height <= 2^31 (rtx_set_frame's bound).
+inline AccumPlan make_accum_plan(uint32_t n, uint32_t width, uint32_t height) {
+    AccumPlan p;
+    p.n = n;
+    p.width = width;
+    p.height = height;
+    p.pixels = (size_t)width * height;
+    p.slot_bytes = p.pixels * kGroupPixelBytes;
+    p.sums_bytes = (size_t)n * p.slot_bytes;
+    return p;
+}
+
+// A call of `frames` frames on top of F accumulated ones, spp samples per
+// pixel and frame: the last frame_index fits the seed's 31 bits
+// (0x80000000 | frame_index) and the final divisor (F + frames) * spp fits the
+// fold kernel's uint32 (and is at least 1).
+inline bool accum_call_valid(uint32_t F, uint32_t frames, uint32_t spp) {
+    if (frames == 0 || spp == 0) return false;
+    const uint64_t total = (uint64_t)F + frames;
+    return total <= 0x7fffffffull && total * spp <= 0xffffffffull;
+}
+
+inline uint32_t accum_rounds(uint32_t n, uint32_t frames) { return frames / n + (frames % n ? 1u : 0u); }
+
+// Round r (0 .. accum_rounds - 1) of such a call.
+struct AccumRound {
+    uint32_t m = 0;            // frames of the round: members 0 .. m-1 render, the others launch nothing
+    uint32_t first_index = 0;  // member i < m renders frame_index first_index + i
+    uint32_t frames_after = 0; // frames in the accumulator after the round's fold
+    uint32_t divisor = 0;      // frames_after * spp
+    std::vector<GroupOp> ops;  // [m - 1] members 1 .. m-1, in order: a whole slot each
+
+    bool takes(uint32_t member) const { return member < m; }
+    uint32_t frame_index(uint32_t member) const { return first_index + member; }
+};
+
+inline AccumRound accum_round(const AccumPlan &p, uint32_t F, uint32_t frames, uint32_t spp, uint32_t r) {
+    AccumRound a;
+    const uint64_t done = (uint64_t)r * p.n;  // frames of the call's earlier rounds
+    const uint64_t left = frames - done;
+    a.m = (uint32_t)(left < p.n ? left : p.n);
+    a.first_index = (uint32_t)(F + done);
+    a.frames_after = a.first_index + a.m;
+    a.divisor = a.frames_after * spp;
+    for (uint32_t i = 1; i < a.m; ++i) a.ops.push_back(GroupOp{i, p.slot_off(i), p.slot_bytes});
+    return a;
 }
 
 }  // namespace rtx

@@ -241,6 +241,10 @@ hipError_t launch_cost(const KParams &p, hipStream_t stream);  // exact grid, p.
 hipError_t launch_deinterleave(const float4 *gathered, float4 *image, uint32_t width,
                                uint32_t height, uint32_t tile_rows, uint32_t nparts,
                                uint32_t max_rows, hipStream_t stream);
+// k_fold_frames (include/rtx.h rtx_fold_frames): accum[p].xyz += sums[k * slot_pixels + p].xyz
+// for k = 0 .. m-1 in that order, image[p] = toGamma(accum[p] / divisor).
+hipError_t launch_fold_frames(float4 *accum, const float4 *sums, uint32_t m, size_t slot_pixels, size_t pixels,
+                              uint32_t divisor, float4 *image, hipStream_t stream);
 hipError_t launch_debug_hit_world(const KScene &s, const float *rays, uint32_t nrays,
                                   float t_min, float t_max, uint32_t start_block, float *out,
                                   hipStream_t stream);
@@ -256,5 +260,7 @@ hipError_t launch_debug_math(int fn, const float *in0, const float *in1, uint32_
 // return `code`; the stream a context launches on at the moment.
 int api_fail(int code, const char *msg);
 hipStream_t ctx_stream(const ::rtx_ctx *c);
+// Whether a world is uploaded, and its samples per pixel (the group's divisor).
+bool ctx_world_spp(const ::rtx_ctx *c, uint32_t *spp);
 
 }  // namespace rtx

@@ -3355,6 +3355,56 @@ __global__ void __launch_bounds__(kBlock) k_deinterleave(const float4 *__restric
     img[i] = g[((uint64_t)part * max_rows + lr) * width + x];
 }
 
+// Ordered fold of m frames' linear sums into an accumulator (include/rtx.h
+// rtx_fold_frames): per pixel a.xyz += sums[k][p].xyz for k = 0 .. m-1 in that
+// order — output_pixel's accumulation, once per frame — then output_pixel's
+// image, toGamma(a / n). A streaming kernel: (m + 3) * pixels * 16 bytes, one
+// float4 per lane per buffer. The slots' loads go out kFoldBatch at a time,
+// back to back, before the adds that need them (bytes in flight); the adds
+// stay in slot order. m is wave-uniform: the tail's size is a scalar branch,
+// and each tail issues its loads unconditionally too (a load under a branch
+// of its own is waited for before the next is issued).
+constexpr uint32_t kFoldBatch = 4;
+constexpr uint32_t kFoldBlocks = 2048;  // grid cap (256 CUs x 8 blocks); the rest is grid-strided
+template <uint32_t B>
+__device__ __forceinline__ void fold_batch(float4 &a, const float4 *__restrict__ s, uint64_t slot_pixels) {
+    float4 v[B];
+#pragma unroll
+    for (uint32_t j = 0; j < B; ++j) v[j] = s[(uint64_t)j * slot_pixels];
+#pragma unroll
+    for (uint32_t j = 0; j < B; ++j) {
+        a.x = a.x + v[j].x;
+        a.y = a.y + v[j].y;
+        a.z = a.z + v[j].z;
+    }
+}
+__global__ void __launch_bounds__(kBlock) k_fold_frames(float4 *__restrict__ accum, const float4 *__restrict__ sums,
+                                                        uint32_t m, uint64_t slot_pixels, uint64_t pixels,
+                                                        uint32_t divisor, float4 *__restrict__ image) {
+    const float n = (float)divisor;
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x; p < pixels; p += stride) {
+        float4 a = accum[p];
+        const float4 *s = sums + p;
+        uint32_t k = 0;
+        for (; k + kFoldBatch <= m; k += kFoldBatch, s += kFoldBatch * slot_pixels) fold_batch<kFoldBatch>(a, s, slot_pixels);
+        static_assert(kFoldBatch == 4, "the tail below covers 1 .. 3 slots");
+        switch (m - k) {
+            case 3: fold_batch<3>(a, s, slot_pixels); break;
+            case 2: fold_batch<2>(a, s, slot_pixels); break;
+            case 1: fold_batch<1>(a, s, slot_pixels); break;
+            default: break;
+        }
+        accum[p] = a;
+        float4 o;
+        o.x = to_gamma(a.x / n);
+        o.y = to_gamma(a.y / n);
+        o.z = to_gamma(a.z / n);
+        o.w = 1.0f;
+        image[p] = o;
+    }
+}
+
 // The cost-ordered render's image, from its slot-ordered staging buffer to
 // the linear framebuffer (ShaderCompute.hlsl:314's one texel per pixel, in
 // pixel order): pixel i is stage[inv[i]], read gathered, stored coalesced.
@@ -3855,6 +3905,15 @@ hipError_t launch_deinterleave(const float4 *gathered, float4 *image, uint32_t w
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_deinterleave, dim3(ceil_div(n, kBlock)), dim3(kBlock), 0, stream, gathered,
                        image, width, height, tile_rows, nparts, max_rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_fold_frames(float4 *accum, const float4 *sums, uint32_t m, size_t slot_pixels, size_t pixels,
+                              uint32_t divisor, float4 *image, hipStream_t stream) {
+    if (pixels == 0 || m == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)pixels - 1) / kBlock + 1, kFoldBlocks);
+    hipLaunchKernelGGL(k_fold_frames, dim3(blocks), dim3(kBlock), 0, stream, accum, sums, m, (uint64_t)slot_pixels,
+                       (uint64_t)pixels, divisor, image);
     return hipGetLastError();
 }
 

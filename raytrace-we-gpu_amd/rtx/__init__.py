@@ -129,6 +129,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_render": (C.c_int, [ctx]),
         "rtx_accumulate": (C.c_int, [ctx, C.c_int]),
         "rtx_accumulated_frames": (u32, [ctx]),
+        "rtx_render_sum": (C.c_int, [ctx, u32, vp]),
+        "rtx_fold_frames": (C.c_int, [ctx, vp, vp, u32, C.c_size_t, C.c_size_t, u32, vp]),
         "rtx_camera_set_aperture": (C.c_int, [C.POINTER(rtx_frame), C.c_float]),
         "rtx_part_rows": (u32, [u32, u32, u32, u32]),
         "rtx_deinterleave_rows": (C.c_int, [ctx, vp, u32, u32, u32, u32, vp]),
@@ -172,12 +174,17 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_group_download": (C.c_int, [vp, f, C.c_size_t]),
         "rtx_group_get_times": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double)]),
+        "rtx_group_accumulate": (C.c_int, [vp, u32, C.c_int]),
+        "rtx_group_accumulated_frames": (u32, [vp]),
+        "rtx_group_get_accumulate_times": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                     C.POINTER(C.c_double)]),
     }
     # entry points added after 1.0 may be absent from older builds (A/B runs
     # of earlier libraries); calling one then fails with AttributeError
     optional = {"rtx_schedule_defaults", "rtx_set_schedule", "rtx_get_schedule", "rtx_debug_hit_world_from",
                 "rtx_build_info", "rtx_debug_scan_rate", "rtx_set_scan_mode"}
     optional |= {n for n in sig if n.startswith("rtx_group_")}  # arrived without a version bump
+    optional |= {"rtx_render_sum", "rtx_fold_frames"}            # ... with rtx_group_accumulate
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -405,6 +412,19 @@ class Context:
         _check(self._lib.rtx_accumulate(self._h, 1 if reset else 0), "rtx_accumulate", self._lib)
         return int(self._lib.rtx_accumulated_frames(self._h))
 
+    def render_sum(self, frame_index: int, d_sum: int):
+        """One frame's linear per-pixel sample sums (what accumulate() adds for
+        its frame number frame_index) into d_sum, width*height float4 with
+        w = 0; the context's own accumulation is untouched."""
+        _check(self._lib.rtx_render_sum(self._h, frame_index, C.c_void_p(d_sum or 0)), "rtx_render_sum", self._lib)
+
+    def fold_frames(self, d_accum: int, d_sums: int, m: int, slot_pixels: int, pixels: int, divisor: int,
+                    d_image: int):
+        """Ordered fold: d_accum[p].xyz += d_sums[k * slot_pixels + p].xyz for
+        k = 0 .. m-1 in that order, d_image[p] = toGamma(d_accum[p] / divisor)."""
+        _check(self._lib.rtx_fold_frames(self._h, C.c_void_p(d_accum or 0), C.c_void_p(d_sums or 0), m, slot_pixels,
+                                         pixels, divisor, C.c_void_p(d_image or 0)), "rtx_fold_frames", self._lib)
+
     def deinterleave(self, d_gathered: int, width: int, height: int, tile_rows: int, nparts: int,
                      d_image: int):
         _check(self._lib.rtx_deinterleave_rows(self._h, C.c_void_p(d_gathered), width, height,
@@ -625,6 +645,30 @@ class Group:
     def render_image(self, tile_rows: int = 5) -> np.ndarray:
         self.render(tile_rows)
         return self.download()
+
+    def accumulate(self, frames: int, reset: bool = False) -> int:
+        """`frames` more progressive frames, whole frames dealt to the members
+        (frame j to member j % n), folded in frame order on the root: the image
+        of as many Context.accumulate calls, bit for bit. Returns the frames
+        accumulated."""
+        _check(self._lib.rtx_group_accumulate(self._h, frames, 1 if reset else 0), "rtx_group_accumulate",
+               self._lib)
+        return self.accumulated_frames
+
+    @property
+    def accumulated_frames(self) -> int:
+        return int(self._lib.rtx_group_accumulated_frames(self._h))
+
+    def accumulate_times(self) -> dict:
+        """HIP-event times of the last round of the last accumulate(), after
+        sync() / download(): {"render_ms": [per member, 0 for one that took no
+        frame in it], "gather_ms", "fold_ms"}. No scaling figure either."""
+        n = len(self.devices)
+        r = (C.c_double * n)()
+        g, d = C.c_double(0.0), C.c_double(0.0)
+        _check(self._lib.rtx_group_get_accumulate_times(self._h, r, C.byref(g), C.byref(d)),
+               "rtx_group_get_accumulate_times", self._lib)
+        return {"render_ms": list(r), "gather_ms": g.value, "fold_ms": d.value}
 
     def times(self) -> dict:
         """HIP-event times of the last synced frame: {"render_ms": [per member],
