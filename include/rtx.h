@@ -40,6 +40,11 @@ extern "C" {
 
 #define RTX_VERSION 145 /* 1.4.5 */
 /* ABI notes.
+ *  1.4.5 (later builds, no version bump): rtx_refine, rtx_refined_samples,
+ *         rtx_refine_state, rtx_refine_export and rtx_refine_import
+ *         (progressive samples along the reference's own RNG chain, and its
+ *         checkpoint); purely additive again: probe for the symbol
+ *         (dlsym "rtx_refine").
  *  1.4.5 (later builds, no version bump): rtx_render_sum, rtx_fold_frames
  *         (RTX_FOLD_MAX), rtx_group_accumulate, rtx_group_accumulated_frames
  *         and rtx_group_get_accumulate_times (progressive frames dealt across
@@ -359,6 +364,62 @@ RTX_API int rtx_render_sum(rtx_ctx *ctx, uint32_t frame_index, void *d_sum);
 #define RTX_FOLD_MAX 64
 RTX_API int rtx_fold_frames(rtx_ctx *ctx, void *d_accum, const void *d_sums, uint32_t m,
                             size_t slot_pixels, size_t pixels, uint32_t divisor, void *d_image);
+/* Progressive refinement along the reference's own RNG chain (chain RNG only).
+ * The reference counts sampleCount / currSamples every Update
+ * (DxCSApp.cpp:491-492) but its frame loop and seed hook stayed commented out;
+ * rtx_accumulate fills that gap with new seeds per frame, so its image after k
+ * frames is no image the reference produces. rtx_refine instead CONTINUES
+ * every pixel's chain: a pixel's whole future depends only on its linear
+ * colour sum so far and its one fp32 seed, and the context keeps both.
+ *
+ * The context owns a chain state — width*height float4 in framebuffer order,
+ * xyz = the pixel's linear sample sum, w = its seed after its last finished
+ * sample — and the number N of samples in it. rtx_refine traces `samples`
+ * more samples of every pixel of the current frame, writes
+ * toGamma(sum / (float)(N + samples)), w = 1, into the context framebuffer and
+ * updates the state and N. Asynchronous on the context stream, like
+ * rtx_render. After calls adding s1..sk the framebuffer is, bit for bit (NaN
+ * pixels included), what rtx_render writes for the same world and frame with
+ * world.spp = s1 + ... + sk, whatever the steps: an image that sharpens in
+ * steps and is the reference's image at every step, and "300 more samples"
+ * at the cost of 300. world.spp is ignored; world.depth (0: zeros, as
+ * rtx_render), frame_index, the thin lens and RTX_FRAME_LAMBERT_GUARD apply as
+ * in rtx_render. The stats count pixels * samples samples and the launch's
+ * segments.
+ * The state restarts at N = 0 (every pixel's chain from its first seed) when
+ * reset != 0, on a first call, after any rtx_upload_world, and after an
+ * rtx_set_frame whose rtx_frame bytes differ from the frame the state was made
+ * for (another size included). An rtx_set_frame of equal bytes keeps it (hosts
+ * call it every Update, as the reference maps PerFrame every Update).
+ * rtx_set_schedule and rtx_set_scan_mode keep it (results never depend on
+ * them); rtx_render, rtx_render_rows, rtx_accumulate and rtx_render_sum
+ * between two calls overwrite the framebuffer but not the state.
+ * RTX_ERR_INVALID, before any HIP call: a null ctx, samples == 0, N + samples
+ * not representable in uint32, or a frame with rng_mode RTX_RNG_PER_SAMPLE —
+ * under a nonzero frame_index that mode's seeds depend on the frame's total
+ * spp (frame_index * spp + s), so "continue" has no single meaning there;
+ * rtx_accumulate is that mode's progressive form. RTX_ERR_STATE: no world or
+ * no frame.
+ * Not covered (later changes): row parts and rtx_group (a group-wide refine),
+ * and ordering the pixel queue by the previous call's measured per-pixel cost
+ * instead of a pre-pass per call. */
+RTX_API int rtx_refine(rtx_ctx *ctx, uint32_t samples, int reset);
+/* N: samples per pixel in the chain state (0 for NULL / none). */
+RTX_API uint32_t rtx_refined_samples(rtx_ctx *ctx);
+/* Device pointer of the chain state (width*height float4), NULL if none. */
+RTX_API void *rtx_refine_state(rtx_ctx *ctx);
+/* The chain state to host memory (synchronous, like rtx_download):
+ * bytes == width*height*16; RTX_ERR_STATE if there is no state. With
+ * rtx_refined_samples it is all a later session needs to resume. */
+RTX_API int rtx_refine_export(rtx_ctx *ctx, float *host_state, size_t bytes);
+/* Installs a chain state with N = samples (>= 1) for the current world and
+ * frame (both needed; bytes == width*height*16) and writes the framebuffer
+ * from it, toGamma(sum / (float)samples): a resumed session shows its image
+ * before it traces anything. The next rtx_refine continues from it.
+ * Synchronous. Whether the state belongs to this world and frame is the
+ * caller's business (rtx_app.hpp's state file checks it). */
+RTX_API int rtx_refine_import(rtx_ctx *ctx, const float *host_state, size_t bytes,
+                              uint32_t samples);
 /* Rows owned by `part` (host arithmetic, no GPU). */
 RTX_API uint32_t rtx_part_rows(uint32_t height, uint32_t tile_rows, uint32_t part,
                                uint32_t nparts);

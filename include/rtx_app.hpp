@@ -121,10 +121,22 @@ public:
     // With a group the frames are dealt to its members
     // (rtx_group_accumulate); otherwise `frames` calls of rtx_accumulate.
     bool Accumulate(uint32_t frames, bool reset);
+    // The reference's sampleCount loop (DxCSApp.cpp:491-492) as it was meant:
+    // `samples` more samples of every pixel along its own RNG chain
+    // (rtx_refine), the image then the plain render's at the samples refined
+    // so far. One context only (a group-wide refine is a later change).
+    bool Refine(uint32_t samples, bool reset);
+    // The chain state as a file (write_chain_state below), tagged with this
+    // app's world and frame; LoadState refuses a file of another size, world
+    // or frame (last_error() says which) and otherwise imports it
+    // (rtx_refine_import): the image is there before anything is traced.
+    bool SaveState(const std::string &path);
+    bool LoadState(const std::string &path);
 
     // Image output contract (§8f-1): the framebuffer, row 0 = image bottom.
     bool Download(std::vector<float> &rgba);
     const AppConfig &config() const { return m_cfg; }
+    const rtx_frame &frame() const { return m_frame; }
     uint32_t sphere_count() const { return m_count; }
     bool ok() const { return m_ok; }
 
@@ -135,11 +147,35 @@ private:
     rtx_frame m_frame{};
     uint32_t m_frame_count = 0;  // ~ sampleCount, DxCSApp.cpp:491
     bool m_ok = true;
+    uint32_t m_depth = 0;  // the uploaded world's depth (its hash in a chain-state file)
 };
 
 // PFM (float RGB, rows stored bottom-to-top = our row order) and binary
 // PPM (8-bit, top-to-bottom: rows flipped, values clamped to [0,1]).
 bool write_pfm(const std::string &path, const float *rgba, uint32_t w, uint32_t h);
 bool write_ppm(const std::string &path, const float *rgba, uint32_t w, uint32_t h);
+
+// Chain-state file (rtx_refine_export / rtx_refine_import): little-endian,
+//   char[8] magic "RTXCHAIN", u32 version (1), u32 width, u32 height,
+//   u32 samples (N), u64 world hash, u64 frame hash,
+//   then width*height float4 (linear sum xyz, seed w), framebuffer order.
+// The hashes are 64-bit FNV-1a: of the world's count, depth and its three
+// arrays (spp is not part of it: refine ignores it), and of the rtx_frame bytes.
+struct ChainStateHeader {
+    uint32_t width = 0, height = 0, samples = 0;
+    uint64_t world_hash = 0, frame_hash = 0;
+};
+constexpr uint32_t kChainStateVersion = 1;
+uint64_t chain_world_hash(uint32_t count, uint32_t depth, const float *spheres, const float *mat_types,
+                          const float *mat_values);
+uint64_t chain_frame_hash(const rtx_frame &frame);
+bool write_chain_state(const std::string &path, const ChainStateHeader &hdr, const float *state);
+// Reads a state written for `expect`'s size, world and frame (its samples are
+// ignored); `samples` receives the file's N. Refuses, with a message in `error`:
+// a file that cannot be opened, a wrong magic, a wrong version, a size that
+// does not match the file's length, a truncated file, and a size or hash that
+// differs from `expect`.
+bool read_chain_state(const std::string &path, const ChainStateHeader &expect, std::vector<float> &state,
+                      uint32_t &samples, std::string &error);
 
 }  // namespace rtx

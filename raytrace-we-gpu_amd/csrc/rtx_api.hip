@@ -105,6 +105,13 @@ struct rtx_ctx {
     float4 *d_accum = nullptr;
     size_t accum_pixels = 0;
     uint32_t accum_frames = 0;
+    // progressive refinement along the reference's RNG chain (rtx_refine):
+    // per pixel (linear sample sum, seed after its last sample), the samples
+    // in it (0: none, the next refine starts fresh) and the frame it is for
+    float4 *d_chain = nullptr;
+    size_t chain_pixels = 0;
+    uint32_t chain_n = 0;
+    rtx_frame chain_frame{};
     // measurement
     unsigned long long *d_counters = nullptr;
     unsigned long long *d_wave_times = nullptr;  // diagnostic (rtx_debug_wave_times)
@@ -320,6 +327,7 @@ void rtx_destroy(rtx_ctx *c) {
     free_world(c);
     (void)hipFree(c->d_fb);
     (void)hipFree(c->d_accum);
+    (void)hipFree(c->d_chain);
     (void)hipFree(c->d_counters);
     (void)hipFree(c->d_wave_times);
     (void)hipFree(c->d_sched);
@@ -782,6 +790,7 @@ int rtx_upload_world(rtx_ctx *c, const rtx_world *w) {
     c->depth = w->depth;
     c->spp = w->spp;
     c->have_world = true;
+    c->chain_n = 0;  // a chain state belongs to the world it was traced in
     return RTX_OK;
 }
 
@@ -802,6 +811,9 @@ int rtx_set_frame(rtx_ctx *c, const rtx_frame *f) {
     if (!(f->lens_u[3] >= 0.0f)) return fail(RTX_ERR_INVALID, "rtx_set_frame: negative lens radius");
     if ((uint64_t)f->width * f->height > (1ull << 31))
         return fail(RTX_ERR_INVALID, "rtx_set_frame: more than 2^31 pixels");
+    // a chain state belongs to its frame: other bytes restart it, the same
+    // bytes again (a host's per-Update call) keep it
+    if (c->chain_n != 0 && std::memcmp(f, &c->chain_frame, sizeof *f) != 0) c->chain_n = 0;
     c->frame = *f;
     c->have_frame = true;
     return RTX_OK;
@@ -818,8 +830,16 @@ uint32_t rtx_part_rows(uint32_t height, uint32_t tile_rows, uint32_t part, uint3
     return rows;
 }
 
+// A refine launch's chain arguments (KParams::chain_in, chain_out, out_n) and
+// its sample count, which replaces the world's spp.
+struct RefineArgs {
+    const float4 *chain_in;
+    float4 *chain_out;
+    uint32_t samples, out_n;
+};
 static int render_impl(rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t nparts, void *d_out,
-                       float4 *accum, uint32_t accum_frames, uint32_t frame_index);
+                       float4 *accum, uint32_t accum_frames, uint32_t frame_index,
+                       const RefineArgs *refine = nullptr);
 
 // Scheduling scratch (words): cost[npix] perm[npix] buckets[2K + kSchedWords], then the
 // per-pixel pre-pass state (float4, 16-byte aligned).
@@ -938,7 +958,7 @@ static rtx::KParams make_params(const rtx_ctx *c, uint32_t rows, uint32_t tile_r
 }
 
 static int render_impl(rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t nparts, void *d_out,
-                       float4 *accum, uint32_t accum_frames, uint32_t frame_index) {
+                       float4 *accum, uint32_t accum_frames, uint32_t frame_index, const RefineArgs *refine) {
     if (!c->have_world) return fail(RTX_ERR_STATE, "rtx_render_rows: no world uploaded");
     if (!c->have_frame) return fail(RTX_ERR_STATE, "rtx_render_rows: no frame set");
     if (tile_rows == 0 || nparts == 0 || part >= nparts)
@@ -962,6 +982,12 @@ static int render_impl(rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t n
         out = c->d_fb;
     }
     rtx::KParams p = make_params(c, rows, tile_rows, part, nparts, out, accum, accum_frames, frame_index);
+    if (refine) {
+        p.spp = refine->samples;
+        p.chain_in = refine->chain_in;
+        p.chain_out = refine->chain_out;
+        p.out_n = refine->out_n;
+    }
 
     if (c->ev_count == c->events.size()) {
         EventPair &old = c->events[c->ev_head];
@@ -1037,11 +1063,108 @@ static int render_impl(rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t n
     RTX_HIP(hipEventRecord(ev.stop, c->stream));
     c->ev_count++;
     c->launches++;
-    c->samples += (uint64_t)rows * f.width * c->spp;
+    c->samples += (uint64_t)rows * f.width * p.spp;
     return RTX_OK;
 }
 
 int rtx_render(rtx_ctx *c) { return rtx_render_rows(c, 1, 0, 1, nullptr); }
+
+// ---- progressive refinement along the reference's RNG chain ---------------
+int rtx_refine(rtx_ctx *c, uint32_t samples, int reset) {
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_refine: null ctx");
+    if (samples == 0) return fail(RTX_ERR_INVALID, "rtx_refine: samples is 0");
+    if (!c->have_world) return fail(RTX_ERR_STATE, "rtx_refine: no world uploaded");
+    if (!c->have_frame) return fail(RTX_ERR_STATE, "rtx_refine: no frame set");
+    if (c->frame.rng_mode == RTX_RNG_PER_SAMPLE)
+        return fail(RTX_ERR_INVALID, "rtx_refine: the per-sample RNG has no chain to continue (rtx_accumulate is its "
+                                     "progressive form)");
+    const size_t px = (size_t)c->frame.width * c->frame.height;
+    const bool fresh = reset || c->chain_n == 0 || !c->d_chain || c->chain_pixels != px ||
+                       std::memcmp(&c->frame, &c->chain_frame, sizeof c->frame) != 0;
+    const uint32_t have = fresh ? 0u : c->chain_n;
+    if (samples > 0xffffffffu - have) return fail(RTX_ERR_INVALID, "rtx_refine: more than 2^32 - 1 samples in all");
+    int rc = set_device(c);
+    if (rc) return rc;
+    if (!c->d_chain || c->chain_pixels != px) {
+        RTX_HIP(hipStreamSynchronize(c->stream));
+        (void)hipFree(c->d_chain);
+        c->d_chain = nullptr;
+        c->chain_pixels = 0;
+        c->chain_n = 0;
+        RTX_HIP(hipMalloc(&c->d_chain, px * sizeof(float4)));
+        c->chain_pixels = px;
+    }
+    c->chain_n = 0;  // until the launch is enqueued
+    RefineArgs a;
+    a.chain_in = fresh ? nullptr : c->d_chain;  // NULL: every pixel starts its chain (pixel_seed)
+    a.chain_out = c->d_chain;
+    a.samples = samples;
+    a.out_n = have + samples;
+    if (c->depth == 0) {
+        // no segment is traced and the image is zeros (rtx_render's trivial
+        // launch); the state keeps its sums (zeros for a fresh one) and N counts on
+        if (fresh) RTX_HIP(hipMemsetAsync(c->d_chain, 0, px * sizeof(float4), c->stream));
+        a.chain_in = a.chain_out = nullptr;
+    }
+    rc = render_impl(c, 1, 0, 1, nullptr, nullptr, 0, c->frame.frame_index, &a);
+    if (rc != RTX_OK) return rc;
+    c->chain_n = have + samples;
+    c->chain_frame = c->frame;
+    return RTX_OK;
+}
+
+uint32_t rtx_refined_samples(rtx_ctx *c) { return c ? c->chain_n : 0; }
+
+void *rtx_refine_state(rtx_ctx *c) { return c && c->chain_n != 0 ? c->d_chain : nullptr; }
+
+int rtx_refine_export(rtx_ctx *c, float *host_state, size_t bytes) {
+    if (!c || !host_state) return fail(RTX_ERR_INVALID, "rtx_refine_export: null argument");
+    if (c->chain_n == 0 || !c->d_chain) return fail(RTX_ERR_STATE, "rtx_refine_export: no chain state");
+    if (bytes != c->chain_pixels * sizeof(float4))
+        return fail(RTX_ERR_INVALID, "rtx_refine_export: bytes != width*height*16");
+    int rc = set_device(c);
+    if (rc) return rc;
+    RTX_HIP(hipMemcpyAsync(host_state, c->d_chain, bytes, hipMemcpyDeviceToHost, c->stream));
+    RTX_HIP(hipStreamSynchronize(c->stream));
+    return check_errors(c, "rtx_refine_export");
+}
+
+int rtx_refine_import(rtx_ctx *c, const float *host_state, size_t bytes, uint32_t samples) {
+    if (!c || !host_state) return fail(RTX_ERR_INVALID, "rtx_refine_import: null argument");
+    if (samples == 0) return fail(RTX_ERR_INVALID, "rtx_refine_import: samples is 0");
+    if (!c->have_world) return fail(RTX_ERR_STATE, "rtx_refine_import: no world uploaded");
+    if (!c->have_frame) return fail(RTX_ERR_STATE, "rtx_refine_import: no frame set");
+    if (c->frame.rng_mode == RTX_RNG_PER_SAMPLE)
+        return fail(RTX_ERR_INVALID, "rtx_refine_import: the per-sample RNG has no chain to continue");
+    const size_t px = (size_t)c->frame.width * c->frame.height;
+    if (bytes != px * sizeof(float4)) return fail(RTX_ERR_INVALID, "rtx_refine_import: bytes != width*height*16");
+    int rc = set_device(c);
+    if (rc) return rc;
+    if (!c->d_chain || c->chain_pixels != px || c->fb_pixels != px) RTX_HIP(hipStreamSynchronize(c->stream));
+    c->chain_n = 0;
+    if (!c->d_chain || c->chain_pixels != px) {
+        (void)hipFree(c->d_chain);
+        c->d_chain = nullptr;
+        c->chain_pixels = 0;
+        RTX_HIP(hipMalloc(&c->d_chain, px * sizeof(float4)));
+        c->chain_pixels = px;
+    }
+    if (c->fb_pixels != px) {
+        (void)hipFree(c->d_fb);
+        c->d_fb = nullptr;
+        c->fb_pixels = 0;
+        RTX_HIP(hipMalloc(&c->d_fb, px * sizeof(float4)));
+        c->fb_pixels = px;
+    }
+    // synchronous, like rtx_copy_to_device: the caller's array is free on return
+    RTX_HIP(hipMemcpyAsync(c->d_chain, host_state, bytes, hipMemcpyHostToDevice, c->stream));
+    hipError_t e = rtx::launch_chain_image(c->d_chain, c->d_fb, px, samples, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_chain_image");
+    RTX_HIP(hipStreamSynchronize(c->stream));
+    c->chain_n = samples;
+    c->chain_frame = c->frame;
+    return RTX_OK;
+}
 
 int rtx_deinterleave_rows(rtx_ctx *c, const void *d_gathered, uint32_t width, uint32_t height,
                           uint32_t tile_rows, uint32_t nparts, void *d_image) {

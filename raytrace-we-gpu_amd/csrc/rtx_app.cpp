@@ -102,6 +102,7 @@ bool RtxCSApp::LoadContent() {
             return m_ok = false;
         }
         m_count = w.count;
+        m_depth = w.depth;
         // CreateBuffer(WorldDef, IMMUTABLE) (:393-413)
         if ((m_group ? rtx_group_upload_world(m_group, &w) : rtx_upload_world(m_ctx, &w)) != RTX_OK) {
             m_error = rtx_last_error();
@@ -133,6 +134,7 @@ bool RtxCSApp::LoadContent() {
     w.count = m_count;
     w.depth = m_cfg.depth;
     w.spp = m_cfg.spp;
+    m_depth = w.depth;
     w.spheres = m_spheres.data();
     w.mat_types = m_mat_types.data();
     w.mat_values = m_mat_values.data();
@@ -203,6 +205,62 @@ bool RtxCSApp::Accumulate(uint32_t frames, bool reset) {
     return m_ok;
 }
 
+bool RtxCSApp::Refine(uint32_t samples, bool reset) {
+    if (!m_ok) return false;
+    if (m_group) {
+        m_error = "Refine: one context only (a group does not refine)";
+        return m_ok = false;
+    }
+    if (rtx_refine(m_ctx, samples, reset ? 1 : 0) != RTX_OK) {
+        m_error = rtx_last_error();
+        m_ok = false;
+    }
+    return m_ok;
+}
+
+bool RtxCSApp::SaveState(const std::string &path) {
+    if (m_group || !m_ctx) {
+        m_error = "SaveState: one context only";
+        return false;
+    }
+    ChainStateHeader h;
+    h.width = m_frame.width;
+    h.height = m_frame.height;
+    h.samples = rtx_refined_samples(m_ctx);
+    h.world_hash = chain_world_hash(m_count, m_depth, m_spheres.data(), m_mat_types.data(), m_mat_values.data());
+    h.frame_hash = chain_frame_hash(m_frame);
+    std::vector<float> st(4 * (size_t)h.width * h.height);
+    if (rtx_refine_export(m_ctx, st.data(), st.size() * sizeof(float)) != RTX_OK) {
+        m_error = rtx_last_error();
+        return false;
+    }
+    if (!write_chain_state(path, h, st.data())) {
+        m_error = "SaveState: cannot write " + path;
+        return false;
+    }
+    return true;
+}
+
+bool RtxCSApp::LoadState(const std::string &path) {
+    if (m_group || !m_ctx) {
+        m_error = "LoadState: one context only";
+        return false;
+    }
+    ChainStateHeader want;
+    want.width = m_frame.width;
+    want.height = m_frame.height;
+    want.world_hash = chain_world_hash(m_count, m_depth, m_spheres.data(), m_mat_types.data(), m_mat_values.data());
+    want.frame_hash = chain_frame_hash(m_frame);
+    std::vector<float> st;
+    uint32_t samples = 0;
+    if (!read_chain_state(path, want, st, samples, m_error)) return false;
+    if (rtx_refine_import(m_ctx, st.data(), st.size() * sizeof(float), samples) != RTX_OK) {
+        m_error = rtx_last_error();
+        return false;
+    }
+    return true;
+}
+
 bool RtxCSApp::Download(std::vector<float> &rgba) {
     rgba.resize(4 * (size_t)m_cfg.width * m_cfg.height);
     const size_t bytes = rgba.size() * sizeof(float);
@@ -244,6 +302,152 @@ bool write_ppm(const std::string &path, const float *rgba, uint32_t w, uint32_t 
         ok = std::fwrite(row.data(), 1, row.size(), f) == row.size();
     }
     return std::fclose(f) == 0 && ok;
+}
+
+namespace {
+
+constexpr char kChainMagic[8] = {'R', 'T', 'X', 'C', 'H', 'A', 'I', 'N'};
+constexpr size_t kChainHeaderBytes = 8 + 4 * 4 + 2 * 8;
+
+uint64_t fnv1a(uint64_t h, const void *data, size_t n) {
+    const unsigned char *p = static_cast<const unsigned char *>(data);
+    for (size_t i = 0; i < n; ++i) h = (h ^ p[i]) * 0x100000001b3ull;
+    return h;
+}
+constexpr uint64_t kFnvBasis = 0xcbf29ce484222325ull;
+
+void put_le(unsigned char *p, uint64_t v, int bytes) {
+    for (int i = 0; i < bytes; ++i) p[i] = (unsigned char)(v >> (8 * i));
+}
+uint64_t get_le(const unsigned char *p, int bytes) {
+    uint64_t v = 0;
+    for (int i = 0; i < bytes; ++i) v |= (uint64_t)p[i] << (8 * i);
+    return v;
+}
+// float <-> little-endian bytes, whatever the host's order
+void put_f32(unsigned char *p, float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    put_le(p, u, 4);
+}
+float get_f32(const unsigned char *p) {
+    const uint32_t u = (uint32_t)get_le(p, 4);
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+std::string hex64(uint64_t v) {
+    char b[24];
+    std::snprintf(b, sizeof b, "%016llx", (unsigned long long)v);
+    return b;
+}
+
+}  // namespace
+
+uint64_t chain_world_hash(uint32_t count, uint32_t depth, const float *spheres, const float *mat_types,
+                          const float *mat_values) {
+    unsigned char head[8];
+    put_le(head, count, 4);
+    put_le(head + 4, depth, 4);
+    uint64_t h = fnv1a(kFnvBasis, head, sizeof head);
+    unsigned char b[4];
+    const float *arr[3] = {spheres, mat_types, mat_values};
+    const size_t len[3] = {4 * (size_t)count, count, 4 * (size_t)count};
+    for (int a = 0; a < 3; ++a)
+        for (size_t i = 0; i < len[a]; ++i) {
+            put_f32(b, arr[a][i]);
+            h = fnv1a(h, b, 4);
+        }
+    return h;
+}
+
+uint64_t chain_frame_hash(const rtx_frame &frame) {
+    // every field of rtx_frame is a 4-byte value and the struct has no
+    // padding: hashed word by word in little-endian order
+    static_assert(sizeof(rtx_frame) % 4 == 0, "rtx_frame is a sequence of 4-byte fields");
+    uint64_t h = kFnvBasis;
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(&frame);
+    for (size_t i = 0; i < sizeof(rtx_frame); i += 4) {
+        uint32_t u;
+        std::memcpy(&u, p + i, 4);
+        unsigned char b[4];
+        put_le(b, u, 4);
+        h = fnv1a(h, b, 4);
+    }
+    return h;
+}
+
+bool write_chain_state(const std::string &path, const ChainStateHeader &hdr, const float *state) {
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    unsigned char head[kChainHeaderBytes];
+    std::memcpy(head, kChainMagic, 8);
+    put_le(head + 8, kChainStateVersion, 4);
+    put_le(head + 12, hdr.width, 4);
+    put_le(head + 16, hdr.height, 4);
+    put_le(head + 20, hdr.samples, 4);
+    put_le(head + 24, hdr.world_hash, 8);
+    put_le(head + 32, hdr.frame_hash, 8);
+    bool ok = std::fwrite(head, 1, sizeof head, f) == sizeof head;
+    std::vector<unsigned char> row(16 * (size_t)hdr.width);
+    for (uint32_t y = 0; y < hdr.height && ok; ++y) {
+        for (size_t i = 0; i < 4 * (size_t)hdr.width; ++i) put_f32(&row[4 * i], state[4 * (size_t)y * hdr.width + i]);
+        ok = std::fwrite(row.data(), 1, row.size(), f) == row.size();
+    }
+    return std::fclose(f) == 0 && ok;
+}
+
+bool read_chain_state(const std::string &path, const ChainStateHeader &expect, std::vector<float> &state,
+                      uint32_t &samples, std::string &error) {
+    FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) {
+        error = "chain state: cannot open " + path;
+        return false;
+    }
+    auto refuse = [&](const std::string &why) {
+        std::fclose(f);
+        error = "chain state " + path + ": " + why;
+        return false;
+    };
+    unsigned char head[kChainHeaderBytes];
+    if (std::fread(head, 1, sizeof head, f) != sizeof head) return refuse("truncated header");
+    if (std::memcmp(head, kChainMagic, 8) != 0) return refuse("wrong magic (not a chain-state file)");
+    const uint32_t version = (uint32_t)get_le(head + 8, 4);
+    if (version != kChainStateVersion)
+        return refuse("format version " + std::to_string(version) + ", this build reads " +
+                      std::to_string(kChainStateVersion));
+    const uint32_t w = (uint32_t)get_le(head + 12, 4), h = (uint32_t)get_le(head + 16, 4);
+    const uint32_t n = (uint32_t)get_le(head + 20, 4);
+    const uint64_t wh = get_le(head + 24, 8), fh = get_le(head + 32, 8);
+    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 31)) return refuse("bad width or height in the header");
+    if (n == 0) return refuse("a state of 0 samples");
+    if (std::fseek(f, 0, SEEK_END) != 0) return refuse("cannot seek");
+    const long end = std::ftell(f);
+    const uint64_t want_len = kChainHeaderBytes + 16ull * w * h;
+    if (end < 0) return refuse("cannot tell its length");
+    if ((uint64_t)end < want_len)
+        return refuse("truncated: its length is " + std::to_string(end) + " bytes, its header's " + std::to_string(w) +
+                      "x" + std::to_string(h) + " needs " + std::to_string(want_len));
+    if ((uint64_t)end != want_len)
+        return refuse("its header's " + std::to_string(w) + "x" + std::to_string(h) + " does not match its length (" +
+                      std::to_string(end) + " bytes, expected " + std::to_string(want_len) + ")");
+    if (w != expect.width || h != expect.height)
+        return refuse("size mismatch: the file is " + std::to_string(w) + "x" + std::to_string(h) + ", the frame " +
+                      std::to_string(expect.width) + "x" + std::to_string(expect.height));
+    if (wh != expect.world_hash)
+        return refuse("world mismatch: the file's world hash " + hex64(wh) + ", this world's " +
+                      hex64(expect.world_hash));
+    if (fh != expect.frame_hash)
+        return refuse("frame mismatch: the file's frame hash " + hex64(fh) + ", this frame's " +
+                      hex64(expect.frame_hash));
+    if (std::fseek(f, (long)kChainHeaderBytes, SEEK_SET) != 0) return refuse("cannot seek");
+    std::vector<unsigned char> raw(16 * (size_t)w * h);
+    if (std::fread(raw.data(), 1, raw.size(), f) != raw.size()) return refuse("truncated payload");
+    state.resize(4 * (size_t)w * h);
+    for (size_t i = 0; i < state.size(); ++i) state[i] = get_f32(&raw[4 * i]);
+    samples = n;
+    std::fclose(f);
+    return true;
 }
 
 }  // namespace rtx

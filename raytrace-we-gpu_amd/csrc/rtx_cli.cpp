@@ -10,6 +10,16 @@
 //           [--reference-frame] [--pfm out.pfm] [--ppm out.ppm]
 //           [--gpus N | --devices a,b,c] [--gather auto|rccl|copy] [--tile-rows T]
 //           [--split rows|frames]
+//           [--refine S1,S2,...] [--save-state FILE] [--load-state FILE]
+// --refine S1,S2,... refines the image along the reference's own RNG chain,
+// one rtx_refine per entry (--spp and --frames are not used): after the last
+// step the image is the plain render's at spp = S1 + S2 + ... (plus a loaded
+// state's samples), and --pfm / --ppm write it. --save-state FILE writes the
+// chain state after the last step; --load-state FILE imports one before the
+// first step (a later session continues where an earlier one stopped) and
+// exits nonzero if the file is damaged or belongs to another size, world or
+// frame. One context only. The JSON line then carries "refine" (the steps),
+// "refined_samples" and "loaded_samples".
 // --gpus N renders each frame across devices 0..N-1 (rtx_group: interleaved
 // tiles of T rows, default 5, one gather to device 0); --devices names them,
 // and a repeated device (0,0,0) rehearses the same split on one GPU, its
@@ -51,7 +61,8 @@ static void usage() {
                  "               [--aperture A] [--accumulate] [--lambert-guard] [--reference-frame]\n"
                  "               [--pfm FILE] [--ppm FILE]\n"
                  "               [--gpus N | --devices a,b,c] [--gather auto|rccl|copy] [--tile-rows T]\n"
-                 "               [--split rows|frames]\n");
+                 "               [--split rows|frames]\n"
+                 "               [--refine S1,S2,...] [--save-state FILE] [--load-state FILE]\n");
 }
 
 int main(int argc, char **argv) {
@@ -71,7 +82,8 @@ int main(int argc, char **argv) {
     }
     int frames = 1, device = 0;
     bool accumulate = false;
-    std::string pfm, ppm;
+    std::string pfm, ppm, save_state, load_state;
+    std::vector<uint32_t> refine;  // --refine: samples per step
     std::vector<int> devices;  // non-empty: a group
     int gather = RTX_GATHER_AUTO;
     bool group_opts = false;   // --gather / --tile-rows given
@@ -93,6 +105,26 @@ int main(int argc, char **argv) {
         else if (a == "--device") device = std::atoi(next());
         else if (a == "--pfm") pfm = next();
         else if (a == "--ppm") ppm = next();
+        else if (a == "--save-state") save_state = next();
+        else if (a == "--load-state") load_state = next();
+        else if (a == "--refine") {
+            refine.clear();
+            const std::string list = next();
+            for (size_t pos = 0; pos <= list.size();) {
+                const size_t comma = std::min(list.find(',', pos), list.size());
+                const std::string item = list.substr(pos, comma - pos);
+                const unsigned long long v = item.empty() || item.size() > 10 ||
+                                                     item.find_first_not_of("0123456789") != std::string::npos
+                                                 ? 0ull
+                                                 : std::strtoull(item.c_str(), nullptr, 10);
+                if (v == 0ull || v > 0xffffffffull) {
+                    usage();
+                    return 2;
+                }
+                refine.push_back((uint32_t)v);
+                pos = comma + 1;
+            }
+        }
         else if (a == "--simple-camera") cfg.simple_camera = true;
         else if (a == "--aperture") cfg.lens_aperture = (float)std::atof(next());
         else if (a == "--accumulate") accumulate = true;
@@ -187,6 +219,15 @@ int main(int argc, char **argv) {
                              "(a group accumulates with --split frames)\n");
         return 2;
     }
+    const bool refining = !refine.empty();
+    if ((!save_state.empty() || !load_state.empty()) && !refining) {
+        std::fprintf(stderr, "rtx_cli: --save-state and --load-state need --refine\n");
+        return 2;
+    }
+    if (refining && (grouped || accumulate)) {
+        std::fprintf(stderr, "rtx_cli: --refine runs on one context, without --accumulate\n");
+        return 2;
+    }
     if (grouped && cfg.tile_rows == 0) {
         usage();
         return 2;
@@ -198,7 +239,19 @@ int main(int argc, char **argv) {
         return 1;
     }
     app.Update();
-    app.Render();  // warm-up frame (also the reference's single frame, main.cpp:38-39)
+    uint32_t loaded_samples = 0;
+    if (refining) {
+        // no warm-up frame: every step's samples count. A saved state first.
+        if (!load_state.empty()) {
+            if (!app.LoadState(load_state)) {
+                std::fprintf(stderr, "rtx_cli: --load-state refused: %s\n", app.last_error().c_str());
+                return 1;
+            }
+            loaded_samples = rtx_refined_samples(app.context());
+        }
+    } else {
+        app.Render();  // warm-up frame (also the reference's single frame, main.cpp:38-39)
+    }
     // ... and one round of whole frames: the row-split warm-up sized every member's
     // buffers for its rows only, and the timed call is to find them fitting
     if (split_frames) app.Accumulate((uint32_t)devices.size(), true);
@@ -216,7 +269,11 @@ int main(int argc, char **argv) {
         app.Update();
         app.Accumulate((uint32_t)frames, true);
     }
-    for (int k = 0; k < frames && !split_frames; ++k) {
+    for (size_t k = 0; k < refine.size(); ++k) {
+        app.Update();  // the same PerFrame bytes every Update: the chain state is kept
+        if (!app.Refine(refine[k], k == 0 && load_state.empty())) break;
+    }
+    for (int k = 0; k < frames && !split_frames && !refining; ++k) {
         app.Update();
         if (accumulate) {
             if (rtx_accumulate(app.context(), k == 0) != RTX_OK) {
@@ -286,6 +343,24 @@ int main(int argc, char **argv) {
                     (unsigned long long)st.sphere_tests, members, devs.c_str(),
                     rtx_group_gather_mode(grp) == RTX_GATHER_RCCL ? "rccl" : "copy", rccl.c_str(), split.c_str(),
                     per.c_str(), gather_ms, split_frames ? "fold_ms" : "deinterleave_ms", deint_ms);
+    } else if (refining) {
+        if (sync_rc != RTX_OK || rtx_get_stats(app.context(), &st) != RTX_OK) {
+            std::fprintf(stderr, "rtx_cli: refine failed: %s\n", rtx_last_error());
+            return 1;
+        }
+        std::string steps;
+        for (size_t k = 0; k < refine.size(); ++k) steps += (k ? ", " : "") + std::to_string(refine[k]);
+        std::printf("{\"width\": %u, \"height\": %u, \"depth\": %u, \"spheres\": %u, \"cbuffers\": %s, "
+                    "\"refine\": [%s], \"loaded_samples\": %u, \"refined_samples\": %u, \"wall_s\": %.6f, "
+                    "\"kernel_ms\": %.4f, \"msamples_per_s\": %.3f, \"segments\": %llu, \"sphere_tests\": %llu}\n",
+                    cfg.width, cfg.height, cfg.depth, app.sphere_count(), cfg.cbuffers ? "true" : "false",
+                    steps.c_str(), loaded_samples, rtx_refined_samples(app.context()), wall, st.kernel_ms,
+                    (double)st.samples / wall / 1e6, (unsigned long long)st.segments,
+                    (unsigned long long)st.sphere_tests);
+        if (!save_state.empty() && !app.SaveState(save_state)) {
+            std::fprintf(stderr, "rtx_cli: --save-state failed: %s\n", app.last_error().c_str());
+            return 1;
+        }
     } else {
         rtx_get_stats(app.context(), &st);
         std::printf("{\"width\": %u, \"height\": %u, \"spp\": %u, \"depth\": %u, \"spheres\": %u, "

@@ -171,6 +171,16 @@ struct KParams {
     // [wave][kPsSlots][ps_cap] float4, batches of at most ps_px pixels
     float *ps_scratch;
     uint32_t ps_px, ps_cap;
+    // refine launch (rtx_refine): `spp` more samples of every pixel along its
+    // own RNG chain. Appended: the frame constants above keep their kernarg
+    // offsets (rtx_kernels.hip frame_vals). All three are uniform and read by
+    // the kRefine kernel instances only, which launch_render takes when
+    // chain_out is set; a plain launch leaves them 0.
+    const float4 *chain_in;        // a pixel started from scratch takes (acc, seed) from chain_in[gid]
+                                   // instead of (0, pixel_seed) (NULL: the chain's first launch)
+    float4 *chain_out;             // a finished pixel's (acc, seed) goes to chain_out[gid] (may be chain_in:
+                                   // a slot is read by whoever starts its pixel, before anyone finishes it)
+    uint32_t out_n;                // output_pixel divides by this, the chain's samples after the launch
 };
 
 // Longest-processing-time-first scheduling for the persistent kernel: a
@@ -245,6 +255,8 @@ hipError_t launch_deinterleave(const float4 *gathered, float4 *image, uint32_t w
 // for k = 0 .. m-1 in that order, image[p] = toGamma(accum[p] / divisor).
 hipError_t launch_fold_frames(float4 *accum, const float4 *sums, uint32_t m, size_t slot_pixels, size_t pixels,
                               uint32_t divisor, float4 *image, hipStream_t stream);
+// k_chain_image (include/rtx.h rtx_refine_import): image[p] = toGamma(chain[p].xyz / n), w = 1.
+hipError_t launch_chain_image(const float4 *chain, float4 *image, size_t pixels, uint32_t n, hipStream_t stream);
 hipError_t launch_debug_hit_world(const KScene &s, const float *rays, uint32_t nrays,
                                   float t_min, float t_max, uint32_t start_block, float *out,
                                   hipStream_t stream);

@@ -1683,8 +1683,11 @@ __device__ __forceinline__ void begin_sample(const KParams &P, const Frame &F, u
 // cost-ordered render with a slot-ordered staging image (KParams::out_slot):
 // the pixel goes to out_slot[slot] and k_unpermute moves it to out[gid] with
 // coalesced stores; ~0u (or no staging): straight to out[gid].
+// kRefine (the refine launch's kernel instances, KParams::chain_in): the
+// divisor is the chain's samples so far (out_n), not this launch's.
+template <bool kRefine = false>
 __device__ __forceinline__ void output_pixel(const KParams &P, uint32_t gid, f3 sum, uint32_t slot = ~0u) {
-    float n = (float)P.spp;
+    float n = (float)(kRefine ? P.out_n : P.spp);
     if (P.accum) {  // progressive: running linear sum over frames
         float4 a = P.accum[gid];
         a.x = a.x + sum.x;
@@ -1711,7 +1714,7 @@ __device__ __forceinline__ void output_pixel(const KParams &P, uint32_t gid, f3 
 #define RTX_EXTRA_BYTES 0
 #endif
 // A pixel's output (output_pixel), or the scheduling pre-pass's record of it.
-template <bool kCost = false>
+template <bool kCost = false, bool kRefine = false>
 __device__ __forceinline__ void write_pixel(const KParams &P, const Lane &L) {
     if constexpr (kCost) {  // scheduling pre-pass: record the pixel's segments
         P.cost_out[L.gid] = L.segs - L.seg0;
@@ -1719,7 +1722,10 @@ __device__ __forceinline__ void write_pixel(const KParams &P, const Lane &L) {
         if (P.state) P.state[L.gid] = make_float4(L.acc.x, L.acc.y, L.acc.z, L.seed);
         return;
     }
-    output_pixel(P, L.gid, L.acc, L.slot);
+    output_pixel<kRefine>(P, L.gid, L.acc, L.slot);
+    // refine launch: the chain's state after this pixel's last sample, which
+    // the next rtx_refine continues from (start_pixel)
+    if constexpr (kRefine) P.chain_out[L.gid] = make_float4(L.acc.x, L.acc.y, L.acc.z, L.seed);
     // A/B build (HBM traffic): the pixel's final state also
     // goes back to its (dead) resume slot: +16 B per pixel of the same
     // scattered cost-order stores as the image
@@ -1938,7 +1944,7 @@ __device__ __forceinline__ bool promote(const KParams &P, const Lane &L, uint32_
 // pixel at a sample boundary if it is projected to need more segments than
 // this (KParams::prom_min once the wave's queue is exhausted). Returns true
 // when the pixel was promoted.
-template <bool kCost = false>
+template <bool kCost = false, bool kRefine = false>
 __device__ __forceinline__ bool shade(const KParams &P, const Frame &F, Lane &L, int hit, float t,
                                       uint32_t prom_thr = 0u) {
     L.segs++;
@@ -1949,7 +1955,7 @@ __device__ __forceinline__ bool shade(const KParams &P, const Frame &F, Lane &L,
     if (ended) {
         L.sample++;
         if (L.sample >= P.spp) {
-            write_pixel<kCost>(P, L);
+            write_pixel<kCost, kRefine>(P, L);
             L.active = false;
             diag_pixel_end(P, L.gid);
         } else if (!kCost && prom_thr != 0u && promote(P, L, prom_thr)) {
@@ -2012,6 +2018,7 @@ __device__ __forceinline__ Frame load_frame(const KParams &P) {
 
 // Start pixel `gid` (local index of this launch's rows) on this lane.
 // Launches with spp == 0 or depth == 0 never get here (k_render_trivial).
+template <bool kRefine = false>
 __device__ __forceinline__ void start_pixel(const KParams &P, const Frame &F, uint32_t gid, Lane &L) {
     L.gid = gid;
     lane_pixel(P, gid, L.x, L.y);
@@ -2027,6 +2034,15 @@ __device__ __forceinline__ void start_pixel(const KParams &P, const Frame &F, ui
         L.acc = mk3(0.0f, 0.0f, 0.0f);
         L.sample = 0;
         L.seed = pixel_seed(P, L.x, L.y, 0);
+        if constexpr (kRefine) {
+            // refine launch: sample 0 of this launch continues the pixel's
+            // chain (chain_in NULL: the chain's first launch, a fresh seed)
+            if (P.chain_in) {
+                const float4 ch = P.chain_in[gid];
+                L.acc = mk3(ch.x, ch.y, ch.z);
+                L.seed = ch.w;
+            }
+        }
         if (P.state && !P.cost_out) L.seg0 |= kSeg0Restart;  // promote() counts its samples from 0
     }
     L.active = true;
@@ -2065,6 +2081,7 @@ __device__ __forceinline__ uint32_t dyn_level(const KParams &P, const Lane &L, f
 // slot of [lo, hi) (the queue counter counts from lo); ONE atomic per wave
 // per refill (ballot + lane rank). Returns true once the queue is
 // exhausted (wave-uniform).
+template <bool kRefine = false>
 __device__ __forceinline__ bool refill(const KParams &P, const Frame &F, uint32_t lo, uint32_t hi, Lane &L) {
     const uint64_t idle = __ballot(!L.active);
     if (idle == 0ull) return false;
@@ -2089,7 +2106,7 @@ __device__ __forceinline__ bool refill(const KParams &P, const Frame &F, uint32_
         if (!L.active) {
             const uint32_t g = rank < avail ? L.cb + rank : nb + (rank - avail);
             if (g < hi) {
-                start_pixel(P, F, P.perm ? P.perm[g] : g, L);
+                start_pixel<kRefine>(P, F, P.perm ? P.perm[g] : g, L);
                 L.slot = g;
                 diag_pixel_start(P, L.gid, 0);
             }
@@ -2110,7 +2127,7 @@ __device__ __forceinline__ bool refill(const KParams &P, const Frame &F, uint32_
     if (!L.active) {
         const uint32_t g = base + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
         if (g < hi) {
-            start_pixel(P, F, P.perm ? P.perm[g] : g, L);
+            start_pixel<kRefine>(P, F, P.perm ? P.perm[g] : g, L);
             L.slot = g;
             diag_pixel_start(P, L.gid, 0);
         }
@@ -2133,6 +2150,7 @@ struct HeavyState {
     bool t1_done, t2_done;
     uint32_t tier;       // 1, 2, or 0 (normal wave)
 };
+template <bool kRefine = false>
 __device__ __forceinline__ bool take_from(const KParams &P, const Frame &F, uint32_t *ctr, uint32_t lo, uint32_t hi,
                                           uint32_t room, uint64_t act, Lane &L, bool &done) {
     const uint32_t lane = threadIdx.x & 63u;
@@ -2146,23 +2164,24 @@ __device__ __forceinline__ bool take_from(const KParams &P, const Frame &F, uint
     const uint32_t take = min(room, hi - h);
     const uint32_t rk = (uint32_t)__popcll(~act & ((1ull << lane) - 1ull));
     if (!L.active && rk < take) {
-        start_pixel(P, F, P.perm[h + rk], L);
+        start_pixel<kRefine>(P, F, P.perm[h + rk], L);
         L.slot = h + rk;
         diag_pixel_start(P, L.gid, ctr == P.heavy ? 1ull : 2ull);
     }
     if (h + room >= hi) done = true;
     return true;
 }
+template <bool kRefine = false>
 __device__ __forceinline__ void take_heavy(const KParams &P, const Frame &F, HeavyState &H, Lane &L) {
     const uint64_t act = __ballot(L.active);
     const uint32_t have = (uint32_t)__popcll(act);
     if (have == 0u) H.tier = 0;
-    if (have == 0u && !H.t1_done && take_from(P, F, P.heavy, 0, H.k1, kHeavy1, act, L, H.t1_done)) {
+    if (have == 0u && !H.t1_done && take_from<kRefine>(P, F, P.heavy, 0, H.k1, kHeavy1, act, L, H.t1_done)) {
         H.tier = 1;
         return;
     }
     if (H.tier == 1u) return;  // tier-1 waves keep to their few rays
-    if (!H.t2_done && have < kHeavy2 && take_from(P, F, P.heavy + 2, H.k1, H.kh, kHeavy2 - have, act, L, H.t2_done))
+    if (!H.t2_done && have < kHeavy2 && take_from<kRefine>(P, F, P.heavy + 2, H.k1, H.kh, kHeavy2 - have, act, L, H.t2_done))
         H.tier = 2;
 }
 
@@ -2517,6 +2536,8 @@ __device__ __forceinline__ bool pre_stop(const KParams &P, uint32_t npix, Lane &
 // lanes pull pixels from the (cost-ordered) queue until it is exhausted;
 // otherwise an exact grid, one pixel per lane. kCost: the scheduling
 // pre-pass (P.cost_out: per-pixel segments, P.state: the state to resume).
+// kRefine: a refine launch's instance (KParams::chain_in, chain_out, out_n:
+// start_pixel, write_pixel, output_pixel); the plain instances hold none of it.
 // Tile-major enumerations of a W x rows pixel grid: j in [0, tile_span) ->
 // pixel index (row-major within a T x T tile, tiles row-major), or ~0u for a
 // slot of a partial tile; T = 0: row-major, the identity. The cost sort
@@ -2541,7 +2562,7 @@ __device__ __forceinline__ uint32_t tile_pixel(uint32_t j, uint32_t width, uint3
 #endif
 constexpr uint32_t kExactTile = RTX_EXACT_TILE;
 
-template <bool kPersist, bool kCost = false, bool kPF = false, bool kLin = false>
+template <bool kPersist, bool kCost = false, bool kPF = false, bool kLin = false, bool kRefine = false>
 __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
     constexpr bool kCulled = kPF && RTX_CULL && !kLin;  // the culled scan (large scenes, not the linear mode)
     // dynamic LDS: [candidate list, list_bytes<kPF>][coop rays, kCoopBytes][coop LDS copy of the spheres]
@@ -2581,7 +2602,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
     bool exhausted = !kPersist;
     if (!kPersist) {
         const uint32_t gid = tile_pixel(blockIdx.x * kRB + threadIdx.x, P.width, P.rows_local, kExactTile);
-        if (gid < npix) start_pixel(P, F, gid, L);
+        if (gid < npix) start_pixel<kRefine>(P, F, gid, L);
     }
     // heavy slots [0, kh) of the queue (k_heavy_split; tier 1 = [0, k1)), normal slots [kh, npix)
     HeavyState H;
@@ -2600,10 +2621,10 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
     Diag D;
     D.begin();
     for (;;) {
-        if (!(H.t1_done && H.t2_done) && (H.tier != 0u || __ballot(L.active) == 0ull)) take_heavy(P, F, H, L);
+        if (!(H.t1_done && H.t2_done) && (H.tier != 0u || __ballot(L.active) == 0ull)) take_heavy<kRefine>(P, F, H, L);
         if (H.tier != 0u && __ballot(L.active) == 0ull) H.tier = 0;  // drained, no heavy slot left
         const bool heavy = H.tier != 0u;
-        if (!heavy && !exhausted) exhausted = refill(P, F, kh, npix, L);
+        if (!heavy && !exhausted) exhausted = refill<kRefine>(P, F, kh, npix, L);
         if (kPersist && kCost && P.pre_done && exhausted && pre_stop(P, npix, L)) continue;
         const uint64_t act = __ballot(L.active);
         D.section(0);
@@ -2659,7 +2680,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
                 // the tail's pixels may be promoted (tier-1 waves already
                 // trace one ray with every lane; promoting tier-2 pixels
                 // measured 1-6 ms slower at R = 2, 4, 8: profiles/R3r_*)
-                promoted = shade<kCost>(P, F, L, min(my_hit, last), my_best,
+                promoted = shade<kCost, kRefine>(P, F, L, min(my_hit, last), my_best,
                                         prom_on && exhausted && H.tier == 0u ? P.prom_min : 0u);
             }
             if (prom_on)
@@ -2685,7 +2706,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
                 float best = __uint_as_float(0x7f800000u);
                 const int hit = hit_world_culled(P.scene, L.o, L.d, L.a, L.inv_a, kTMin, best, list);
                 D.section(1);
-                promoted = shade<kCost>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
+                promoted = shade<kCost, kRefine>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
             }
         } else if ((RTX_PF_LDS || RTX_PF_RING) && kPF) {  // every lane of the wave fills the scan's LDS tile
             float best = __uint_as_float(0x7f800000u);
@@ -2693,7 +2714,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
             const int hit = hit_world_pre_ld<kPF, decltype(ldc), true>(P.scene, ldc, L.o, L.d, L.a, L.inv_a, kTMin,
                                                                        best, list, nullptr, 0, pf_tile, L.active);
             D.section(1);
-            if (L.active) promoted = shade<kCost>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
+            if (L.active) promoted = shade<kCost, kRefine>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
         } else if (L.active) {
             float best = __uint_as_float(0x7f800000u);
             // scenes that fit the coop's LDS copy resolve their candidates
@@ -2704,7 +2725,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
                                                         RTX_SCAN_LDS ? sl.pr : nullptr)
                                 : hit_world_pre<kPF>(P.scene, L.o, L.d, L.a, L.inv_a, kTMin, best, list, pack);
             D.section(1);
-            promoted = shade<kCost>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
+            promoted = shade<kCost, kRefine>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
         }
         D.section(2);
         if (prom_on)  // pixels written this iteration (promoted ones are counted by whoever finishes them)
@@ -2832,6 +2853,7 @@ __device__ __forceinline__ int take_promoted_groups(const KParams &P, const Fram
 // copy, took LDS the render's blocks needed: at R = 8 (7 k_trace waves per
 // CU) only ~79 % of k_render's lanes were resident (profiles/R6r_pixel_timelines.jsonl).
 constexpr uint32_t kTraceThreads = 256;
+template <bool kRefine = false>
 __global__ void __launch_bounds__(kTraceThreads, 4) k_trace(const KParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_mem[];
     const SphLds sl = lds_copy(P.scene, reinterpret_cast<float *>(s_mem), true, kTraceThreads);
@@ -2871,7 +2893,7 @@ __global__ void __launch_bounds__(kTraceThreads, 4) k_trace(const KParams P) {
                 base = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)base, 0, 64));
                 const uint32_t rank = (uint32_t)__popcll(need & ((1ull << (lane & ~(g - 1u))) - 1ull));
                 if (!W.active && base + rank < k1) {
-                    start_pixel(P, F, P.perm[base + rank], W);
+                    start_pixel<kRefine>(P, F, P.perm[base + rank], W);
                     W.slot = base + rank;
                     diag_pixel_start(P, W.gid, 1ull);
                 }
@@ -2927,7 +2949,7 @@ __global__ void __launch_bounds__(kTraceThreads, 4) k_trace(const KParams P) {
         }
         if (ended) {
             if (first) {
-                write_pixel<false>(P, W);
+                write_pixel<false, kRefine>(P, W);
                 diag_pixel_end(P, W.gid);
                 if (W.slot == ~0u)  // a promoted pixel: k_render's exit count
                     __hip_atomic_fetch_add(&P.prom[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -3340,6 +3362,18 @@ __global__ void __launch_bounds__(kBlock) k_render_trivial(const KParams P) {
     write_pixel(P, L);
 }
 
+// A chain state's image (rtx_refine_import): output_pixel's arithmetic on
+// the stored sums, n samples per pixel.
+__global__ void __launch_bounds__(kBlock) k_chain_image(const float4 *__restrict__ chain, float4 *__restrict__ image,
+                                                        uint64_t pixels, uint32_t samples) {
+    const float n = (float)samples;
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x; p < pixels; p += stride) {
+        const float4 a = chain[p];
+        image[p] = make_float4(to_gamma(a.x / n), to_gamma(a.y / n), to_gamma(a.z / n), 1.0f);
+    }
+}
+
 // Gathered [nparts][max_rows][width] -> image [height][width].
 __global__ void __launch_bounds__(kBlock) k_deinterleave(const float4 *__restrict__ g,
                                                          float4 *__restrict__ img, uint32_t width,
@@ -3622,20 +3656,30 @@ static bool use_pf(const KScene &s) { return s.n_pad > kScanPfMin; }
 // every block of every segment (the reference's Hittable_list order of work,
 // with the prefilter), through the per-wave LDS tile in the chain render.
 static bool use_lin(const KScene &s) { return use_pf(s) && s.cpre == nullptr; }
-template <bool kPersist, bool kCost>
+// kRefine: the refine launch's instances (KParams::chain_in, chain_out,
+// out_n; the plain instances hold none of that code).
+template <bool kPersist, bool kCost, bool kRefine = false>
 static const void *render_fn(const KScene &s) {
-    return !use_pf(s)   ? (const void *)k_render<kPersist, kCost, false>
-           : use_lin(s) ? (const void *)k_render<kPersist, kCost, true, true>
-                        : (const void *)k_render<kPersist, kCost, true>;
+    return !use_pf(s)   ? (const void *)k_render<kPersist, kCost, false, false, kRefine>
+           : use_lin(s) ? (const void *)k_render<kPersist, kCost, true, true, kRefine>
+                        : (const void *)k_render<kPersist, kCost, true, false, kRefine>;
 }
-template <bool kPersist, bool kCost>
+template <bool kPersist, bool kCost, bool kRefine = false>
 static void launch_k(const KScene &s, uint32_t blocks, size_t lds, hipStream_t stream, const KParams &a) {
     if (!use_pf(s))
-        hipLaunchKernelGGL((k_render<kPersist, kCost, false>), dim3(blocks), dim3(kRB), lds, stream, a);
+        hipLaunchKernelGGL((k_render<kPersist, kCost, false, false, kRefine>), dim3(blocks), dim3(kRB), lds, stream, a);
     else if (use_lin(s))
-        hipLaunchKernelGGL((k_render<kPersist, kCost, true, true>), dim3(blocks), dim3(kRB), lds, stream, a);
+        hipLaunchKernelGGL((k_render<kPersist, kCost, true, true, kRefine>), dim3(blocks), dim3(kRB), lds, stream, a);
     else
-        hipLaunchKernelGGL((k_render<kPersist, kCost, true>), dim3(blocks), dim3(kRB), lds, stream, a);
+        hipLaunchKernelGGL((k_render<kPersist, kCost, true, false, kRefine>), dim3(blocks), dim3(kRB), lds, stream, a);
+}
+// a refine launch (chain_out set) takes the kRefine instance
+template <bool kPersist, bool kCost>
+static void launch_kr(const KScene &s, uint32_t blocks, size_t lds, hipStream_t stream, const KParams &a) {
+    if (a.chain_out)
+        launch_k<kPersist, kCost, true>(s, blocks, lds, stream, a);
+    else
+        launch_k<kPersist, kCost, false>(s, blocks, lds, stream, a);
 }
 
 // Dynamic LDS of the chain-RNG kernels: candidate lists + coop ray slots +
@@ -3735,9 +3779,15 @@ hipError_t launch_render(const KParams &p_in, const KSchedule &sched, hipStream_
     if (e == hipSuccess) e = allow_lds(render_fn<false, false>(p.scene), lds);
     if (e == hipSuccess) e = allow_lds(render_fn<false, true>(p.scene), lds);
     if (e == hipSuccess) e = allow_lds(render_fn<true, true>(p.scene), lds);
+    if (p.chain_out) {
+        if (e == hipSuccess) e = allow_lds(render_fn<true, false, true>(p.scene), lds);
+        if (e == hipSuccess) e = allow_lds(render_fn<false, false, true>(p.scene), lds);
+        if (e == hipSuccess) e = allow_lds(render_fn<false, true, true>(p.scene), lds);
+        if (e == hipSuccess) e = allow_lds(render_fn<true, true, true>(p.scene), lds);
+    }
     if (e != hipSuccess) return e;
     if (!sched.cost || p.spp < kLptMinSpp) {
-        launch_k<false, false>(p.scene, need_x, lds, stream, p);
+        launch_kr<false, false>(p.scene, need_x, lds, stream, p);
         return hipGetLastError();
     }
     if (sched.nbuckets != kCostBuckets || sched.npix < lanes) return hipErrorInvalidValue;
@@ -3779,9 +3829,9 @@ hipError_t launch_render(const KParams &p_in, const KSchedule &sched, hipStream_
             c.pre_done = sched.buckets + 2 * kCostBuckets + 6;  // heavy[6], zeroed above
             c.pre_stop = (uint32_t)(kPreStopFrac * (double)pblocks * kRB);
         }
-        launch_k<true, true>(p.scene, pblocks, lds, stream, c);
+        launch_kr<true, true>(p.scene, pblocks, lds, stream, c);
     } else {
-        launch_k<false, true>(p.scene, need_x, lds, stream, c);
+        launch_kr<false, true>(p.scene, need_x, lds, stream, c);
     }
     // 2. counting sort by cost, descending
     // (in pixel tiles except for a small share: R = 8 12.7 vs 13.0 ms, S6r, S6v)
@@ -3880,14 +3930,17 @@ hipError_t launch_render(const KParams &p_in, const KSchedule &sched, hipStream_
         e = hipEventRecord(sched.ev_fork, stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(sched.aux, sched.ev_fork, 0);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_trace, dim3((trace_waves + kTraceThreads / 64u - 1u) / (kTraceThreads / 64u)), dim3(kTraceThreads), tlds,
-                           sched.aux, q);
+        const dim3 tgrid((trace_waves + kTraceThreads / 64u - 1u) / (kTraceThreads / 64u));
+        if (q.chain_out)
+            hipLaunchKernelGGL(k_trace<true>, tgrid, dim3(kTraceThreads), tlds, sched.aux, q);
+        else
+            hipLaunchKernelGGL(k_trace<false>, tgrid, dim3(kTraceThreads), tlds, sched.aux, q);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipEventRecord(sched.ev_join, sched.aux);
         if (e != hipSuccess) return e;
         blocks = max(1u, blocks - (trace_waves + 3u) / 4u);
     }
-    launch_k<true, false>(p.scene, blocks, lds, stream, q);
+    launch_kr<true, false>(p.scene, blocks, lds, stream, q);
     e = hipGetLastError();
     if (e == hipSuccess && trace_waves > 0) e = hipStreamWaitEvent(stream, sched.ev_join, 0);
     if (e == hipSuccess && sched.stage) {
@@ -3914,6 +3967,13 @@ hipError_t launch_fold_frames(float4 *accum, const float4 *sums, uint32_t m, siz
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)pixels - 1) / kBlock + 1, kFoldBlocks);
     hipLaunchKernelGGL(k_fold_frames, dim3(blocks), dim3(kBlock), 0, stream, accum, sums, m, (uint64_t)slot_pixels,
                        (uint64_t)pixels, divisor, image);
+    return hipGetLastError();
+}
+
+hipError_t launch_chain_image(const float4 *chain, float4 *image, size_t pixels, uint32_t n, hipStream_t stream) {
+    if (pixels == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)pixels - 1) / kBlock + 1, kFoldBlocks);
+    hipLaunchKernelGGL(k_chain_image, dim3(blocks), dim3(kBlock), 0, stream, chain, image, (uint64_t)pixels, n);
     return hipGetLastError();
 }
 

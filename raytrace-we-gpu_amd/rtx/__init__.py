@@ -131,6 +131,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_accumulated_frames": (u32, [ctx]),
         "rtx_render_sum": (C.c_int, [ctx, u32, vp]),
         "rtx_fold_frames": (C.c_int, [ctx, vp, vp, u32, C.c_size_t, C.c_size_t, u32, vp]),
+        "rtx_refine": (C.c_int, [ctx, u32, C.c_int]),
+        "rtx_refined_samples": (u32, [ctx]),
+        "rtx_refine_state": (vp, [ctx]),
+        "rtx_refine_export": (C.c_int, [ctx, f, C.c_size_t]),
+        "rtx_refine_import": (C.c_int, [ctx, f, C.c_size_t, u32]),
         "rtx_camera_set_aperture": (C.c_int, [C.POINTER(rtx_frame), C.c_float]),
         "rtx_part_rows": (u32, [u32, u32, u32, u32]),
         "rtx_deinterleave_rows": (C.c_int, [ctx, vp, u32, u32, u32, u32, vp]),
@@ -185,6 +190,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                 "rtx_build_info", "rtx_debug_scan_rate", "rtx_set_scan_mode"}
     optional |= {n for n in sig if n.startswith("rtx_group_")}  # arrived without a version bump
     optional |= {"rtx_render_sum", "rtx_fold_frames"}            # ... with rtx_group_accumulate
+    optional |= {n for n in sig if n.startswith("rtx_refine")}   # ... probe "rtx_refine"
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -424,6 +430,34 @@ class Context:
         k = 0 .. m-1 in that order, d_image[p] = toGamma(d_accum[p] / divisor)."""
         _check(self._lib.rtx_fold_frames(self._h, C.c_void_p(d_accum or 0), C.c_void_p(d_sums or 0), m, slot_pixels,
                                          pixels, divisor, C.c_void_p(d_image or 0)), "rtx_fold_frames", self._lib)
+
+    def refine(self, samples: int, reset: bool = False) -> int:
+        """`samples` more samples of every pixel along the reference's own RNG
+        chain (rtx_refine): the framebuffer is then, bit for bit, the plain
+        render at spp = the samples refined so far, which it returns."""
+        _check(self._lib.rtx_refine(self._h, samples, 1 if reset else 0), "rtx_refine", self._lib)
+        return int(self._lib.rtx_refined_samples(self._h))
+
+    @property
+    def refined_samples(self) -> int:
+        """Samples per pixel in the chain state (0: none)."""
+        return int(self._lib.rtx_refined_samples(self._h))
+
+    def refine_export(self) -> np.ndarray:
+        """The chain state, (H, W, 4) float32: xyz the pixel's linear sample
+        sum, w its seed after its last sample (rtx_refine_export)."""
+        f = self.frame
+        out = np.empty((f.height, f.width, 4), np.float32)
+        _check(self._lib.rtx_refine_export(self._h, _fptr(out), out.nbytes), "rtx_refine_export", self._lib)
+        return out
+
+    def refine_import(self, state: np.ndarray, samples: int):
+        """Install a chain state of `samples` samples per pixel for the current
+        world and frame and write its image (rtx_refine_import); the next
+        refine() continues from it."""
+        state = np.ascontiguousarray(state, np.float32)
+        _check(self._lib.rtx_refine_import(self._h, _fptr(state), state.nbytes, samples), "rtx_refine_import",
+               self._lib)
 
     def deinterleave(self, d_gathered: int, width: int, height: int, tile_rows: int, nparts: int,
                      d_image: int):
