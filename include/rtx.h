@@ -44,7 +44,9 @@ extern "C" {
  *         rtx_refine_state, rtx_refine_export and rtx_refine_import
  *         (progressive samples along the reference's own RNG chain, and its
  *         checkpoint); purely additive again: probe for the symbol
- *         (dlsym "rtx_refine").
+ *         (dlsym "rtx_refine"). rtx_refine_set_keys, rtx_refine_last_keys and
+ *         rtx_refine_cost (the cost map a refine launch records, and queue keys
+ *         carried from it: dlsym "rtx_refine_set_keys").
  *  1.4.5 (later builds, no version bump): rtx_render_sum, rtx_fold_frames
  *         (RTX_FOLD_MAX), rtx_group_accumulate, rtx_group_accumulated_frames
  *         and rtx_group_get_accumulate_times (progressive frames dealt across
@@ -400,10 +402,45 @@ RTX_API int rtx_fold_frames(rtx_ctx *ctx, void *d_accum, const void *d_sums, uin
  * spp (frame_index * spp + s), so "continue" has no single meaning there;
  * rtx_accumulate is that mode's progressive form. RTX_ERR_STATE: no world or
  * no frame.
- * Not covered (later changes): row parts and rtx_group (a group-wide refine),
- * and ordering the pixel queue by the previous call's measured per-pixel cost
- * instead of a pre-pass per call. */
+ * Not covered (later changes): row parts and rtx_group (a group-wide refine).
+ * The pixel queue's order: see rtx_refine_set_keys below. */
 RTX_API int rtx_refine(rtx_ctx *ctx, uint32_t samples, int reset);
+/* The cost map and the queue keys of a refine launch (1.4.5, later builds, no
+ * version bump: probe with dlsym "rtx_refine_set_keys").
+ * Every rtx_refine launch records, per pixel, the ray segments (hit_world
+ * calls) it spent on that pixel — exact in every kernel path; the map's sum is
+ * the launch's rtx_stats.segments. By default (RTX_REFINE_KEYS_PREPASS) every
+ * scheduled launch still orders its pixel queue by a cost pre-pass of its own.
+ * Under RTX_REFINE_KEYS_CARRIED the next launch builds the queue from the
+ * previous launch's map instead and runs no pre-pass, when it can: the map is
+ * valid, this call has at least 8 samples (smaller steps are unscheduled), and
+ * the map covers at least the samples a pre-pass would trace (2; 1 for scenes
+ * of more than 1,024 spheres). Otherwise the launch takes the pre-pass as
+ * before. Images, the chain state, the map and the segment counts are bit for
+ * bit the same in either mode: results never depend on the schedule.
+ * The map is valid after any rtx_refine that traced segments. It falls with
+ * the chain state (reset, rtx_upload_world, an rtx_set_frame with other bytes
+ * or another size), after rtx_refine_import (the state file holds no map: the
+ * first step after a resume takes the pre-pass), after a depth == 0 step, and
+ * when samples * depth >= 2^32 (a count could wrap). rtx_render,
+ * rtx_render_rows, rtx_accumulate, rtx_render_sum, rtx_set_schedule,
+ * rtx_set_scan_mode and rtx_refine_set_keys leave it alone. */
+#define RTX_REFINE_KEYS_PREPASS 0     /* a cost pre-pass per launch (the default) */
+#define RTX_REFINE_KEYS_CARRIED 1     /* the previous launch's cost map, where valid */
+#define RTX_REFINE_KEYS_UNSCHEDULED 2 /* rtx_refine_last_keys only */
+/* RTX_ERR_INVALID, before any HIP call, for a null ctx or another mode. Keeps
+ * the chain state and the map. */
+RTX_API int rtx_refine_set_keys(rtx_ctx *ctx, int mode);
+/* What the last rtx_refine launch was keyed by: RTX_REFINE_KEYS_PREPASS,
+ * RTX_REFINE_KEYS_CARRIED, or RTX_REFINE_KEYS_UNSCHEDULED (the exact grid of a
+ * step below 8 samples, the depth == 0 launch, or no launch yet). A null ctx:
+ * RTX_ERR_INVALID. */
+RTX_API int rtx_refine_last_keys(rtx_ctx *ctx);
+/* The cost map to host memory (synchronous, like rtx_download): width*height
+ * uint32 in framebuffer order (row 0 = bottom), and in *samples the samples of
+ * the step it covers. bytes == width*height*4. RTX_ERR_STATE if there is no
+ * valid map; RTX_ERR_INVALID for a null argument or other bytes. */
+RTX_API int rtx_refine_cost(rtx_ctx *ctx, uint32_t *host_cost, size_t bytes, uint32_t *samples);
 /* N: samples per pixel in the chain state (0 for NULL / none). */
 RTX_API uint32_t rtx_refined_samples(rtx_ctx *ctx);
 /* Device pointer of the chain state (width*height float4), NULL if none. */

@@ -126,6 +126,11 @@ public:
     // (rtx_refine), the image then the plain render's at the samples refined
     // so far. One context only (a group-wide refine is a later change).
     bool Refine(uint32_t samples, bool reset);
+    // What orders a scheduled Refine's pixel queue: RTX_REFINE_KEYS_PREPASS (a
+    // cost pre-pass per step, the default) or RTX_REFINE_KEYS_CARRIED (the
+    // previous step's measured per-pixel cost; rtx_refine_set_keys). The
+    // images are the same. One context only.
+    bool SetRefineKeys(int mode);
     // The chain state as a file (write_chain_state below), tagged with this
     // app's world and frame; LoadState refuses a file of another size, world
     // or frame (last_error() says which) and otherwise imports it

@@ -112,6 +112,15 @@ struct rtx_ctx {
     size_t chain_pixels = 0;
     uint32_t chain_n = 0;
     rtx_frame chain_frame{};
+    // ... and the cost map (rtx_refine_cost): per pixel the segments the last
+    // refine launch spent on it, width*height uint32 behind the chain state in
+    // the same allocation (cost_map_of). cost_s_prev: the samples it covers;
+    // the map is valid while that and chain_n are nonzero, so it falls with
+    // the chain state. refine_keys: rtx_refine_set_keys; last_keys: what the
+    // last refine launch was keyed by.
+    uint32_t cost_s_prev = 0;
+    int refine_keys = RTX_REFINE_KEYS_PREPASS;
+    int last_keys = RTX_REFINE_KEYS_UNSCHEDULED;
     // measurement
     unsigned long long *d_counters = nullptr;
     unsigned long long *d_wave_times = nullptr;  // diagnostic (rtx_debug_wave_times)
@@ -836,7 +845,13 @@ struct RefineArgs {
     const float4 *chain_in;
     float4 *chain_out;
     uint32_t samples, out_n;
+    uint32_t *cost_map;  // KSchedule::cost_map
+    uint32_t carry_spp;  // ... carry_spp (0: pre-pass keys)
 };
+// The chain state's allocation: chain_pixels float4, then the cost map.
+static size_t chain_bytes(size_t px) { return px * (sizeof(float4) + sizeof(uint32_t)); }
+static uint32_t *cost_map_of(const rtx_ctx *c) { return reinterpret_cast<uint32_t *>(c->d_chain + c->chain_pixels); }
+static bool cost_map_valid(const rtx_ctx *c) { return c->d_chain && c->chain_n != 0 && c->cost_s_prev != 0; }
 static int render_impl(rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t nparts, void *d_out,
                        float4 *accum, uint32_t accum_frames, uint32_t frame_index,
                        const RefineArgs *refine = nullptr);
@@ -1058,6 +1073,8 @@ static int render_impl(rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t n
     sched.epoch = (uint32_t)++c->epoch;
     sched.ev_fork = c->ev_fork;
     sched.ev_join = c->ev_join;
+    sched.cost_map = refine ? refine->cost_map : nullptr;
+    sched.carry_spp = refine ? refine->carry_spp : 0u;
     hipError_t e = rtx::launch_render(p, sched, c->stream);
     if (e != hipSuccess) return hip_fail(e, "launch_render");
     RTX_HIP(hipEventRecord(ev.stop, c->stream));
@@ -1091,11 +1108,18 @@ int rtx_refine(rtx_ctx *c, uint32_t samples, int reset) {
         c->d_chain = nullptr;
         c->chain_pixels = 0;
         c->chain_n = 0;
-        RTX_HIP(hipMalloc(&c->d_chain, px * sizeof(float4)));
+        RTX_HIP(hipMalloc(&c->d_chain, chain_bytes(px)));
         c->chain_pixels = px;
     }
+    // the previous launch's cost map keys this one when the mode asks for it
+    // and the map can (rtx_refine_keys.h); a fresh chain has none
+    const uint32_t s_prev = fresh || c->chain_n == 0 ? 0u : c->cost_s_prev;
+    const bool carried = rtx::launch_is_carried(c->refine_keys, s_prev, samples, c->n_pad > rtx::kScanPfMin);
     c->chain_n = 0;  // until the launch is enqueued
+    c->cost_s_prev = 0;
     RefineArgs a;
+    a.cost_map = cost_map_of(c);
+    a.carry_spp = carried ? s_prev : 0u;
     a.chain_in = fresh ? nullptr : c->d_chain;  // NULL: every pixel starts its chain (pixel_seed)
     a.chain_out = c->d_chain;
     a.samples = samples;
@@ -1110,7 +1134,39 @@ int rtx_refine(rtx_ctx *c, uint32_t samples, int reset) {
     if (rc != RTX_OK) return rc;
     c->chain_n = have + samples;
     c->chain_frame = c->frame;
+    // every launch that traced segments leaves its map (none at depth 0, or
+    // where a count could wrap)
+    c->cost_s_prev = rtx::cost_map_after(samples, c->depth);
+    c->last_keys = c->depth == 0 || samples < rtx::kLptMinSpp ? RTX_REFINE_KEYS_UNSCHEDULED
+                   : carried                                  ? RTX_REFINE_KEYS_CARRIED
+                                                              : RTX_REFINE_KEYS_PREPASS;
     return RTX_OK;
+}
+
+int rtx_refine_set_keys(rtx_ctx *c, int mode) {
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_refine_set_keys: null ctx");
+    if (mode != RTX_REFINE_KEYS_PREPASS && mode != RTX_REFINE_KEYS_CARRIED)
+        return fail(RTX_ERR_INVALID, "rtx_refine_set_keys: unknown mode");
+    c->refine_keys = mode;  // the chain state and the map stay
+    return RTX_OK;
+}
+
+int rtx_refine_last_keys(rtx_ctx *c) {
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_refine_last_keys: null ctx");
+    return c->last_keys;
+}
+
+int rtx_refine_cost(rtx_ctx *c, uint32_t *host_cost, size_t bytes, uint32_t *samples) {
+    if (!c || !host_cost || !samples) return fail(RTX_ERR_INVALID, "rtx_refine_cost: null argument");
+    if (!cost_map_valid(c)) return fail(RTX_ERR_STATE, "rtx_refine_cost: no valid cost map");
+    if (bytes != c->chain_pixels * sizeof(uint32_t))
+        return fail(RTX_ERR_INVALID, "rtx_refine_cost: bytes != width*height*4");
+    int rc = set_device(c);
+    if (rc) return rc;
+    RTX_HIP(hipMemcpyAsync(host_cost, cost_map_of(c), bytes, hipMemcpyDeviceToHost, c->stream));
+    RTX_HIP(hipStreamSynchronize(c->stream));
+    *samples = c->cost_s_prev;
+    return check_errors(c, "rtx_refine_cost");
 }
 
 uint32_t rtx_refined_samples(rtx_ctx *c) { return c ? c->chain_n : 0; }
@@ -1142,11 +1198,12 @@ int rtx_refine_import(rtx_ctx *c, const float *host_state, size_t bytes, uint32_
     if (rc) return rc;
     if (!c->d_chain || c->chain_pixels != px || c->fb_pixels != px) RTX_HIP(hipStreamSynchronize(c->stream));
     c->chain_n = 0;
+    c->cost_s_prev = 0;  // an installed state has no cost map: the next step takes the pre-pass
     if (!c->d_chain || c->chain_pixels != px) {
         (void)hipFree(c->d_chain);
         c->d_chain = nullptr;
         c->chain_pixels = 0;
-        RTX_HIP(hipMalloc(&c->d_chain, px * sizeof(float4)));
+        RTX_HIP(hipMalloc(&c->d_chain, chain_bytes(px)));
         c->chain_pixels = px;
     }
     if (c->fb_pixels != px) {

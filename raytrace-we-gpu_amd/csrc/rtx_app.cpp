@@ -218,6 +218,19 @@ bool RtxCSApp::Refine(uint32_t samples, bool reset) {
     return m_ok;
 }
 
+bool RtxCSApp::SetRefineKeys(int mode) {
+    if (!m_ok) return false;
+    if (m_group || !m_ctx) {
+        m_error = "SetRefineKeys: one context only (a group does not refine)";
+        return false;
+    }
+    if (rtx_refine_set_keys(m_ctx, mode) != RTX_OK) {
+        m_error = rtx_last_error();
+        return false;
+    }
+    return true;
+}
+
 bool RtxCSApp::SaveState(const std::string &path) {
     if (m_group || !m_ctx) {
         m_error = "SaveState: one context only";

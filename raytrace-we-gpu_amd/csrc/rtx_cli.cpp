@@ -11,6 +11,7 @@
 //           [--gpus N | --devices a,b,c] [--gather auto|rccl|copy] [--tile-rows T]
 //           [--split rows|frames]
 //           [--refine S1,S2,...] [--save-state FILE] [--load-state FILE]
+//           [--refine-keys prepass|carried]
 // --refine S1,S2,... refines the image along the reference's own RNG chain,
 // one rtx_refine per entry (--spp and --frames are not used): after the last
 // step the image is the plain render's at spp = S1 + S2 + ... (plus a loaded
@@ -19,7 +20,10 @@
 // first step (a later session continues where an earlier one stopped) and
 // exits nonzero if the file is damaged or belongs to another size, world or
 // frame. One context only. The JSON line then carries "refine" (the steps),
-// "refined_samples" and "loaded_samples".
+// "refined_samples" and "loaded_samples". --refine-keys carried orders each
+// step's pixel queue by the previous step's measured per-pixel cost instead of
+// a pre-pass per step (rtx_refine_set_keys; the image is the same), and the
+// JSON line carries "refine_keys".
 // --gpus N renders each frame across devices 0..N-1 (rtx_group: interleaved
 // tiles of T rows, default 5, one gather to device 0); --devices names them,
 // and a repeated device (0,0,0) rehearses the same split on one GPU, its
@@ -62,7 +66,8 @@ static void usage() {
                  "               [--pfm FILE] [--ppm FILE]\n"
                  "               [--gpus N | --devices a,b,c] [--gather auto|rccl|copy] [--tile-rows T]\n"
                  "               [--split rows|frames]\n"
-                 "               [--refine S1,S2,...] [--save-state FILE] [--load-state FILE]\n");
+                 "               [--refine S1,S2,...] [--save-state FILE] [--load-state FILE]\n"
+                 "               [--refine-keys prepass|carried]\n");
 }
 
 int main(int argc, char **argv) {
@@ -84,6 +89,7 @@ int main(int argc, char **argv) {
     bool accumulate = false;
     std::string pfm, ppm, save_state, load_state;
     std::vector<uint32_t> refine;  // --refine: samples per step
+    int refine_keys = -1;          // --refine-keys (RTX_REFINE_KEYS_*; -1: not given)
     std::vector<int> devices;  // non-empty: a group
     int gather = RTX_GATHER_AUTO;
     bool group_opts = false;   // --gather / --tile-rows given
@@ -123,6 +129,15 @@ int main(int argc, char **argv) {
                 }
                 refine.push_back((uint32_t)v);
                 pos = comma + 1;
+            }
+        }
+        else if (a == "--refine-keys") {
+            const std::string m = next();
+            if (m == "prepass") refine_keys = RTX_REFINE_KEYS_PREPASS;
+            else if (m == "carried") refine_keys = RTX_REFINE_KEYS_CARRIED;
+            else {
+                usage();
+                return 2;
             }
         }
         else if (a == "--simple-camera") cfg.simple_camera = true;
@@ -224,6 +239,10 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "rtx_cli: --save-state and --load-state need --refine\n");
         return 2;
     }
+    if (refine_keys >= 0 && !refining) {
+        std::fprintf(stderr, "rtx_cli: --refine-keys needs --refine\n");
+        return 2;
+    }
     if (refining && (grouped || accumulate)) {
         std::fprintf(stderr, "rtx_cli: --refine runs on one context, without --accumulate\n");
         return 2;
@@ -241,6 +260,10 @@ int main(int argc, char **argv) {
     app.Update();
     uint32_t loaded_samples = 0;
     if (refining) {
+        if (refine_keys >= 0 && !app.SetRefineKeys(refine_keys)) {
+            std::fprintf(stderr, "rtx_cli: --refine-keys failed: %s\n", app.last_error().c_str());
+            return 1;
+        }
         // no warm-up frame: every step's samples count. A saved state first.
         if (!load_state.empty()) {
             if (!app.LoadState(load_state)) {
@@ -352,11 +375,12 @@ int main(int argc, char **argv) {
         for (size_t k = 0; k < refine.size(); ++k) steps += (k ? ", " : "") + std::to_string(refine[k]);
         std::printf("{\"width\": %u, \"height\": %u, \"depth\": %u, \"spheres\": %u, \"cbuffers\": %s, "
                     "\"refine\": [%s], \"loaded_samples\": %u, \"refined_samples\": %u, \"wall_s\": %.6f, "
-                    "\"kernel_ms\": %.4f, \"msamples_per_s\": %.3f, \"segments\": %llu, \"sphere_tests\": %llu}\n",
+                    "\"kernel_ms\": %.4f, \"msamples_per_s\": %.3f, \"segments\": %llu, \"sphere_tests\": %llu, "
+                    "\"refine_keys\": \"%s\"}\n",
                     cfg.width, cfg.height, cfg.depth, app.sphere_count(), cfg.cbuffers ? "true" : "false",
                     steps.c_str(), loaded_samples, rtx_refined_samples(app.context()), wall, st.kernel_ms,
                     (double)st.samples / wall / 1e6, (unsigned long long)st.segments,
-                    (unsigned long long)st.sphere_tests);
+                    (unsigned long long)st.sphere_tests, refine_keys == RTX_REFINE_KEYS_CARRIED ? "carried" : "prepass");
         if (!save_state.empty() && !app.SaveState(save_state)) {
             std::fprintf(stderr, "rtx_cli: --save-state failed: %s\n", app.last_error().c_str());
             return 1;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "rtx_grid.h"
+#include "rtx_refine_keys.h"  // kCostBuckets, kCostSpp, kCostSppLarge, kLptMinSpp; the carried key
 
 struct rtx_ctx;  // include/rtx.h
 
@@ -160,7 +161,7 @@ struct KParams {
                                    // [4] heartbeat: s_memrealtime >> 10 of a tracing wave (valve); NULL: off
     uint32_t *errors;              // launch error bits (kErr*), read back by rtx_sync / rtx_get_stats
     unsigned long long *err_diag;  // the first valve firing's record (kErrDiagWords; NULL: none)
-    uint32_t *prom_q;              // [prom_cap][8] (gid, sample, seed, acc.xyz, -, epoch)
+    uint32_t *prom_q;              // [prom_cap][8] (gid, sample, seed, acc.xyz, segments so far (refine), epoch)
     uint32_t prom_cap, prom_min, epoch;
     uint32_t *heavy;               // [0] tier-1 counter [1] kh [2] tier-2 counter [3] k1 [4] k0
                                    // [5] mean segments per pixel at the full spp (float bits) (NULL = none)
@@ -181,6 +182,15 @@ struct KParams {
     float4 *chain_out;             // a finished pixel's (acc, seed) goes to chain_out[gid] (may be chain_in:
                                    // a slot is read by whoever starts its pixel, before anyone finishes it)
     uint32_t out_n;                // output_pixel divides by this, the chain's samples after the launch
+    // the refine launch's cost map (rtx_refine_cost), appended like the three
+    // above and read by the kRefine instances only
+    uint32_t *cost_map;            // whoever finishes pixel gid stores the segments this launch spent on it
+                                   // in cost_map[gid] (never NULL in a kRefine instance). Whoever starts
+                                   // the pixel reads the slot first: the pre-pass's count of a resumed
+                                   // pixel (the kRefine pre-pass stores it here too), or in a carried
+                                   // launch the previous launch's count
+    uint32_t carry_spp;            // carried launch: the samples the map's previous counts cover, s_prev; no
+                                   // pre-pass ran and `state` is NULL (cost_in = cost_map). 0: not carried
 };
 
 // Longest-processing-time-first scheduling for the persistent kernel: a
@@ -226,21 +236,17 @@ struct KSchedule {
     uint32_t *prom_q;   // promotion queue storage, prom_cap entries of 8 words
     uint32_t prom_cap;
     uint32_t epoch;     // launch counter: a promotion entry is ready when its last word equals it
+    // refine launches: the context's cost map (KParams::cost_map; not part of
+    // the scratch above: it lives from one launch to the next) and, when this
+    // launch is keyed by it, the samples it covers (0: pre-pass keys)
+    uint32_t *cost_map;
+    uint32_t carry_spp;
 };
-constexpr uint32_t kCostBuckets = 256;
 // Scheduling words after the two bucket arrays (counts, cursors), zeroed per
 // launch: heavy[8] (KParams::heavy; heavy[6]: the pre-pass's pre_done), then
 // prom[8] (KParams::prom).
 constexpr uint32_t kSchedWords = 16;
-#ifndef RTX_COST_SPP
-#define RTX_COST_SPP 2
-#endif
-constexpr uint32_t kCostSpp = RTX_COST_SPP;  // pre-pass samples per pixel (kept: the render resumes after them)
-#ifndef RTX_COST_SPP_LARGE
-#define RTX_COST_SPP_LARGE 1
-#endif
-constexpr uint32_t kCostSppLarge = RTX_COST_SPP_LARGE;  // ... for scenes above kScanPfMin spheres (C5: 1,997 vs 2,018 ms)
-constexpr uint32_t kLptMinSpp = 8;  // below this the pre-pass costs more than it saves: exact grid
+// (kCostBuckets, kCostSpp, kCostSppLarge and kLptMinSpp: rtx_refine_keys.h)
 constexpr uint32_t kBlock = 256;    // threads per block of the auxiliary kernels (4 waves)
 
 hipError_t launch_render(const KParams &p, const KSchedule &sched, hipStream_t stream);

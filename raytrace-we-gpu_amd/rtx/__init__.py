@@ -50,6 +50,8 @@ SCAN_MODES = {"auto": 0, "linear": 1}  # rtx_set_scan_mode (RTX_SCAN_AUTO / RTX_
 FN = dict(sqrt=0, div=1, sin=2, cos=3, log2=4, exp2=5, pow=6, basehash=7,
           hash1=8, hash2=9, hash3=10, rius=11, lambert_dir=12, lambert_dir_guard=13)
 FRAME_LAMBERT_GUARD = 1  # rtx_frame.flags bit (RTX_FRAME_LAMBERT_GUARD)
+# rtx_refine_set_keys / rtx_refine_last_keys (RTX_REFINE_KEYS_*; "unscheduled": last_keys only)
+REFINE_KEYS = {"prepass": 0, "carried": 1, "unscheduled": 2}
 GATHER_MODES = {"auto": 0, "rccl": 1, "copy": 2}  # rtx_group_create (RTX_GATHER_*)
 GROUP_MAX = 64  # RTX_GROUP_MAX
 
@@ -136,6 +138,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_refine_state": (vp, [ctx]),
         "rtx_refine_export": (C.c_int, [ctx, f, C.c_size_t]),
         "rtx_refine_import": (C.c_int, [ctx, f, C.c_size_t, u32]),
+        "rtx_refine_set_keys": (C.c_int, [ctx, C.c_int]),
+        "rtx_refine_last_keys": (C.c_int, [ctx]),
+        "rtx_refine_cost": (C.c_int, [ctx, C.POINTER(u32), C.c_size_t, C.POINTER(u32)]),
         "rtx_camera_set_aperture": (C.c_int, [C.POINTER(rtx_frame), C.c_float]),
         "rtx_part_rows": (u32, [u32, u32, u32, u32]),
         "rtx_deinterleave_rows": (C.c_int, [ctx, vp, u32, u32, u32, u32, vp]),
@@ -458,6 +463,33 @@ class Context:
         state = np.ascontiguousarray(state, np.float32)
         _check(self._lib.rtx_refine_import(self._h, _fptr(state), state.nbytes, samples), "rtx_refine_import",
                self._lib)
+
+    def set_refine_keys(self, mode: str):
+        """What orders a scheduled refine launch's pixel queue: "prepass" (a
+        cost pre-pass per launch, the default) or "carried" (the previous
+        launch's cost map where it is valid, no pre-pass). Results are the
+        same either way (rtx_refine_set_keys)."""
+        if mode not in ("prepass", "carried"):
+            raise ValueError(f"refine keys {mode!r}: 'prepass' or 'carried'")
+        _check(self._lib.rtx_refine_set_keys(self._h, REFINE_KEYS[mode]), "rtx_refine_set_keys", self._lib)
+
+    @property
+    def refine_last_keys(self) -> str:
+        """What the last refine launch was keyed by: "prepass", "carried" or
+        "unscheduled" (rtx_refine_last_keys)."""
+        k = int(self._lib.rtx_refine_last_keys(self._h))
+        _check(min(k, 0), "rtx_refine_last_keys", self._lib)
+        return {v: n for n, v in REFINE_KEYS.items()}[k]
+
+    def refine_cost(self):
+        """The last refine launch's cost map and the samples it covers:
+        ((H, W) uint32 ray segments per pixel, samples) (rtx_refine_cost)."""
+        f = self.frame
+        out = np.empty((f.height, f.width), np.uint32)
+        n = C.c_uint32(0)
+        _check(self._lib.rtx_refine_cost(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.nbytes, C.byref(n)),
+               "rtx_refine_cost", self._lib)
+        return out, int(n.value)
 
     def deinterleave(self, d_gathered: int, width: int, height: int, tile_rows: int, nparts: int,
                      d_image: int):
