@@ -46,7 +46,10 @@ extern "C" {
  *         checkpoint); purely additive again: probe for the symbol
  *         (dlsym "rtx_refine"). rtx_refine_set_keys, rtx_refine_last_keys and
  *         rtx_refine_cost (the cost map a refine launch records, and queue keys
- *         carried from it: dlsym "rtx_refine_set_keys").
+ *         carried from it: dlsym "rtx_refine_set_keys"). rtx_refine_adaptive,
+ *         rtx_refine_pending, rtx_refine_counts, rtx_refine_error and
+ *         rtx_adaptive_error (refinement of the pixels that are still noisy:
+ *         dlsym "rtx_refine_adaptive").
  *  1.4.5 (later builds, no version bump): rtx_render_sum, rtx_fold_frames
  *         (RTX_FOLD_MAX), rtx_group_accumulate, rtx_group_accumulated_frames
  *         and rtx_group_get_accumulate_times (progressive frames dealt across
@@ -441,8 +444,79 @@ RTX_API int rtx_refine_last_keys(rtx_ctx *ctx);
  * the step it covers. bytes == width*height*4. RTX_ERR_STATE if there is no
  * valid map; RTX_ERR_INVALID for a null argument or other bytes. */
 RTX_API int rtx_refine_cost(rtx_ctx *ctx, uint32_t *host_cost, size_t bytes, uint32_t *samples);
-/* N: samples per pixel in the chain state (0 for NULL / none). */
+/* N: samples per pixel in the chain state (0 for NULL / none): the sum of the
+ * steps since the state began. After adaptive steps (below) that is the count
+ * of a pixel that took part in every step; rtx_refine_counts has each pixel's. */
 RTX_API uint32_t rtx_refined_samples(rtx_ctx *ctx);
+
+/* ---- adaptive refinement: only the pixels that are still noisy -------------
+ * (later builds, no version bump: probe with dlsym "rtx_refine_adaptive").
+ * Next to the chain state the context keeps, per pixel, `count` (the samples
+ * in the pixel's sum) and `err` (the error estimate E of the pixel's last
+ * step). rtx_refine_adaptive traces `samples` more samples of every ACTIVE
+ * pixel along its chain and leaves every other pixel alone: its state, count,
+ * err, cost-map entry and framebuffer value are not touched. So a pixel that
+ * has taken n samples holds, bit for bit, what rtx_render writes for it at
+ * world.spp = n — the image is a mosaic of the reference's pixels at per-pixel
+ * spp — and which pixels were traced is a deterministic function of the sums.
+ *
+ * E of a step that took a pixel from n_old to n_new samples, from its linear
+ * sums before and after (fp32, in this order, IEEE division and square root,
+ * no fma):
+ *   n_old == 0 -> +inf
+ *   a = (float)n_old, b = (float)n_new, sf = (float)(n_new - n_old)
+ *   m0.c = sum_old.c / a,  m1.c = sum_new.c / b          (c = x, y, z)
+ *   d = (|m1.x - m0.x| + |m1.y - m0.y|) + |m1.z - m0.z|
+ *   l = (m1.x + m1.y) + m1.z
+ *   E = (d * sqrt(a / sf)) / sqrt(l + 0.01f)
+ * NaN sums give a NaN E. rtx_adaptive_error is that function on the host (no
+ * GPU, no context).
+ *
+ * Pixel p is active in a call (samples, threshold, max_samples) iff
+ *   some pixel q of its 3 x 3 neighbourhood inside the image has
+ *   E_q >= threshold (false for a NaN E: a NaN pixel stays NaN), and
+ *   max_samples == 0 or count_p + samples <= max_samples.
+ *
+ * The maps begin and fall with the chain state (reset, rtx_upload_world,
+ * rtx_set_frame with other bytes). The first adaptive call over a uniform
+ * state of N samples (a fresh one: N = 0; after rtx_refine or
+ * rtx_refine_import: their N) fills count with N and err with +inf, so that
+ * call traces every pixel, and after a fresh start so does the second (E stays
+ * +inf for n_old == 0).
+ *
+ * A call with active pixels is one scheduled launch over those pixels, keyed
+ * by the cost map where it is valid (rtx_refine_set_keys does not affect it;
+ * rtx_refine_last_keys reports CARRIED), and rtx_stats.samples counts
+ * active * samples. The host reads the 4-byte active count back before it
+ * sizes the launch: one small stream synchronisation per call. A call with no
+ * active pixel launches no render and changes nothing (rtx_refine_last_keys:
+ * UNSCHEDULED; rtx_refined_samples stays). *active (may be NULL) receives the
+ * number of pixels traced. Inactive pixels keep their own last step's entry
+ * of the cost map (rtx_refine_cost), whose *samples is the last call's.
+ *
+ * RTX_ERR_INVALID, before any GPU work: a null ctx, samples == 0, a NaN
+ * threshold, max_samples nonzero and below samples, rtx_refined_samples +
+ * samples above 2^32 - 1, samples * depth >= 2^32, depth == 0, a per-sample
+ * RNG frame. RTX_ERR_STATE: no world or no frame.
+ * After a call that left the counts non-uniform, rtx_refine without reset
+ * returns RTX_ERR_STATE (continue with rtx_refine_adaptive); rtx_refine_export
+ * still copies the state, rtx_refine_import installs a uniform one. Plain
+ * renders and rtx_accumulate overwrite the framebuffer only, as for rtx_refine. */
+RTX_API float rtx_adaptive_error(const float sum_old[3], uint32_t n_old,
+                                 const float sum_new[3], uint32_t n_new);
+RTX_API int rtx_refine_adaptive(rtx_ctx *ctx, uint32_t samples, float threshold,
+                                uint32_t max_samples, int reset, uint32_t *active);
+/* The number of pixels the same call would trace now: the mask only, nothing
+ * is traced or changed (a context with no state answers for a fresh one:
+ * every pixel). Synchronous. *active must not be NULL. */
+RTX_API int rtx_refine_pending(rtx_ctx *ctx, uint32_t samples, float threshold,
+                               uint32_t max_samples, uint32_t *active);
+/* The count and err maps to host memory (synchronous, like rtx_download):
+ * width*height uint32 / float in framebuffer order, bytes == width*height*4.
+ * RTX_ERR_STATE if there is no chain state. A uniform state that no adaptive
+ * call has touched yet reads as count N and err +inf. */
+RTX_API int rtx_refine_counts(rtx_ctx *ctx, uint32_t *host_counts, size_t bytes);
+RTX_API int rtx_refine_error(rtx_ctx *ctx, float *host_err, size_t bytes);
 /* Device pointer of the chain state (width*height float4), NULL if none. */
 RTX_API void *rtx_refine_state(rtx_ctx *ctx);
 /* The chain state to host memory (synchronous, like rtx_download):

@@ -126,6 +126,11 @@ public:
     // (rtx_refine), the image then the plain render's at the samples refined
     // so far. One context only (a group-wide refine is a later change).
     bool Refine(uint32_t samples, bool reset);
+    // `samples` more samples of the pixels that are still noisy
+    // (rtx_refine_adaptive: an error estimate >= threshold in the pixel's
+    // 3 x 3 neighbourhood, and its count within max_samples; 0: no cap);
+    // *active (may be NULL): how many were traced. One context only.
+    bool RefineAdaptive(uint32_t samples, float threshold, uint32_t max_samples, bool reset, uint32_t *active);
     // What orders a scheduled Refine's pixel queue: RTX_REFINE_KEYS_PREPASS (a
     // cost pre-pass per step, the default) or RTX_REFINE_KEYS_CARRIED (the
     // previous step's measured per-pixel cost; rtx_refine_set_keys). The

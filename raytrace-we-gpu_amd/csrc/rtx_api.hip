@@ -121,6 +121,15 @@ struct rtx_ctx {
     uint32_t cost_s_prev = 0;
     int refine_keys = RTX_REFINE_KEYS_PREPASS;
     int last_keys = RTX_REFINE_KEYS_UNSCHEDULED;
+    // adaptive refinement (rtx_refine_adaptive): the per-pixel maps beside the
+    // chain state, allocated by the first adaptive call (adapt_maps).
+    // adapt_valid: they describe the chain state; otherwise the state is
+    // uniform (every count is chain_n, every error +inf) and the next adaptive
+    // call fills them so. adapt_mixed: the counts may differ (some call traced
+    // a proper subset). Both only mean something while chain_n != 0.
+    uint32_t *d_adapt = nullptr;
+    size_t adapt_pixels = 0;
+    bool adapt_valid = false, adapt_mixed = false;
     // measurement
     unsigned long long *d_counters = nullptr;
     unsigned long long *d_wave_times = nullptr;  // diagnostic (rtx_debug_wave_times)
@@ -337,6 +346,7 @@ void rtx_destroy(rtx_ctx *c) {
     (void)hipFree(c->d_fb);
     (void)hipFree(c->d_accum);
     (void)hipFree(c->d_chain);
+    (void)hipFree(c->d_adapt);
     (void)hipFree(c->d_counters);
     (void)hipFree(c->d_wave_times);
     (void)hipFree(c->d_sched);
@@ -847,6 +857,7 @@ struct RefineArgs {
     uint32_t samples, out_n;
     uint32_t *cost_map;  // KSchedule::cost_map
     uint32_t carry_spp;  // ... carry_spp (0: pre-pass keys)
+    const rtx::KAdaptive *adaptive = nullptr;  // an adaptive launch: its maps and active count
 };
 // The chain state's allocation: chain_pixels float4, then the cost map.
 static size_t chain_bytes(size_t px) { return px * (sizeof(float4) + sizeof(uint32_t)); }
@@ -1075,12 +1086,13 @@ static int render_impl(rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t n
     sched.ev_join = c->ev_join;
     sched.cost_map = refine ? refine->cost_map : nullptr;
     sched.carry_spp = refine ? refine->carry_spp : 0u;
-    hipError_t e = rtx::launch_render(p, sched, c->stream);
+    const rtx::KAdaptive *ad = refine ? refine->adaptive : nullptr;
+    hipError_t e = ad ? rtx::launch_render_adaptive(p, sched, *ad, c->stream) : rtx::launch_render(p, sched, c->stream);
     if (e != hipSuccess) return hip_fail(e, "launch_render");
     RTX_HIP(hipEventRecord(ev.stop, c->stream));
     c->ev_count++;
     c->launches++;
-    c->samples += (uint64_t)rows * f.width * p.spp;
+    c->samples += (ad ? (uint64_t)ad->active : (uint64_t)rows * f.width) * p.spp;
     return RTX_OK;
 }
 
@@ -1100,6 +1112,9 @@ int rtx_refine(rtx_ctx *c, uint32_t samples, int reset) {
                        std::memcmp(&c->frame, &c->chain_frame, sizeof c->frame) != 0;
     const uint32_t have = fresh ? 0u : c->chain_n;
     if (samples > 0xffffffffu - have) return fail(RTX_ERR_INVALID, "rtx_refine: more than 2^32 - 1 samples in all");
+    if (!fresh && c->adapt_valid && c->adapt_mixed)
+        return fail(RTX_ERR_STATE, "rtx_refine: the state's per-pixel sample counts differ after adaptive steps: "
+                                   "continue with rtx_refine_adaptive, or reset");
     int rc = set_device(c);
     if (rc) return rc;
     if (!c->d_chain || c->chain_pixels != px) {
@@ -1117,6 +1132,7 @@ int rtx_refine(rtx_ctx *c, uint32_t samples, int reset) {
     const bool carried = rtx::launch_is_carried(c->refine_keys, s_prev, samples, c->n_pad > rtx::kScanPfMin);
     c->chain_n = 0;  // until the launch is enqueued
     c->cost_s_prev = 0;
+    c->adapt_valid = c->adapt_mixed = false;  // uniform counts after this launch: the next adaptive call fills its maps
     RefineArgs a;
     a.cost_map = cost_map_of(c);
     a.carry_spp = carried ? s_prev : 0u;
@@ -1199,6 +1215,7 @@ int rtx_refine_import(rtx_ctx *c, const float *host_state, size_t bytes, uint32_
     if (!c->d_chain || c->chain_pixels != px || c->fb_pixels != px) RTX_HIP(hipStreamSynchronize(c->stream));
     c->chain_n = 0;
     c->cost_s_prev = 0;  // an installed state has no cost map: the next step takes the pre-pass
+    c->adapt_valid = c->adapt_mixed = false;  // ... and is uniform
     if (!c->d_chain || c->chain_pixels != px) {
         (void)hipFree(c->d_chain);
         c->d_chain = nullptr;
@@ -1222,6 +1239,180 @@ int rtx_refine_import(rtx_ctx *c, const float *host_state, size_t bytes, uint32_
     c->chain_frame = c->frame;
     return RTX_OK;
 }
+
+// ---- adaptive refinement (rtx_adaptive.h) ----------------------------------
+float rtx_adaptive_error(const float sum_old[3], uint32_t n_old, const float sum_new[3], uint32_t n_new) {
+    return rtx::adaptive_error_with(sum_old, n_old, sum_new, n_new, [](float v) { return sqrtf(v); });
+}
+
+// The adaptive maps' allocation: count[px] uint32, err[px] float, the active
+// count (one word, padded to 4), then the flags, px bytes.
+static size_t adapt_bytes(size_t px) { return (2 * px + 4) * sizeof(uint32_t) + px; }
+static rtx::KAdaptive adapt_maps(const rtx_ctx *c) {
+    rtx::KAdaptive a{};
+    a.count = c->d_adapt;
+    a.err = reinterpret_cast<float *>(c->d_adapt + c->adapt_pixels);
+    a.n_active = c->d_adapt + 2 * c->adapt_pixels;
+    a.flags = reinterpret_cast<uint8_t *>(c->d_adapt + 2 * c->adapt_pixels + 4);
+    return a;
+}
+// Whether a call continues the context's chain state (else it starts fresh).
+static bool chain_continues(const rtx_ctx *c, int reset) {
+    const size_t px = (size_t)c->frame.width * c->frame.height;
+    return !reset && c->chain_n != 0 && c->d_chain && c->chain_pixels == px &&
+           std::memcmp(&c->frame, &c->chain_frame, sizeof c->frame) == 0;
+}
+// The argument and state rules the two calls share, decided before any HIP call.
+static int adaptive_check(const rtx_ctx *c, const char *fn, uint32_t samples, float threshold, uint32_t max_samples,
+                          int reset) {
+    char buf[160];
+    auto bad = [&](int code, const char *why) {
+        std::snprintf(buf, sizeof buf, "%s: %s", fn, why);
+        return fail(code, buf);
+    };
+    if (!c) return bad(RTX_ERR_INVALID, "null ctx");
+    if (const char *why = rtx::adaptive_args_error(samples, threshold, max_samples)) return bad(RTX_ERR_INVALID, why);
+    if (!c->have_world) return bad(RTX_ERR_STATE, "no world uploaded");
+    if (!c->have_frame) return bad(RTX_ERR_STATE, "no frame set");
+    if (c->frame.rng_mode == RTX_RNG_PER_SAMPLE) return bad(RTX_ERR_INVALID, "the per-sample RNG has no chain to continue");
+    if (c->depth == 0) return bad(RTX_ERR_INVALID, "depth is 0: nothing to estimate an error from");
+    if (!rtx::cost_map_fits(samples, c->depth)) return bad(RTX_ERR_INVALID, "samples * depth does not fit 32 bits");
+    const uint32_t have = chain_continues(c, reset) ? c->chain_n : 0u;
+    if (samples > 0xffffffffu - have) return bad(RTX_ERR_INVALID, "more than 2^32 - 1 samples in all");
+    return RTX_OK;
+}
+// What a uniform state of `have` samples answers without its maps: every error
+// is +inf (>= any threshold), so only the cap decides.
+static uint32_t uniform_active(size_t px, uint32_t have, uint32_t samples, uint32_t max_samples) {
+    return max_samples == 0u || (uint64_t)have + samples <= max_samples ? (uint32_t)px : 0u;
+}
+// The flags of a call over valid maps and their number (synchronous: the
+// 4-byte count comes back to the host, which sizes the launch by it).
+static int adaptive_mask(rtx_ctx *c, uint32_t samples, float threshold, uint32_t max_samples, rtx::KAdaptive *a) {
+    *a = adapt_maps(c);
+    hipError_t e = rtx::launch_adaptive_mask(*a, c->frame.width, c->frame.height, samples, threshold, max_samples,
+                                             c->stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_adaptive_mask");
+    RTX_HIP(hipMemcpyAsync(&a->active, a->n_active, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    RTX_HIP(hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+
+int rtx_refine_adaptive(rtx_ctx *c, uint32_t samples, float threshold, uint32_t max_samples, int reset,
+                        uint32_t *active) {
+    int rc = adaptive_check(c, "rtx_refine_adaptive", samples, threshold, max_samples, reset);
+    if (rc) return rc;
+    const size_t px = (size_t)c->frame.width * c->frame.height;
+    const bool fresh = !chain_continues(c, reset);
+    const uint32_t have = fresh ? 0u : c->chain_n;
+    rc = set_device(c);
+    if (rc) return rc;
+    if (!c->d_chain || c->chain_pixels != px) {
+        RTX_HIP(hipStreamSynchronize(c->stream));
+        (void)hipFree(c->d_chain);
+        c->d_chain = nullptr;
+        c->chain_pixels = 0;
+        c->chain_n = 0;
+        RTX_HIP(hipMalloc(&c->d_chain, chain_bytes(px)));
+        c->chain_pixels = px;
+    }
+    if (!c->d_adapt || c->adapt_pixels != px) {
+        RTX_HIP(hipStreamSynchronize(c->stream));
+        (void)hipFree(c->d_adapt);
+        c->d_adapt = nullptr;
+        c->adapt_pixels = 0;
+        c->adapt_valid = false;
+        RTX_HIP(hipMalloc(&c->d_adapt, adapt_bytes(px)));
+        c->adapt_pixels = px;
+    }
+    if (fresh || !c->adapt_valid) {  // a uniform state of `have` samples, no estimate yet
+        const rtx::KAdaptive m = adapt_maps(c);
+        RTX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m.count), (int)have, px, c->stream));
+        RTX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m.err), 0x7f800000, px, c->stream));
+        c->adapt_valid = !fresh;  // (a fresh start: only once its launch is enqueued)
+        c->adapt_mixed = false;
+    }
+    rtx::KAdaptive ka;
+    rc = adaptive_mask(c, samples, threshold, max_samples, &ka);
+    if (rc) return rc;
+    if (active) *active = ka.active;
+    if (ka.active == 0) {  // (never a fresh start: its errors are +inf and its counts 0)
+        c->last_keys = RTX_REFINE_KEYS_UNSCHEDULED;
+        return RTX_OK;
+    }
+    // keyed by the cost map wherever it is valid, whatever rtx_refine_set_keys
+    // says and however few samples it covers; else every key is equal
+    const uint32_t s_prev = fresh ? 0u : c->cost_s_prev;
+    c->chain_n = 0;  // until the launch is enqueued
+    c->cost_s_prev = 0;
+    c->adapt_valid = false;
+    RefineArgs a;
+    a.cost_map = cost_map_of(c);
+    a.carry_spp = s_prev;
+    a.chain_in = fresh ? nullptr : c->d_chain;  // NULL: every count is 0, every pixel starts its chain
+    a.chain_out = c->d_chain;
+    a.samples = samples;
+    a.out_n = 0;  // (each pixel divides by its own count)
+    a.adaptive = &ka;
+    rc = render_impl(c, 1, 0, 1, nullptr, nullptr, 0, c->frame.frame_index, &a);
+    if (rc != RTX_OK) return rc;
+    c->chain_n = have + samples;
+    c->chain_frame = c->frame;
+    c->cost_s_prev = rtx::cost_map_after(samples, c->depth);
+    c->last_keys = RTX_REFINE_KEYS_CARRIED;
+    c->adapt_valid = true;
+    if (ka.active != px) c->adapt_mixed = true;
+    return RTX_OK;
+}
+
+int rtx_refine_pending(rtx_ctx *c, uint32_t samples, float threshold, uint32_t max_samples, uint32_t *active) {
+    int rc = adaptive_check(c, "rtx_refine_pending", samples, threshold, max_samples, 0);
+    if (rc) return rc;
+    if (!active) return fail(RTX_ERR_INVALID, "rtx_refine_pending: null active");
+    const size_t px = (size_t)c->frame.width * c->frame.height;
+    const bool fresh = !chain_continues(c, 0);
+    if (fresh || !c->adapt_valid || !c->d_adapt || c->adapt_pixels != px) {
+        *active = uniform_active(px, fresh ? 0u : c->chain_n, samples, max_samples);
+        return RTX_OK;
+    }
+    rc = set_device(c);
+    if (rc) return rc;
+    rtx::KAdaptive ka;
+    rc = adaptive_mask(c, samples, threshold, max_samples, &ka);
+    if (rc) return rc;
+    *active = ka.active;
+    return RTX_OK;
+}
+
+// rtx_refine_counts / rtx_refine_error: map 0 / 1, or a uniform state's value.
+static int adaptive_read(rtx_ctx *c, const char *fn, int which, void *host, size_t bytes) {
+    char buf[96];
+    if (!c || !host) {
+        std::snprintf(buf, sizeof buf, "%s: null argument", fn);
+        return fail(RTX_ERR_INVALID, buf);
+    }
+    if (c->chain_n == 0 || !c->d_chain) {
+        std::snprintf(buf, sizeof buf, "%s: no chain state", fn);
+        return fail(RTX_ERR_STATE, buf);
+    }
+    if (bytes != c->chain_pixels * sizeof(uint32_t)) {
+        std::snprintf(buf, sizeof buf, "%s: bytes != width*height*4", fn);
+        return fail(RTX_ERR_INVALID, buf);
+    }
+    if (!c->adapt_valid || !c->d_adapt || c->adapt_pixels != c->chain_pixels) {
+        const uint32_t v = which == 0 ? c->chain_n : 0x7f800000u;
+        uint32_t *w = static_cast<uint32_t *>(host);
+        for (size_t i = 0; i < c->chain_pixels; ++i) w[i] = v;
+        return RTX_OK;
+    }
+    int rc = set_device(c);
+    if (rc) return rc;
+    RTX_HIP(hipMemcpyAsync(host, c->d_adapt + (size_t)which * c->adapt_pixels, bytes, hipMemcpyDeviceToHost, c->stream));
+    RTX_HIP(hipStreamSynchronize(c->stream));
+    return check_errors(c, fn);
+}
+int rtx_refine_counts(rtx_ctx *c, uint32_t *host, size_t bytes) { return adaptive_read(c, "rtx_refine_counts", 0, host, bytes); }
+int rtx_refine_error(rtx_ctx *c, float *host, size_t bytes) { return adaptive_read(c, "rtx_refine_error", 1, host, bytes); }
 
 int rtx_deinterleave_rows(rtx_ctx *c, const void *d_gathered, uint32_t width, uint32_t height,
                           uint32_t tile_rows, uint32_t nparts, void *d_image) {

@@ -218,6 +218,19 @@ bool RtxCSApp::Refine(uint32_t samples, bool reset) {
     return m_ok;
 }
 
+bool RtxCSApp::RefineAdaptive(uint32_t samples, float threshold, uint32_t max_samples, bool reset, uint32_t *active) {
+    if (!m_ok) return false;
+    if (m_group) {
+        m_error = "RefineAdaptive: one context only (a group does not refine)";
+        return m_ok = false;
+    }
+    if (rtx_refine_adaptive(m_ctx, samples, threshold, max_samples, reset ? 1 : 0, active) != RTX_OK) {
+        m_error = rtx_last_error();
+        m_ok = false;
+    }
+    return m_ok;
+}
+
 bool RtxCSApp::SetRefineKeys(int mode) {
     if (!m_ok) return false;
     if (m_group || !m_ctx) {
@@ -242,6 +255,18 @@ bool RtxCSApp::SaveState(const std::string &path) {
     h.samples = rtx_refined_samples(m_ctx);
     h.world_hash = chain_world_hash(m_count, m_depth, m_spheres.data(), m_mat_types.data(), m_mat_values.data());
     h.frame_hash = chain_frame_hash(m_frame);
+    // the file holds one N for the frame: after adaptive steps (RefineAdaptive)
+    // the per-pixel counts must still be uniform
+    std::vector<uint32_t> counts((size_t)h.width * h.height);
+    if (rtx_refine_counts(m_ctx, counts.data(), counts.size() * sizeof(uint32_t)) != RTX_OK) {
+        m_error = rtx_last_error();
+        return false;
+    }
+    if (*std::min_element(counts.begin(), counts.end()) != *std::max_element(counts.begin(), counts.end())) {
+        m_error = "SaveState: the per-pixel sample counts differ after adaptive steps, and the state file holds one "
+                  "count for the frame (a checkpoint of adaptive state is not supported)";
+        return false;
+    }
     std::vector<float> st(4 * (size_t)h.width * h.height);
     if (rtx_refine_export(m_ctx, st.data(), st.size() * sizeof(float)) != RTX_OK) {
         m_error = rtx_last_error();

@@ -12,6 +12,7 @@
 //           [--split rows|frames]
 //           [--refine S1,S2,...] [--save-state FILE] [--load-state FILE]
 //           [--refine-keys prepass|carried]
+//           [--refine-adaptive S,THRESHOLD[,MAX] --steps K] [--dump-counts FILE]
 // --refine S1,S2,... refines the image along the reference's own RNG chain,
 // one rtx_refine per entry (--spp and --frames are not used): after the last
 // step the image is the plain render's at spp = S1 + S2 + ... (plus a loaded
@@ -24,6 +25,14 @@
 // step's pixel queue by the previous step's measured per-pixel cost instead of
 // a pre-pass per step (rtx_refine_set_keys; the image is the same), and the
 // JSON line carries "refine_keys".
+// --refine-adaptive S,THRESHOLD[,MAX] --steps K refines only the pixels that
+// are still noisy (rtx_refine_adaptive: S samples per step, MAX the per-pixel
+// cap, 0 or absent: none), until nothing is active or K steps have run, and
+// prints each step's active count on stderr; the JSON line carries "active"
+// (per step) and "steps_run". --dump-counts FILE writes the per-pixel sample
+// counts as a PFM (the count in all three channels). --save-state works while
+// the counts are uniform; a checkpoint of a non-uniform state is refused
+// (RtxCSApp::SaveState).
 // --gpus N renders each frame across devices 0..N-1 (rtx_group: interleaved
 // tiles of T rows, default 5, one gather to device 0); --devices names them,
 // and a repeated device (0,0,0) rehearses the same split on one GPU, its
@@ -67,7 +76,8 @@ static void usage() {
                  "               [--gpus N | --devices a,b,c] [--gather auto|rccl|copy] [--tile-rows T]\n"
                  "               [--split rows|frames]\n"
                  "               [--refine S1,S2,...] [--save-state FILE] [--load-state FILE]\n"
-                 "               [--refine-keys prepass|carried]\n");
+                 "               [--refine-keys prepass|carried]\n"
+                 "               [--refine-adaptive S,THRESHOLD[,MAX] --steps K] [--dump-counts FILE]\n");
 }
 
 int main(int argc, char **argv) {
@@ -90,6 +100,10 @@ int main(int argc, char **argv) {
     std::string pfm, ppm, save_state, load_state;
     std::vector<uint32_t> refine;  // --refine: samples per step
     int refine_keys = -1;          // --refine-keys (RTX_REFINE_KEYS_*; -1: not given)
+    uint32_t ad_samples = 0, ad_max = 0;  // --refine-adaptive S,THRESHOLD[,MAX] (S 0: not given)
+    float ad_threshold = 0.0f;
+    int ad_steps = 1;              // --steps
+    std::string dump_counts;       // --dump-counts
     std::vector<int> devices;  // non-empty: a group
     int gather = RTX_GATHER_AUTO;
     bool group_opts = false;   // --gather / --tile-rows given
@@ -131,6 +145,21 @@ int main(int argc, char **argv) {
                 pos = comma + 1;
             }
         }
+        else if (a == "--refine-adaptive") {
+            unsigned long long s = 0, m = 0;
+            float t = 0.0f;
+            char tail = 0;
+            const int got = std::sscanf(next(), "%llu,%f,%llu%c", &s, &t, &m, &tail);
+            if ((got != 2 && got != 3) || s == 0ull || s > 0xffffffffull || m > 0xffffffffull || t != t) {
+                usage();
+                return 2;
+            }
+            ad_samples = (uint32_t)s;
+            ad_threshold = t;
+            ad_max = (uint32_t)m;
+        }
+        else if (a == "--steps") ad_steps = std::atoi(next());
+        else if (a == "--dump-counts") dump_counts = next();
         else if (a == "--refine-keys") {
             const std::string m = next();
             if (m == "prepass") refine_keys = RTX_REFINE_KEYS_PREPASS;
@@ -234,7 +263,16 @@ int main(int argc, char **argv) {
                              "(a group accumulates with --split frames)\n");
         return 2;
     }
-    const bool refining = !refine.empty();
+    const bool adaptive = ad_samples != 0u;
+    if (adaptive && (!refine.empty() || !load_state.empty() || ad_steps < 1)) {
+        std::fprintf(stderr, "rtx_cli: --refine-adaptive takes --steps K >= 1, without --refine and --load-state\n");
+        return 2;
+    }
+    if (!dump_counts.empty() && !adaptive) {
+        std::fprintf(stderr, "rtx_cli: --dump-counts needs --refine-adaptive\n");
+        return 2;
+    }
+    const bool refining = !refine.empty() || adaptive;
     if ((!save_state.empty() || !load_state.empty()) && !refining) {
         std::fprintf(stderr, "rtx_cli: --save-state and --load-state need --refine\n");
         return 2;
@@ -295,6 +333,15 @@ int main(int argc, char **argv) {
     for (size_t k = 0; k < refine.size(); ++k) {
         app.Update();  // the same PerFrame bytes every Update: the chain state is kept
         if (!app.Refine(refine[k], k == 0 && load_state.empty())) break;
+    }
+    std::vector<uint32_t> ad_active;  // --refine-adaptive: pixels traced per step
+    for (int k = 0; adaptive && k < ad_steps; ++k) {
+        app.Update();
+        uint32_t n = 0;
+        if (!app.RefineAdaptive(ad_samples, ad_threshold, ad_max, k == 0, &n)) break;
+        std::fprintf(stderr, "rtx_cli: adaptive step %d: %u active\n", k + 1, n);
+        if (n == 0u) break;  // nothing is noisy any more (or every pixel is at its cap)
+        ad_active.push_back(n);
     }
     for (int k = 0; k < frames && !split_frames && !refining; ++k) {
         app.Update();
@@ -373,6 +420,26 @@ int main(int argc, char **argv) {
         }
         std::string steps;
         for (size_t k = 0; k < refine.size(); ++k) steps += (k ? ", " : "") + std::to_string(refine[k]);
+        for (size_t k = 0; k < ad_active.size(); ++k) steps += (k ? ", " : "") + std::to_string(ad_samples);
+        std::vector<uint32_t> counts;
+        if (adaptive) {
+            counts.resize((size_t)cfg.width * cfg.height);
+            if (rtx_refine_counts(app.context(), counts.data(), counts.size() * sizeof(uint32_t)) != RTX_OK) {
+                std::fprintf(stderr, "rtx_cli: counts failed: %s\n", rtx_last_error());
+                return 1;
+            }
+            std::string act;
+            for (size_t k = 0; k < ad_active.size(); ++k) act += (k ? ", " : "") + std::to_string(ad_active[k]);
+            std::printf("{\"refine_adaptive\": {\"samples\": %u, \"threshold\": %.9g, \"max_samples\": %u, "
+                        "\"steps\": %d, \"steps_run\": %zu, \"active\": [%s]}}\n",
+                        ad_samples, (double)ad_threshold, ad_max, ad_steps, ad_active.size(), act.c_str());
+            if (!dump_counts.empty()) {
+                std::vector<float> img(4 * counts.size());
+                for (size_t i = 0; i < counts.size(); ++i)
+                    img[4 * i] = img[4 * i + 1] = img[4 * i + 2] = img[4 * i + 3] = (float)counts[i];
+                if (!rtx::write_pfm(dump_counts, img.data(), cfg.width, cfg.height)) return 1;
+            }
+        }
         std::printf("{\"width\": %u, \"height\": %u, \"depth\": %u, \"spheres\": %u, \"cbuffers\": %s, "
                     "\"refine\": [%s], \"loaded_samples\": %u, \"refined_samples\": %u, \"wall_s\": %.6f, "
                     "\"kernel_ms\": %.4f, \"msamples_per_s\": %.3f, \"segments\": %llu, \"sphere_tests\": %llu, "

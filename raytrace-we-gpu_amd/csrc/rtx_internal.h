@@ -7,6 +7,7 @@
 
 #include "rtx_grid.h"
 #include "rtx_refine_keys.h"  // kCostBuckets, kCostSpp, kCostSppLarge, kLptMinSpp; the carried key
+#include "rtx_adaptive.h"     // the adaptive rule: a pixel's error estimate, the activity mask
 
 struct rtx_ctx;  // include/rtx.h
 
@@ -191,6 +192,13 @@ struct KParams {
                                    // launch the previous launch's count
     uint32_t carry_spp;            // carried launch: the samples the map's previous counts cover, s_prev; no
                                    // pre-pass ran and `state` is NULL (cost_in = cost_map). 0: not carried
+    // adaptive refine launch (rtx_refine_adaptive): the queue holds the active
+    // pixels only. Appended like the above and read by the kAdapt kernel
+    // instances only (launch_render_adaptive); any other launch leaves them 0.
+    uint32_t qlen;                 // the queue's length, the active pixels: perm[0 .. qlen)
+    uint32_t *count;               // per pixel the samples in its sum: whoever finishes pixel gid reads
+                                   // count[gid] (n_old), divides by n_new = n_old + spp, stores n_new
+    float *err;                    // ... and stores the step's error estimate (rtx_adaptive.h) in err[gid]
 };
 
 // Longest-processing-time-first scheduling for the persistent kernel: a
@@ -250,6 +258,24 @@ constexpr uint32_t kSchedWords = 16;
 constexpr uint32_t kBlock = 256;    // threads per block of the auxiliary kernels (4 waves)
 
 hipError_t launch_render(const KParams &p, const KSchedule &sched, hipStream_t stream);
+// An adaptive refine launch's per-pixel maps (the context's, width * rows each).
+struct KAdaptive {
+    uint8_t *flags;    // k_adaptive_mask: 1 where the call traces the pixel
+    uint32_t *n_active;  // ... and how many it set (one word, device)
+    uint32_t *count;   // KParams::count
+    float *err;        // KParams::err
+    uint32_t active;   // *n_active, read back by the host: the queue's length (> 0)
+};
+// k_adaptive_mask: flags[i] = adaptive_active(err, count, i, ...) and their
+// number in *n_active (zeroed here first).
+hipError_t launch_adaptive_mask(const KAdaptive &a, uint32_t width, uint32_t rows, uint32_t samples, float threshold,
+                                uint32_t max_samples, hipStream_t stream);
+// The scheduled render over the a.active flagged pixels: a carried-style
+// launch (no pre-pass, no resume state; keys from sched.cost_map when
+// sched.carry_spp != 0, else all equal), sized like a row part of a.active
+// pixels. p: a whole-frame refine launch's parameters (chain_out set, the
+// chain RNG, spp and depth > 0).
+hipError_t launch_render_adaptive(const KParams &p, const KSchedule &sched, const KAdaptive &a, hipStream_t stream);
 // Floats of k_render_ps scratch a launch with these parameters needs (0 when
 // it takes another kernel).
 size_t ps_scratch_floats(const KParams &p);

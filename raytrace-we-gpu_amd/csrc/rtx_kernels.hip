@@ -1697,9 +1697,12 @@ __device__ __forceinline__ void begin_sample(const KParams &P, const Frame &F, u
 // coalesced stores; ~0u (or no staging): straight to out[gid].
 // kRefine (the refine launch's kernel instances, KParams::chain_in): the
 // divisor is the chain's samples so far (out_n), not this launch's.
-template <bool kRefine = false>
-__device__ __forceinline__ void output_pixel(const KParams &P, uint32_t gid, f3 sum, uint32_t slot = ~0u) {
-    float n = (float)(kRefine ? P.out_n : P.spp);
+// kAdapt (the adaptive refine launch's instances): the pixel's own count
+// after the launch, n_new.
+template <bool kRefine = false, bool kAdapt = false>
+__device__ __forceinline__ void output_pixel(const KParams &P, uint32_t gid, f3 sum, uint32_t slot = ~0u,
+                                             uint32_t n_new = 0u) {
+    float n = (float)(kAdapt ? n_new : kRefine ? P.out_n : P.spp);
     if (P.accum) {  // progressive: running linear sum over frames
         float4 a = P.accum[gid];
         a.x = a.x + sum.x;
@@ -1726,8 +1729,26 @@ __device__ __forceinline__ void output_pixel(const KParams &P, uint32_t gid, f3 
 #define RTX_EXTRA_BYTES 0
 #endif
 // A pixel's output (output_pixel), or the scheduling pre-pass's record of it.
-template <bool kCost = false, bool kRefine = false>
+// kAdapt (an adaptive refine launch: rtx_adaptive.h): the pixel's count and
+// its old sum are read here, at the finish, so the lane carries no state for
+// them. Its chain slot still holds the previous launch's sum (written only by
+// whoever finishes the pixel, and that is this lane, below); a fresh state's
+// slot holds anything, and n_old == 0 reads none of it.
+template <bool kCost = false, bool kRefine = false, bool kAdapt = false>
 __device__ __forceinline__ void write_pixel(const KParams &P, const Lane &L) {
+    if constexpr (kAdapt) {
+        const float4 old = P.chain_out[L.gid];
+        const uint32_t n_old = P.count[L.gid];
+        const uint32_t n_new = n_old + P.spp;
+        const float so[3] = {old.x, old.y, old.z}, sn[3] = {L.acc.x, L.acc.y, L.acc.z};
+        const float e = adaptive_error_with(so, n_old, sn, n_new, [](float v) { return sqrt_rn(v); });
+        output_pixel<true, true>(P, L.gid, L.acc, L.slot, n_new);
+        P.chain_out[L.gid] = make_float4(L.acc.x, L.acc.y, L.acc.z, L.seed);
+        P.count[L.gid] = n_new;
+        P.err[L.gid] = e;
+        P.cost_map[L.gid] = launch_segs(P, L);
+        return;
+    }
     if constexpr (kCost) {  // scheduling pre-pass: record the pixel's segments
         P.cost_out[L.gid] = L.segs - L.seg0;
         // (a refine launch's pre-pass: also into the cost map, where the render
@@ -1966,7 +1987,7 @@ __device__ __forceinline__ bool promote(const KParams &P, const Lane &L, uint32_
 // pixel at a sample boundary if it is projected to need more segments than
 // this (KParams::prom_min once the wave's queue is exhausted). Returns true
 // when the pixel was promoted.
-template <bool kCost = false, bool kRefine = false>
+template <bool kCost = false, bool kRefine = false, bool kAdapt = false>
 __device__ __forceinline__ bool shade(const KParams &P, const Frame &F, Lane &L, int hit, float t,
                                       uint32_t prom_thr = 0u) {
     L.segs++;
@@ -1977,7 +1998,7 @@ __device__ __forceinline__ bool shade(const KParams &P, const Frame &F, Lane &L,
     if (ended) {
         L.sample++;
         if (L.sample >= P.spp) {
-            write_pixel<kCost, kRefine>(P, L);
+            write_pixel<kCost, kRefine, kAdapt>(P, L);
             L.active = false;
             diag_pixel_end(P, L.gid);
         } else if (!kCost && prom_thr != 0u && promote<kRefine>(P, L, prom_thr)) {
@@ -2608,8 +2629,14 @@ __device__ __forceinline__ uint32_t tile_pixel(uint32_t j, uint32_t width, uint3
 #endif
 constexpr uint32_t kExactTile = RTX_EXACT_TILE;
 
-template <bool kPersist, bool kCost = false, bool kPF = false, bool kLin = false, bool kRefine = false>
+// kAdapt (with kPersist and kRefine): an adaptive refine launch's instance —
+// the queue holds the qlen active pixels only (KParams::qlen), write_pixel
+// keeps the per-pixel count and error. npix stays the image's pixel count (the
+// torn-entry guards).
+template <bool kPersist, bool kCost = false, bool kPF = false, bool kLin = false, bool kRefine = false,
+          bool kAdapt = false>
 __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
+    static_assert(!kAdapt || (kPersist && kRefine && !kCost), "adaptive: the persistent refine render only");
     constexpr bool kCulled = kPF && RTX_CULL && !kLin;  // the culled scan (large scenes, not the linear mode)
     // dynamic LDS: [candidate list, list_bytes<kPF>][coop rays, kCoopBytes][coop LDS copy of the spheres]
     extern __shared__ __attribute__((aligned(16))) unsigned char s_mem[];
@@ -2639,6 +2666,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
     const int last = (int)P.scene.n - 1;
     const Frame F = load_frame(P);
     const uint32_t npix = P.rows_local * P.width;
+    const uint32_t qlen = kAdapt ? P.qlen : npix;  // the queue's length
     const unsigned long long t_start = P.wave_times ? __builtin_amdgcn_s_memrealtime() : 0ull;
     Lane L;
     L.active = false;
@@ -2652,7 +2680,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
     }
     // heavy slots [0, kh) of the queue (k_heavy_split; tier 1 = [0, k1)), normal slots [kh, npix)
     HeavyState H;
-    H.kh = (kPersist && P.heavy) ? min(P.heavy[1], npix) : 0u;
+    H.kh = (kPersist && P.heavy) ? min(P.heavy[1], qlen) : 0u;
     H.k1 = (kPersist && P.heavy) ? min(P.heavy[3], H.kh) : 0u;
     H.t1_done = H.k1 == 0u || P.trace_ext != 0u;  // tier 1: k_trace when it runs beside this kernel
     H.t2_done = H.k1 == H.kh;
@@ -2661,7 +2689,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
     // the mean pixel's segments (dynamic priority's unit)
     const float dyn_m = (kPersist && P.cost_in && P.heavy) ? __uint_as_float(P.heavy[5]) : 0.0f;
     // promotion's exit count: the pixels this kernel owns (tier 1 is k_trace's when it runs beside it)
-    const uint32_t owned = npix - (P.trace_ext != 0u ? H.k1 : 0u);
+    const uint32_t owned = qlen - (P.trace_ext != 0u ? H.k1 : 0u);
     uint32_t written = 0;  // pixels this wave wrote since it last reported
     unsigned long long last_beat = 0;  // the wave's last heartbeat (beat)
     Diag D;
@@ -2670,7 +2698,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
         if (!(H.t1_done && H.t2_done) && (H.tier != 0u || __ballot(L.active) == 0ull)) take_heavy<kRefine>(P, F, H, L);
         if (H.tier != 0u && __ballot(L.active) == 0ull) H.tier = 0;  // drained, no heavy slot left
         const bool heavy = H.tier != 0u;
-        if (!heavy && !exhausted) exhausted = refill<kRefine>(P, F, kh, npix, L);
+        if (!heavy && !exhausted) exhausted = refill<kRefine>(P, F, kh, qlen, L);
         if (kPersist && kCost && P.pre_done && exhausted && pre_stop(P, npix, L)) continue;
         const uint64_t act = __ballot(L.active);
         D.section(0);
@@ -2726,7 +2754,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
                 // the tail's pixels may be promoted (tier-1 waves already
                 // trace one ray with every lane; promoting tier-2 pixels
                 // measured 1-6 ms slower at R = 2, 4, 8: profiles/R3r_*)
-                promoted = shade<kCost, kRefine>(P, F, L, min(my_hit, last), my_best,
+                promoted = shade<kCost, kRefine, kAdapt>(P, F, L, min(my_hit, last), my_best,
                                         prom_on && exhausted && H.tier == 0u ? P.prom_min : 0u);
             }
             if (prom_on)
@@ -2752,7 +2780,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
                 float best = __uint_as_float(0x7f800000u);
                 const int hit = hit_world_culled(P.scene, L.o, L.d, L.a, L.inv_a, kTMin, best, list);
                 D.section(1);
-                promoted = shade<kCost, kRefine>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
+                promoted = shade<kCost, kRefine, kAdapt>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
             }
         } else if ((RTX_PF_LDS || RTX_PF_RING) && kPF) {  // every lane of the wave fills the scan's LDS tile
             float best = __uint_as_float(0x7f800000u);
@@ -2760,7 +2788,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
             const int hit = hit_world_pre_ld<kPF, decltype(ldc), true>(P.scene, ldc, L.o, L.d, L.a, L.inv_a, kTMin,
                                                                        best, list, nullptr, 0, pf_tile, L.active);
             D.section(1);
-            if (L.active) promoted = shade<kCost, kRefine>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
+            if (L.active) promoted = shade<kCost, kRefine, kAdapt>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
         } else if (L.active) {
             float best = __uint_as_float(0x7f800000u);
             // scenes that fit the coop's LDS copy resolve their candidates
@@ -2771,7 +2799,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
                                                         RTX_SCAN_LDS ? sl.pr : nullptr)
                                 : hit_world_pre<kPF>(P.scene, L.o, L.d, L.a, L.inv_a, kTMin, best, list, pack);
             D.section(1);
-            promoted = shade<kCost, kRefine>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
+            promoted = shade<kCost, kRefine, kAdapt>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
         }
         D.section(2);
         if (prom_on)  // pixels written this iteration (promoted ones are counted by whoever finishes them)
@@ -2902,14 +2930,15 @@ __device__ __forceinline__ int take_promoted_groups(const KParams &P, const Fram
 // copy, took LDS the render's blocks needed: at R = 8 (7 k_trace waves per
 // CU) only ~79 % of k_render's lanes were resident (profiles/R6r_pixel_timelines.jsonl).
 constexpr uint32_t kTraceThreads = 256;
-template <bool kRefine = false>
+template <bool kRefine = false, bool kAdapt = false>
 __global__ void __launch_bounds__(kTraceThreads, 4) k_trace(const KParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_mem[];
     const SphLds sl = lds_copy(P.scene, reinterpret_cast<float *>(s_mem), true, kTraceThreads);
     __syncthreads();
     const Frame F = load_frame(P);
     const uint32_t npix = P.rows_local * P.width;
-    const uint32_t k1 = min(P.heavy[3], min(P.heavy[1], npix));
+    const uint32_t qlen = kAdapt ? P.qlen : npix;  // the queue's length (adaptive: the active pixels)
+    const uint32_t k1 = min(P.heavy[3], min(P.heavy[1], qlen));
     const uint32_t k0 = min(P.heavy[4], k1);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t lg_many = min(max(P.trace_lg, 3u), 6u);
@@ -2955,7 +2984,7 @@ __global__ void __launch_bounds__(kTraceThreads, 4) k_trace(const KParams P) {
             const uint64_t need = __ballot(!W.active && (lane & (g - 1u)) == 0u);
             if (need != 0ull) {
                 set_prio(P.prio_t1);
-                if (take_promoted_groups<kRefine>(P, F, npix, npix - k1, need, lg, act == 0ull, W) < 0) serve_done = true;
+                if (take_promoted_groups<kRefine>(P, F, npix, qlen - k1, need, lg, act == 0ull, W) < 0) serve_done = true;
                 set_prio(P.prio_t1);
                 act = __ballot(W.active);
             }
@@ -2998,7 +3027,7 @@ __global__ void __launch_bounds__(kTraceThreads, 4) k_trace(const KParams P) {
         }
         if (ended) {
             if (first) {
-                write_pixel<false, kRefine>(P, W);
+                write_pixel<false, kRefine, kAdapt>(P, W);
                 diag_pixel_end(P, W.gid);
                 if (W.slot == ~0u)  // a promoted pixel: k_render's exit count
                     __hip_atomic_fetch_add(&P.prom[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -3158,6 +3187,77 @@ __global__ void __launch_bounds__(kBlock) k_carried_scatter(const uint32_t *map,
             perm[g] = i;
             if (inv) inv[i] = g;
         }
+    }
+}
+
+// ---- adaptive refine launch (rtx_adaptive.h) ------------------------------
+// The activity flags of a call (samples, threshold, max_samples) from the
+// per-pixel maps, and their number: one atomic per wave that has any.
+__global__ void __launch_bounds__(kBlock) k_adaptive_mask(const float *__restrict__ err,
+                                                          const uint32_t *__restrict__ count, uint32_t width,
+                                                          uint32_t rows, uint32_t samples, float threshold,
+                                                          uint32_t max_samples, uint8_t *__restrict__ flags,
+                                                          uint32_t *__restrict__ n_active) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const bool on = i < width * rows && adaptive_active(err, count, i, width, rows, samples, threshold, max_samples);
+    if (i < width * rows) flags[i] = on ? 1u : 0u;
+    const uint64_t b = __ballot(on);
+    if (b != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(n_active, (uint32_t)__popcll(b));
+}
+// k_carried_hist's and k_carried_scatter's siblings for an adaptive launch:
+// only flagged pixels are keyed and placed, so perm has as many entries as
+// there are flags and inv marks an unflagged pixel as having no slot (~0u).
+// s_prev 0: no valid cost map, every key is equal (the last bucket: no pixel
+// is heavy, k_heavy_split).
+__global__ void __launch_bounds__(kBlock) k_adaptive_hist(const uint32_t *map, const uint8_t *flags, uint32_t width,
+                                                          uint32_t rows, uint32_t s_prev, uint32_t tile,
+                                                          uint32_t tile_y, uint32_t *counts) {
+    __shared__ uint32_t h[kCostBuckets];
+    for (uint32_t b = threadIdx.x; b < kCostBuckets; b += kBlock) h[b] = 0;
+    __syncthreads();
+    const uint32_t base = blockIdx.x * kBlock * kSortPerThread;
+    for (uint32_t k = 0; k < kSortPerThread; ++k) {
+        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile, tile_y);
+        if (i != ~0u && flags[i] != 0u)
+            atomicAdd(&h[s_prev != 0u ? carried_key(map, i, width, rows, s_prev) : kCostBuckets - 1u], 1u);
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < kCostBuckets; b += kBlock)
+        if (h[b]) atomicAdd(&counts[b], h[b]);
+}
+__global__ void __launch_bounds__(kBlock) k_adaptive_scatter(const uint32_t *map, const uint8_t *flags, uint32_t width,
+                                                             uint32_t rows, uint32_t s_prev, uint32_t tile,
+                                                             uint32_t tile_y, const uint32_t *counts,
+                                                             uint32_t *cursors, uint32_t *perm, uint32_t *inv) {
+    __shared__ uint32_t h[kCostBuckets], start[kCostBuckets];
+    for (uint32_t b = threadIdx.x; b < kCostBuckets; b += kBlock) h[b] = 0;
+    __syncthreads();
+    const uint32_t base = blockIdx.x * kBlock * kSortPerThread;
+    uint32_t rank[kSortPerThread], key[kSortPerThread];
+    for (uint32_t k = 0; k < kSortPerThread; ++k) {
+        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile, tile_y);
+        const bool on = i != ~0u && flags[i] != 0u;
+        key[k] = !on ? ~0u : s_prev != 0u ? carried_key(map, i, width, rows, s_prev) : kCostBuckets - 1u;
+        rank[k] = on ? atomicAdd(&h[key[k]], 1u) : 0u;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t pre = 0;
+        for (uint32_t b = 0; b < kCostBuckets; ++b) {
+            start[b] = pre;
+            pre += counts[b];
+        }
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < kCostBuckets; b += kBlock)
+        if (h[b]) start[b] += atomicAdd(&cursors[b], h[b]);
+    __syncthreads();
+    for (uint32_t k = 0; k < kSortPerThread; ++k) {
+        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile, tile_y);
+        if (i == ~0u) continue;
+        const uint32_t g = key[k] != ~0u ? start[key[k]] + rank[k] : ~0u;
+        if (g != ~0u) perm[g] = i;
+        if (inv) inv[i] = g;
     }
 }
 
@@ -3555,6 +3655,18 @@ __global__ void __launch_bounds__(kBlock) k_unpermute(const float4 *__restrict__
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= npix) return;
     const float4 v = stage[inv[i]];
+    if (__float_as_uint(v.w) == tag) out[i] = make_float4(v.x, v.y, v.z, 1.0f);
+}
+// ... after an adaptive launch: a pixel without a slot (inv ~0u: inactive)
+// keeps its framebuffer value.
+__global__ void __launch_bounds__(kBlock) k_unpermute_adaptive(const float4 *__restrict__ stage,
+                                                               const uint32_t *__restrict__ inv, uint32_t npix,
+                                                               uint32_t tag, float4 *__restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= npix) return;
+    const uint32_t g = inv[i];
+    if (g == ~0u) return;
+    const float4 v = stage[g];
     if (__float_as_uint(v.w) == tag) out[i] = make_float4(v.x, v.y, v.z, 1.0f);
 }
 
@@ -4071,6 +4183,135 @@ hipError_t launch_render(const KParams &p_in, const KSchedule &sched, hipStream_
     if (e == hipSuccess && sched.stage) {
         hipLaunchKernelGGL(k_unpermute, dim3(ceil_div(lanes, kBlock)), dim3(kBlock), 0, stream, sched.stage, sched.inv,
                            (uint32_t)lanes, q.stage_tag, p.out);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
+// ---- adaptive refine launch ------------------------------------------------
+hipError_t launch_adaptive_mask(const KAdaptive &a, uint32_t width, uint32_t rows, uint32_t samples, float threshold,
+                                uint32_t max_samples, hipStream_t stream) {
+    const uint64_t npix = (uint64_t)width * rows;
+    hipError_t e = hipMemsetAsync(a.n_active, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess || npix == 0) return e;
+    hipLaunchKernelGGL(k_adaptive_mask, dim3(ceil_div(npix, kBlock)), dim3(kBlock), 0, stream, a.err, a.count, width,
+                       rows, samples, threshold, max_samples, a.flags, a.n_active);
+    return hipGetLastError();
+}
+
+// the adaptive instance of the persistent refine render, by scene class
+static const void *adaptive_fn(const KScene &s) {
+    return !use_pf(s)   ? (const void *)k_render<true, false, false, false, true, true>
+           : use_lin(s) ? (const void *)k_render<true, false, true, true, true, true>
+                        : (const void *)k_render<true, false, true, false, true, true>;
+}
+
+// launch_render's steps 2 and 3 for a carried launch, over the flagged pixels:
+// every size class (share, blocks, k_trace's fraction, the promotion
+// threshold, k_heavy_split's npix, the queue tiles) is that of a row part of
+// a.active pixels; the sort enumerates the whole image and drops the rest.
+hipError_t launch_render_adaptive(const KParams &p_in, const KSchedule &sched, const KAdaptive &a, hipStream_t stream) {
+    const KTune &tune = sched.tune;
+    KParams p = p_in;
+    const uint64_t image = (uint64_t)p.rows_local * p.width;
+    const uint64_t lanes = a.active;
+    if (lanes == 0 || lanes > image || p.spp == 0 || p.depth == 0 || p.rng_mode == 1u || !p.chain_out || p.accum ||
+        !sched.cost_map || !sched.cost || !sched.stage || !a.flags || !a.count || !a.err)
+        return hipErrorInvalidValue;
+    if (sched.nbuckets != kCostBuckets || sched.npix < image) return hipErrorInvalidValue;
+    p.coop_max = min(max(p.scene.n <= kCoopLds ? tune.coop_max : tune.coop_max_large, 1u), 64u);
+    p.prio_t1 = tune.prio_t1;
+    p.prio_t2 = tune.prio_t2;
+    p.prio_hot = tune.prio_hot;
+    p.cost_map = sched.cost_map;
+    const bool pf = use_pf(p.scene);
+    const size_t lds = render_lds(p.scene);
+    const void *fn = adaptive_fn(p.scene);
+    hipError_t e = allow_lds(fn, lds);
+    if (e == hipSuccess) e = hipMemsetAsync(sched.buckets, 0, (2 * kCostBuckets + kSchedWords) * sizeof(uint32_t), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(p.queue, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    const uint32_t need = ceil_div(lanes, kRB);
+    const uint32_t rb = resident_blocks(fn, lds);
+    const uint32_t qtile = RTX_QUEUE_TILE_ALL || (double)lanes >= tune.rho * (double)min(need, rb) * kRB ? kQueueTile : 0u;
+    const uint32_t sblocks = ceil_div(tile_span(p.width, p.rows_local, qtile), kBlock * kSortPerThread);
+    hipLaunchKernelGGL(k_adaptive_hist, dim3(sblocks), dim3(kBlock), 0, stream, sched.cost_map, a.flags, p.width,
+                       p.rows_local, sched.carry_spp, qtile, 0u, sched.buckets);
+    uint32_t blocks = min(need, rb);
+    const double ppl0 = (double)lanes / ((double)blocks * kRB);
+    {
+        const double occ = ppl0 < tune.rho ? tune.occ_small : ppl0 < tune.rho_low ? tune.occ_low : tune.occ_normal;
+        blocks = max(1u, (uint32_t)(blocks * occ + 0.5));
+    }
+    uint32_t *heavy = sched.buckets + 2 * kCostBuckets;
+    hipLaunchKernelGGL(k_heavy_split, dim3(1), dim3(64), 0, stream, sched.buckets, (uint32_t)lanes, blocks * kRB, p.spp,
+                       heavy, tune);
+    hipLaunchKernelGGL(k_adaptive_scatter, dim3(sblocks), dim3(kBlock), 0, stream, sched.cost_map, a.flags, p.width,
+                       p.rows_local, sched.carry_spp, qtile, 0u, sched.buckets, sched.buckets + kCostBuckets, sched.perm,
+                       sched.inv);
+    KParams q = p;
+    q.qlen = (uint32_t)lanes;
+    q.count = a.count;
+    q.err = a.err;
+    q.cost_spp = 0u;
+    q.perm = sched.perm;
+    q.out_slot = sched.stage;
+    q.stage_tag = sched.epoch;
+    q.state = nullptr;  // no pre-pass ran: every pixel starts in start_pixel's fresh branch, from chain_in
+    q.carry_spp = sched.carry_spp;
+    q.prio_slots = (uint32_t)((double)blocks * kRB * tune.prio_frac);
+    q.heavy = heavy;
+    if (tune.dyn1 > 0.0 && sched.carry_spp != 0u) {  // (no valid map: no rate to seed the dynamic priority with)
+        q.cost_in = sched.cost_map;
+        q.dyn_bar[0] = (float)tune.dyn1;
+        q.dyn_bar[1] = (float)tune.dyn2;
+        q.dyn_bar[2] = (float)tune.dyn3;
+    }
+    const double ppl = (double)lanes / ((double)blocks * kRB);
+    q.chunk = (!pf && ppl >= tune.rho2) ? min(tune.chunk, 4096u) : ppl >= tune.rho_low ? min(tune.chunk, kChunkShare) : 0u;
+    uint32_t trace_waves = 0;
+    if (sched.aux && !pf && p.scene.n <= kCoopLds) {
+        const double frac = ppl < tune.rho ? tune.trace_small : ppl < tune.rho_low ? tune.trace_low
+                            : ppl < tune.rho2 ? tune.trace_medium : tune.trace_large;
+        trace_waves = (uint32_t)(frac * blocks * (kRB / 64) + 0.5);
+    }
+    {
+        const double pm = p.scene.n > kCoopLds ? tune.prom_big
+                          : ppl < tune.rho     ? tune.prom_small : ppl < tune.rho_low ? tune.prom_low
+                          : ppl < tune.rho2    ? tune.prom_medium : tune.prom_large;
+        if (pm > 0.0 && sched.prom_q && sched.prom_cap > 0) {
+            q.prom = sched.buckets + 2 * kCostBuckets + 8;
+            q.prom_q = sched.prom_q;
+            q.prom_cap = sched.prom_cap;
+            q.prom_min = (uint32_t)std::min<double>(pm, 4e9);
+            q.epoch = sched.epoch;
+        }
+    }
+    if (trace_waves > 0) {
+        q.trace_ext = 1u;
+        q.trace_lg = 6u - (uint32_t)__builtin_ctz(max(1u, min(tune.trace_group, 64u)));
+        const size_t tlds = coop_lds_bytes(p.scene.n);
+        e = hipEventRecord(sched.ev_fork, stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(sched.aux, sched.ev_fork, 0);
+        if (e != hipSuccess) return e;
+        const dim3 tgrid((trace_waves + kTraceThreads / 64u - 1u) / (kTraceThreads / 64u));
+        hipLaunchKernelGGL((k_trace<true, true>), tgrid, dim3(kTraceThreads), tlds, sched.aux, q);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(sched.ev_join, sched.aux);
+        if (e != hipSuccess) return e;
+        blocks = max(1u, blocks - (trace_waves + 3u) / 4u);
+    }
+    if (!pf)
+        hipLaunchKernelGGL((k_render<true, false, false, false, true, true>), dim3(blocks), dim3(kRB), lds, stream, q);
+    else if (use_lin(p.scene))
+        hipLaunchKernelGGL((k_render<true, false, true, true, true, true>), dim3(blocks), dim3(kRB), lds, stream, q);
+    else
+        hipLaunchKernelGGL((k_render<true, false, true, false, true, true>), dim3(blocks), dim3(kRB), lds, stream, q);
+    e = hipGetLastError();
+    if (e == hipSuccess && trace_waves > 0) e = hipStreamWaitEvent(stream, sched.ev_join, 0);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_unpermute_adaptive, dim3(ceil_div(image, kBlock)), dim3(kBlock), 0, stream, sched.stage,
+                           sched.inv, (uint32_t)image, q.stage_tag, p.out);
         e = hipGetLastError();
     }
     return e;

@@ -141,6 +141,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_refine_set_keys": (C.c_int, [ctx, C.c_int]),
         "rtx_refine_last_keys": (C.c_int, [ctx]),
         "rtx_refine_cost": (C.c_int, [ctx, C.POINTER(u32), C.c_size_t, C.POINTER(u32)]),
+        "rtx_adaptive_error": (C.c_float, [f, u32, f, u32]),
+        "rtx_refine_adaptive": (C.c_int, [ctx, u32, C.c_float, u32, C.c_int, C.POINTER(u32)]),
+        "rtx_refine_pending": (C.c_int, [ctx, u32, C.c_float, u32, C.POINTER(u32)]),
+        "rtx_refine_counts": (C.c_int, [ctx, C.POINTER(u32), C.c_size_t]),
+        "rtx_refine_error": (C.c_int, [ctx, f, C.c_size_t]),
         "rtx_camera_set_aperture": (C.c_int, [C.POINTER(rtx_frame), C.c_float]),
         "rtx_part_rows": (u32, [u32, u32, u32, u32]),
         "rtx_deinterleave_rows": (C.c_int, [ctx, vp, u32, u32, u32, u32, vp]),
@@ -196,6 +201,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     optional |= {n for n in sig if n.startswith("rtx_group_")}  # arrived without a version bump
     optional |= {"rtx_render_sum", "rtx_fold_frames"}            # ... with rtx_group_accumulate
     optional |= {n for n in sig if n.startswith("rtx_refine")}   # ... probe "rtx_refine"
+    optional |= {"rtx_adaptive_error"}                           # ... with rtx_refine_adaptive
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -353,6 +359,15 @@ def device_count() -> int:
     return n.value if rc == RTX_OK else 0
 
 
+def adaptive_error(sum_old, n_old: int, sum_new, n_new: int, lib: Optional[C.CDLL] = None) -> float:
+    """The error estimate E of a step that took a pixel from n_old to n_new
+    samples, from its linear sums (x, y, z) before and after: the kernels' own
+    fp32 arithmetic on the host, no GPU (rtx_adaptive_error)."""
+    a = np.ascontiguousarray(sum_old, np.float32).reshape(3)
+    b = np.ascontiguousarray(sum_new, np.float32).reshape(3)
+    return float((lib or load_library()).rtx_adaptive_error(_fptr(a), n_old, _fptr(b), n_new))
+
+
 # ---------------------------------------------------------------------------
 # GPU context
 # ---------------------------------------------------------------------------
@@ -490,6 +505,41 @@ class Context:
         _check(self._lib.rtx_refine_cost(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.nbytes, C.byref(n)),
                "rtx_refine_cost", self._lib)
         return out, int(n.value)
+
+    def refine_adaptive(self, samples: int, threshold: float, max_samples: int = 0, reset: bool = False) -> int:
+        """Trace `samples` more samples of every pixel that is still noisy:
+        one whose 3 x 3 neighbourhood holds an error estimate >= threshold and
+        whose count stays within max_samples (0: no cap). Every other pixel
+        keeps its state and its framebuffer value. Returns the number of
+        pixels traced (rtx_refine_adaptive)."""
+        n = C.c_uint32(0)
+        _check(self._lib.rtx_refine_adaptive(self._h, samples, threshold, max_samples, 1 if reset else 0, C.byref(n)),
+               "rtx_refine_adaptive", self._lib)
+        return int(n.value)
+
+    def refine_pending(self, samples: int, threshold: float, max_samples: int = 0) -> int:
+        """The number of pixels refine_adaptive with these arguments would
+        trace now; nothing is traced or changed (rtx_refine_pending)."""
+        n = C.c_uint32(0)
+        _check(self._lib.rtx_refine_pending(self._h, samples, threshold, max_samples, C.byref(n)),
+               "rtx_refine_pending", self._lib)
+        return int(n.value)
+
+    def refine_counts(self) -> np.ndarray:
+        """(H, W) uint32: the samples in every pixel's sum (rtx_refine_counts)."""
+        f = self.frame
+        out = np.empty((f.height, f.width), np.uint32)
+        _check(self._lib.rtx_refine_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.nbytes),
+               "rtx_refine_counts", self._lib)
+        return out
+
+    def refine_error(self) -> np.ndarray:
+        """(H, W) float32: the error estimate of every pixel's last step
+        (+inf: none yet) (rtx_refine_error)."""
+        f = self.frame
+        out = np.empty((f.height, f.width), np.float32)
+        _check(self._lib.rtx_refine_error(self._h, _fptr(out), out.nbytes), "rtx_refine_error", self._lib)
+        return out
 
     def deinterleave(self, d_gathered: int, width: int, height: int, tile_rows: int, nparts: int,
                      d_image: int):
