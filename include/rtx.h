@@ -40,6 +40,12 @@ extern "C" {
 
 #define RTX_VERSION 145 /* 1.4.5 */
 /* ABI notes.
+ *  1.4.5 (later builds, no version bump): rtx_refine_rows,
+ *         rtx_refine_import_rows and rtx_refine_shape (refinement of a row
+ *         part on a context), rtx_group_refine, rtx_group_refined_samples,
+ *         rtx_group_refine_export and rtx_group_refine_import (progressive
+ *         refinement across a group's members, and its checkpoint); purely
+ *         additive again: probe for the symbol (dlsym "rtx_group_refine").
  *  1.4.5 (later builds, no version bump): rtx_refine, rtx_refined_samples,
  *         rtx_refine_state, rtx_refine_export and rtx_refine_import
  *         (progressive samples along the reference's own RNG chain, and its
@@ -405,9 +411,51 @@ RTX_API int rtx_fold_frames(rtx_ctx *ctx, void *d_accum, const void *d_sums, uin
  * spp (frame_index * spp + s), so "continue" has no single meaning there;
  * rtx_accumulate is that mode's progressive form. RTX_ERR_STATE: no world or
  * no frame.
- * Not covered (later changes): row parts and rtx_group (a group-wide refine).
+ * Row parts: rtx_refine_rows below; a group-wide refine: rtx_group_refine.
+ * Not covered (a later change): adaptive refinement across row parts.
  * The pixel queue's order: see rtx_refine_set_keys below. */
 RTX_API int rtx_refine(rtx_ctx *ctx, uint32_t samples, int reset);
+/* rtx_refine for the rows of partition `part` of `nparts` (rtx_render_rows'
+ * partition; later builds, no version bump: probe with dlsym
+ * "rtx_group_refine" or "rtx_refine_rows"). rtx_refine(ctx, s, reset) is
+ * rtx_refine_rows(ctx, 1, 0, 1, s, reset, NULL).
+ * The chain state and the cost map then cover the part's rows only:
+ * rtx_part_rows(...) * width entries in the part's row order (ascending,
+ * contiguous: d_out's order). d_out: device pointer to at least rows * width
+ * float4; it receives toGamma(sum / (float)(N + samples)), w = 1, for those
+ * rows. d_out == NULL is allowed only with nparts == 1 and selects the context
+ * framebuffer, as rtx_refine does. A pixel's seed depends only on its global
+ * position, so the parts of a frame, each refined on its own state, hold the
+ * rows of the one-context image and state bit for bit.
+ * A state has a shape (tile_rows, part, nparts); every shape with nparts == 1
+ * is the same whole-frame shape whatever tile_rows (reported as (1, 0, 1)).
+ * The state restarts at N = 0 under rtx_refine's rules and also when the call's
+ * shape differs from the state's. rtx_refine_export, rtx_refine_cost and
+ * rtx_refine_state serve a state of any shape: their `bytes` must match the
+ * state's own pixel count (rows * width). Carried keys (rtx_refine_set_keys)
+ * work on a part unchanged, the map in part order; the key's 3 x 3 window runs
+ * over the part's local rows, which affects the queue's order only.
+ * Adaptive refinement of a part state is not supported: on a context whose
+ * state has nparts > 1, rtx_refine_adaptive with reset == 0, rtx_refine_pending,
+ * rtx_refine_counts and rtx_refine_error return RTX_ERR_STATE before any GPU
+ * work; rtx_refine_adaptive with reset != 0 starts its whole-frame state.
+ * RTX_ERR_INVALID, before any HIP call: a null ctx, samples == 0,
+ * tile_rows == 0, nparts == 0, part >= nparts, d_out == NULL with nparts > 1,
+ * N + samples above 2^32 - 1, a per-sample-RNG frame. RTX_ERR_STATE: no world
+ * or no frame. A part that owns no rows returns RTX_OK, launches nothing and
+ * leaves the state alone. */
+RTX_API int rtx_refine_rows(rtx_ctx *ctx, uint32_t tile_rows, uint32_t part, uint32_t nparts,
+                            uint32_t samples, int reset, void *d_out);
+/* rtx_refine_import (below) for a part: bytes == rows*width*16, the state in
+ * the part's row order; d_out receives the part's image rows
+ * (toGamma(sum / (float)samples)); NULL with nparts > 1: no image is written,
+ * NULL with nparts == 1: the context framebuffer. Synchronous. */
+RTX_API int rtx_refine_import_rows(rtx_ctx *ctx, uint32_t tile_rows, uint32_t part, uint32_t nparts,
+                                   const float *host_state, size_t bytes, uint32_t samples,
+                                   void *d_out);
+/* The shape of the chain state (NULL outputs are skipped); RTX_ERR_STATE when
+ * there is no state, RTX_ERR_INVALID for a null ctx. */
+RTX_API int rtx_refine_shape(rtx_ctx *ctx, uint32_t *tile_rows, uint32_t *part, uint32_t *nparts);
 /* The cost map and the queue keys of a refine launch (1.4.5, later builds, no
  * version bump: probe with dlsym "rtx_refine_set_keys").
  * Every rtx_refine launch records, per pixel, the ray segments (hit_world
@@ -441,8 +489,10 @@ RTX_API int rtx_refine_set_keys(rtx_ctx *ctx, int mode);
 RTX_API int rtx_refine_last_keys(rtx_ctx *ctx);
 /* The cost map to host memory (synchronous, like rtx_download): width*height
  * uint32 in framebuffer order (row 0 = bottom), and in *samples the samples of
- * the step it covers. bytes == width*height*4. RTX_ERR_STATE if there is no
- * valid map; RTX_ERR_INVALID for a null argument or other bytes. */
+ * the step it covers. bytes == width*height*4; for a part state
+ * (rtx_refine_rows) the part's rows * width * 4, in the part's row order.
+ * RTX_ERR_STATE if there is no valid map; RTX_ERR_INVALID for a null argument
+ * or other bytes. */
 RTX_API int rtx_refine_cost(rtx_ctx *ctx, uint32_t *host_cost, size_t bytes, uint32_t *samples);
 /* N: samples per pixel in the chain state (0 for NULL / none): the sum of the
  * steps since the state began. After adaptive steps (below) that is the count
@@ -517,10 +567,13 @@ RTX_API int rtx_refine_pending(rtx_ctx *ctx, uint32_t samples, float threshold,
  * call has touched yet reads as count N and err +inf. */
 RTX_API int rtx_refine_counts(rtx_ctx *ctx, uint32_t *host_counts, size_t bytes);
 RTX_API int rtx_refine_error(rtx_ctx *ctx, float *host_err, size_t bytes);
-/* Device pointer of the chain state (width*height float4), NULL if none. */
+/* Device pointer of the chain state (width*height float4; a part state: its
+ * rows * width), NULL if none. */
 RTX_API void *rtx_refine_state(rtx_ctx *ctx);
 /* The chain state to host memory (synchronous, like rtx_download):
- * bytes == width*height*16; RTX_ERR_STATE if there is no state. With
+ * bytes == width*height*16 (a part state, rtx_refine_rows: its rows * width *
+ * 16, in the part's row order; rtx_refine_shape names the part);
+ * RTX_ERR_STATE if there is no state. With
  * rtx_refined_samples it is all a later session needs to resume. */
 RTX_API int rtx_refine_export(rtx_ctx *ctx, float *host_state, size_t bytes);
 /* Installs a chain state with N = samples (>= 1) for the current world and
@@ -585,8 +638,9 @@ RTX_API void rtx_group_destroy(rtx_group *g);
 /* Members (0 for NULL). */
 RTX_API uint32_t rtx_group_size(rtx_group *g);
 /* Member's context, borrowed: for its schedule, scan mode (before
- * rtx_group_upload_world) and stats. Its stream, world and frame belong to
- * the group. NULL if out of range. */
+ * rtx_group_upload_world), stats and refine keys (rtx_refine_set_keys: what
+ * orders its rtx_group_refine launches). Its stream, world, frame and chain
+ * state belong to the group. NULL if out of range. */
 RTX_API rtx_ctx *rtx_group_ctx(rtx_group *g, uint32_t member);
 /* The transport in use: RTX_GATHER_RCCL or RTX_GATHER_COPY (AUTO resolved). */
 RTX_API int rtx_group_gather_mode(rtx_group *g);
@@ -608,7 +662,8 @@ RTX_API int rtx_group_sync(rtx_group *g);
 RTX_API void *rtx_group_image(rtx_group *g);
 /* rtx_group_sync, then the image to host memory. */
 RTX_API int rtx_group_download(rtx_group *g, float *host_rgba, size_t bytes);
-/* HIP-event times of the last frame, after rtx_group_sync / _download:
+/* HIP-event times of the last frame (rendered by rtx_group_render or refined
+ * by rtx_group_refine), after rtx_group_sync / _download:
  * render_ms[n] each member's render (0 for a member without rows), the gather
  * and the de-interleave on the root's stream. NULL outputs are skipped.
  * Members sharing a device run one after another: their times add up and say
@@ -653,6 +708,46 @@ RTX_API uint32_t rtx_group_accumulated_frames(rtx_group *g);
  * the gather and the fold on the root's stream. NULL outputs are skipped. */
 RTX_API int rtx_group_get_accumulate_times(rtx_group *g, double *render_ms, double *gather_ms,
                                            double *fold_ms);
+/* Progressive refinement along the reference's RNG chain across the members
+ * (later builds, no version bump: probe with dlsym "rtx_group_refine"). A
+ * pixel's chain is sequential, so frames cannot be dealt to members as
+ * rtx_group_accumulate does; the row split is exact, because the seed depends
+ * only on the global pixel. Each member that owns rows runs
+ * rtx_refine_rows(ctx_i, tile_rows, i, n, samples, fresh, d_out_i) — its chain
+ * state covers its own rows — into the buffers of rtx_group_render, followed
+ * by the same gather and de-interleave (a one-member group with copies refines
+ * straight into the image). Asynchronous like rtx_group_render. After calls
+ * adding s1..sk rtx_group_image is bit for bit (NaN included) what rtx_refine
+ * gives on one context, so what rtx_render gives at spp = s1 + ... + sk.
+ * The group decides freshness itself and passes it to every member: its state
+ * restarts at N = 0 on reset != 0, a first call, a tile_rows other than the
+ * state's, rtx_group_upload_world, and rtx_group_set_frame with other bytes.
+ * Before it launches anything the group checks that every row-owning member's
+ * rtx_refined_samples and rtx_refine_shape agree with its own N and shape: a
+ * mismatch (someone refined through a borrowed rtx_group_ctx) is RTX_ERR_STATE
+ * naming the member. If a member's launch fails after earlier members were
+ * enqueued, N becomes 0 (the next call restarts everyone) and the error
+ * carries the member's index. rtx_group_render and rtx_group_accumulate between
+ * two calls overwrite the image, not the states.
+ * RTX_ERR_INVALID, before any HIP call: a null group, samples == 0,
+ * tile_rows == 0, a per-sample-RNG frame, N + samples above 2^32 - 1.
+ * RTX_ERR_STATE: no frame or no world. */
+RTX_API int rtx_group_refine(rtx_group *g, uint32_t samples, uint32_t tile_rows, int reset);
+/* N of the group's chain state (0 for NULL / none). */
+RTX_API uint32_t rtx_group_refined_samples(rtx_group *g);
+/* The group's chain state as ONE whole-frame state, [height][width] float4 in
+ * framebuffer order, bytes == width*height*16: byte for byte what
+ * rtx_refine_export gives on one context at the same N, so one state (file)
+ * moves between a context and a group of any size and tile_rows. Synchronous.
+ * RTX_ERR_STATE: no state, or a member that disagrees with the group. */
+RTX_API int rtx_group_refine_export(rtx_group *g, float *host_state, size_t bytes);
+/* The inverse: every member receives its rows (rtx_refine_import_rows), its
+ * image rows go into its slot, then the gather and the de-interleave run: the
+ * image is there before anything is traced, and N = samples with this
+ * tile_rows. Synchronous. Errors as rtx_group_refine, and RTX_ERR_INVALID for
+ * a null host_state or other bytes. */
+RTX_API int rtx_group_refine_import(rtx_group *g, uint32_t tile_rows, const float *host_state,
+                                    size_t bytes, uint32_t samples);
 
 /* ---- device buffers (for callers without their own allocator) ----------
  * Ordered on the context stream; copies are synchronous. d_ptr from

@@ -124,22 +124,30 @@ public:
     // The reference's sampleCount loop (DxCSApp.cpp:491-492) as it was meant:
     // `samples` more samples of every pixel along its own RNG chain
     // (rtx_refine), the image then the plain render's at the samples refined
-    // so far. One context only (a group-wide refine is a later change).
+    // so far. With a group every member refines its own rows
+    // (rtx_group_refine, AppConfig::tile_rows) and the image is the same.
     bool Refine(uint32_t samples, bool reset);
+    // Samples refined so far (rtx_refined_samples, or the group's).
+    uint32_t RefinedSamples() const;
     // `samples` more samples of the pixels that are still noisy
     // (rtx_refine_adaptive: an error estimate >= threshold in the pixel's
     // 3 x 3 neighbourhood, and its count within max_samples; 0: no cap);
-    // *active (may be NULL): how many were traced. One context only.
+    // *active (may be NULL): how many were traced. One context only: with a
+    // group it returns false with a message (a pixel's neighbourhood crosses
+    // the members' tile edges).
     bool RefineAdaptive(uint32_t samples, float threshold, uint32_t max_samples, bool reset, uint32_t *active);
     // What orders a scheduled Refine's pixel queue: RTX_REFINE_KEYS_PREPASS (a
     // cost pre-pass per step, the default) or RTX_REFINE_KEYS_CARRIED (the
     // previous step's measured per-pixel cost; rtx_refine_set_keys). The
-    // images are the same. One context only.
+    // images are the same. With a group: every member.
     bool SetRefineKeys(int mode);
     // The chain state as a file (write_chain_state below), tagged with this
     // app's world and frame; LoadState refuses a file of another size, world
     // or frame (last_error() says which) and otherwise imports it
     // (rtx_refine_import): the image is there before anything is traced.
+    // With a group the file is the same one whole-frame state
+    // (rtx_group_refine_export / _import): a file saved by one context loads
+    // into a group of any size and tile_rows, and the other way round.
     bool SaveState(const std::string &path);
     bool LoadState(const std::string &path);
 

@@ -112,8 +112,12 @@ struct rtx_ctx {
     size_t chain_pixels = 0;
     uint32_t chain_n = 0;
     rtx_frame chain_frame{};
+    // ... and the rows it covers (rtx_refine_rows): part chain_part of
+    // chain_nparts in tiles of chain_tile rows, chain_pixels = its rows * width
+    // in the part's row order; the whole frame is (1, 0, 1) whatever tile_rows
+    uint32_t chain_tile = 1, chain_part = 0, chain_nparts = 1;
     // ... and the cost map (rtx_refine_cost): per pixel the segments the last
-    // refine launch spent on it, width*height uint32 behind the chain state in
+    // refine launch spent on it, chain_pixels uint32 behind the chain state in
     // the same allocation (cost_map_of). cost_s_prev: the samples it covers;
     // the map is valid while that and chain_n are nonzero, so it falls with
     // the chain state. refine_keys: rtx_refine_set_keys; last_keys: what the
@@ -1099,33 +1103,65 @@ static int render_impl(rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t n
 int rtx_render(rtx_ctx *c) { return rtx_render_rows(c, 1, 0, 1, nullptr); }
 
 // ---- progressive refinement along the reference's RNG chain ---------------
-int rtx_refine(rtx_ctx *c, uint32_t samples, int reset) {
-    if (!c) return fail(RTX_ERR_INVALID, "rtx_refine: null ctx");
-    if (samples == 0) return fail(RTX_ERR_INVALID, "rtx_refine: samples is 0");
-    if (!c->have_world) return fail(RTX_ERR_STATE, "rtx_refine: no world uploaded");
-    if (!c->have_frame) return fail(RTX_ERR_STATE, "rtx_refine: no frame set");
+// The argument rules rtx_refine_rows and rtx_refine_import_rows share, decided
+// before the context is looked at (and before any HIP call).
+static int refine_rows_args(const char *fn, const rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t nparts,
+                            uint32_t samples) {
+    auto bad = [&](const char *why) { return fail(RTX_ERR_INVALID, std::string(fn) + ": " + why); };
+    if (!c) return bad("null ctx");
+    if (samples == 0) return bad("samples is 0");
+    if (tile_rows == 0 || nparts == 0 || part >= nparts) return bad("bad partition (tile_rows, part, nparts)");
+    return RTX_OK;
+}
+// ... and the state rules, which need the context's world and frame.
+static int refine_rows_state(const char *fn, const rtx_ctx *c) {
+    if (!c->have_world) return fail(RTX_ERR_STATE, std::string(fn) + ": no world uploaded");
+    if (!c->have_frame) return fail(RTX_ERR_STATE, std::string(fn) + ": no frame set");
     if (c->frame.rng_mode == RTX_RNG_PER_SAMPLE)
-        return fail(RTX_ERR_INVALID, "rtx_refine: the per-sample RNG has no chain to continue (rtx_accumulate is its "
-                                     "progressive form)");
-    const size_t px = (size_t)c->frame.width * c->frame.height;
+        return fail(RTX_ERR_INVALID, std::string(fn) + ": the per-sample RNG has no chain to continue (rtx_accumulate "
+                                                       "is its progressive form)");
+    return RTX_OK;
+}
+// The chain state's allocation for px pixels of shape (tile_rows, part, nparts);
+// another size drains the stream and replaces it (N falls to 0).
+static int ensure_chain(rtx_ctx *c, size_t px) {
+    if (c->d_chain && c->chain_pixels == px) return RTX_OK;
+    RTX_HIP(hipStreamSynchronize(c->stream));
+    (void)hipFree(c->d_chain);
+    c->d_chain = nullptr;
+    c->chain_pixels = 0;
+    c->chain_n = 0;
+    RTX_HIP(hipMalloc(&c->d_chain, chain_bytes(px)));
+    c->chain_pixels = px;
+    return RTX_OK;
+}
+static bool chain_shape_is(const rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t nparts) {
+    return c->chain_tile == tile_rows && c->chain_part == part && c->chain_nparts == nparts;
+}
+
+static int refine_rows_impl(const char *fn, rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t nparts,
+                            uint32_t samples, int reset, void *d_out) {
+    int rc = refine_rows_args(fn, c, tile_rows, part, nparts, samples);
+    if (rc) return rc;
+    if (!d_out && nparts > 1) return fail(RTX_ERR_INVALID, std::string(fn) + ": d_out NULL needs nparts == 1");
+    rc = refine_rows_state(fn, c);
+    if (rc) return rc;
+    if (nparts == 1) tile_rows = 1;  // one whole-frame shape, and rtx_refine's launch, whatever tile_rows
+    const uint32_t rows = rtx_part_rows(c->frame.height, tile_rows, part, nparts);
+    if (rows == 0) return RTX_OK;  // a part without rows: nothing to launch, the state stays
+    const size_t px = (size_t)c->frame.width * rows;
     const bool fresh = reset || c->chain_n == 0 || !c->d_chain || c->chain_pixels != px ||
+                       !chain_shape_is(c, tile_rows, part, nparts) ||
                        std::memcmp(&c->frame, &c->chain_frame, sizeof c->frame) != 0;
     const uint32_t have = fresh ? 0u : c->chain_n;
-    if (samples > 0xffffffffu - have) return fail(RTX_ERR_INVALID, "rtx_refine: more than 2^32 - 1 samples in all");
+    if (samples > 0xffffffffu - have) return fail(RTX_ERR_INVALID, std::string(fn) + ": more than 2^32 - 1 samples in all");
     if (!fresh && c->adapt_valid && c->adapt_mixed)
-        return fail(RTX_ERR_STATE, "rtx_refine: the state's per-pixel sample counts differ after adaptive steps: "
-                                   "continue with rtx_refine_adaptive, or reset");
-    int rc = set_device(c);
+        return fail(RTX_ERR_STATE, std::string(fn) + ": the state's per-pixel sample counts differ after adaptive "
+                                                     "steps: continue with rtx_refine_adaptive, or reset");
+    rc = set_device(c);
     if (rc) return rc;
-    if (!c->d_chain || c->chain_pixels != px) {
-        RTX_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_chain);
-        c->d_chain = nullptr;
-        c->chain_pixels = 0;
-        c->chain_n = 0;
-        RTX_HIP(hipMalloc(&c->d_chain, chain_bytes(px)));
-        c->chain_pixels = px;
-    }
+    rc = ensure_chain(c, px);
+    if (rc) return rc;
     // the previous launch's cost map keys this one when the mode asks for it
     // and the map can (rtx_refine_keys.h); a fresh chain has none
     const uint32_t s_prev = fresh || c->chain_n == 0 ? 0u : c->cost_s_prev;
@@ -1133,6 +1169,9 @@ int rtx_refine(rtx_ctx *c, uint32_t samples, int reset) {
     c->chain_n = 0;  // until the launch is enqueued
     c->cost_s_prev = 0;
     c->adapt_valid = c->adapt_mixed = false;  // uniform counts after this launch: the next adaptive call fills its maps
+    c->chain_tile = tile_rows;
+    c->chain_part = part;
+    c->chain_nparts = nparts;
     RefineArgs a;
     a.cost_map = cost_map_of(c);
     a.carry_spp = carried ? s_prev : 0u;
@@ -1146,7 +1185,7 @@ int rtx_refine(rtx_ctx *c, uint32_t samples, int reset) {
         if (fresh) RTX_HIP(hipMemsetAsync(c->d_chain, 0, px * sizeof(float4), c->stream));
         a.chain_in = a.chain_out = nullptr;
     }
-    rc = render_impl(c, 1, 0, 1, nullptr, nullptr, 0, c->frame.frame_index, &a);
+    rc = render_impl(c, tile_rows, part, nparts, d_out, nullptr, 0, c->frame.frame_index, &a);
     if (rc != RTX_OK) return rc;
     c->chain_n = have + samples;
     c->chain_frame = c->frame;
@@ -1156,6 +1195,24 @@ int rtx_refine(rtx_ctx *c, uint32_t samples, int reset) {
     c->last_keys = c->depth == 0 || samples < rtx::kLptMinSpp ? RTX_REFINE_KEYS_UNSCHEDULED
                    : carried                                  ? RTX_REFINE_KEYS_CARRIED
                                                               : RTX_REFINE_KEYS_PREPASS;
+    return RTX_OK;
+}
+
+int rtx_refine(rtx_ctx *c, uint32_t samples, int reset) {
+    return refine_rows_impl("rtx_refine", c, 1, 0, 1, samples, reset, nullptr);
+}
+
+int rtx_refine_rows(rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t nparts, uint32_t samples, int reset,
+                    void *d_out) {
+    return refine_rows_impl("rtx_refine_rows", c, tile_rows, part, nparts, samples, reset, d_out);
+}
+
+int rtx_refine_shape(rtx_ctx *c, uint32_t *tile_rows, uint32_t *part, uint32_t *nparts) {
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_refine_shape: null ctx");
+    if (c->chain_n == 0 || !c->d_chain) return fail(RTX_ERR_STATE, "rtx_refine_shape: no chain state");
+    if (tile_rows) *tile_rows = c->chain_tile;
+    if (part) *part = c->chain_part;
+    if (nparts) *nparts = c->chain_nparts;
     return RTX_OK;
 }
 
@@ -1176,7 +1233,8 @@ int rtx_refine_cost(rtx_ctx *c, uint32_t *host_cost, size_t bytes, uint32_t *sam
     if (!c || !host_cost || !samples) return fail(RTX_ERR_INVALID, "rtx_refine_cost: null argument");
     if (!cost_map_valid(c)) return fail(RTX_ERR_STATE, "rtx_refine_cost: no valid cost map");
     if (bytes != c->chain_pixels * sizeof(uint32_t))
-        return fail(RTX_ERR_INVALID, "rtx_refine_cost: bytes != width*height*4");
+        return fail(RTX_ERR_INVALID, "rtx_refine_cost: bytes != the state's pixels * 4 (width*height, or a part's "
+                                     "rows * width)");
     int rc = set_device(c);
     if (rc) return rc;
     RTX_HIP(hipMemcpyAsync(host_cost, cost_map_of(c), bytes, hipMemcpyDeviceToHost, c->stream));
@@ -1193,7 +1251,8 @@ int rtx_refine_export(rtx_ctx *c, float *host_state, size_t bytes) {
     if (!c || !host_state) return fail(RTX_ERR_INVALID, "rtx_refine_export: null argument");
     if (c->chain_n == 0 || !c->d_chain) return fail(RTX_ERR_STATE, "rtx_refine_export: no chain state");
     if (bytes != c->chain_pixels * sizeof(float4))
-        return fail(RTX_ERR_INVALID, "rtx_refine_export: bytes != width*height*16");
+        return fail(RTX_ERR_INVALID, "rtx_refine_export: bytes != the state's pixels * 16 (width*height, or a part's "
+                                     "rows * width)");
     int rc = set_device(c);
     if (rc) return rc;
     RTX_HIP(hipMemcpyAsync(host_state, c->d_chain, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -1201,43 +1260,61 @@ int rtx_refine_export(rtx_ctx *c, float *host_state, size_t bytes) {
     return check_errors(c, "rtx_refine_export");
 }
 
-int rtx_refine_import(rtx_ctx *c, const float *host_state, size_t bytes, uint32_t samples) {
-    if (!c || !host_state) return fail(RTX_ERR_INVALID, "rtx_refine_import: null argument");
-    if (samples == 0) return fail(RTX_ERR_INVALID, "rtx_refine_import: samples is 0");
-    if (!c->have_world) return fail(RTX_ERR_STATE, "rtx_refine_import: no world uploaded");
-    if (!c->have_frame) return fail(RTX_ERR_STATE, "rtx_refine_import: no frame set");
-    if (c->frame.rng_mode == RTX_RNG_PER_SAMPLE)
-        return fail(RTX_ERR_INVALID, "rtx_refine_import: the per-sample RNG has no chain to continue");
-    const size_t px = (size_t)c->frame.width * c->frame.height;
-    if (bytes != px * sizeof(float4)) return fail(RTX_ERR_INVALID, "rtx_refine_import: bytes != width*height*16");
-    int rc = set_device(c);
+static int refine_import_impl(const char *fn, rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t nparts,
+                              const float *host_state, size_t bytes, uint32_t samples, void *d_out) {
+    int rc = refine_rows_args(fn, c, tile_rows, part, nparts, samples);
     if (rc) return rc;
-    if (!c->d_chain || c->chain_pixels != px || c->fb_pixels != px) RTX_HIP(hipStreamSynchronize(c->stream));
+    rc = refine_rows_state(fn, c);
+    if (rc) return rc;
+    if (nparts == 1) tile_rows = 1;  // the whole-frame shape
+    const uint32_t rows = rtx_part_rows(c->frame.height, tile_rows, part, nparts);
+    const size_t px = (size_t)c->frame.width * rows;
+    if (bytes != px * sizeof(float4))
+        return fail(RTX_ERR_INVALID, std::string(fn) + ": bytes != rows*width*16 (the whole frame: width*height*16)");
+    if (rows == 0) return RTX_OK;  // a part without rows: the state stays
+    if (!host_state) return fail(RTX_ERR_INVALID, std::string(fn) + ": null host_state");
+    rc = set_device(c);
+    if (rc) return rc;
     c->chain_n = 0;
     c->cost_s_prev = 0;  // an installed state has no cost map: the next step takes the pre-pass
     c->adapt_valid = c->adapt_mixed = false;  // ... and is uniform
-    if (!c->d_chain || c->chain_pixels != px) {
-        (void)hipFree(c->d_chain);
-        c->d_chain = nullptr;
-        c->chain_pixels = 0;
-        RTX_HIP(hipMalloc(&c->d_chain, chain_bytes(px)));
-        c->chain_pixels = px;
-    }
-    if (c->fb_pixels != px) {
-        (void)hipFree(c->d_fb);
-        c->d_fb = nullptr;
-        c->fb_pixels = 0;
-        RTX_HIP(hipMalloc(&c->d_fb, px * sizeof(float4)));
-        c->fb_pixels = px;
+    rc = ensure_chain(c, px);
+    if (rc) return rc;
+    float4 *out = reinterpret_cast<float4 *>(d_out);
+    if (!out && nparts == 1) {  // the context framebuffer, as rtx_refine's
+        if (c->fb_pixels != px) {
+            RTX_HIP(hipStreamSynchronize(c->stream));
+            (void)hipFree(c->d_fb);
+            c->d_fb = nullptr;
+            c->fb_pixels = 0;
+            RTX_HIP(hipMalloc(&c->d_fb, px * sizeof(float4)));
+            c->fb_pixels = px;
+        }
+        out = c->d_fb;
     }
     // synchronous, like rtx_copy_to_device: the caller's array is free on return
     RTX_HIP(hipMemcpyAsync(c->d_chain, host_state, bytes, hipMemcpyHostToDevice, c->stream));
-    hipError_t e = rtx::launch_chain_image(c->d_chain, c->d_fb, px, samples, c->stream);
-    if (e != hipSuccess) return hip_fail(e, "launch_chain_image");
+    if (out) {  // (a part without d_out: no image)
+        hipError_t e = rtx::launch_chain_image(c->d_chain, out, px, samples, c->stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_chain_image");
+    }
     RTX_HIP(hipStreamSynchronize(c->stream));
     c->chain_n = samples;
     c->chain_frame = c->frame;
+    c->chain_tile = tile_rows;
+    c->chain_part = part;
+    c->chain_nparts = nparts;
     return RTX_OK;
+}
+
+int rtx_refine_import(rtx_ctx *c, const float *host_state, size_t bytes, uint32_t samples) {
+    if (!c || !host_state) return fail(RTX_ERR_INVALID, "rtx_refine_import: null argument");
+    return refine_import_impl("rtx_refine_import", c, 1, 0, 1, host_state, bytes, samples, nullptr);
+}
+
+int rtx_refine_import_rows(rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t nparts, const float *host_state,
+                           size_t bytes, uint32_t samples, void *d_out) {
+    return refine_import_impl("rtx_refine_import_rows", c, tile_rows, part, nparts, host_state, bytes, samples, d_out);
 }
 
 // ---- adaptive refinement (rtx_adaptive.h) ----------------------------------
@@ -1256,16 +1333,22 @@ static rtx::KAdaptive adapt_maps(const rtx_ctx *c) {
     a.flags = reinterpret_cast<uint8_t *>(c->d_adapt + 2 * c->adapt_pixels + 4);
     return a;
 }
+// A chain state of a row part (rtx_refine_rows with nparts > 1): the adaptive
+// entry points refuse it (a pixel's 3 x 3 neighbourhood crosses tile edges).
+static bool part_state(const rtx_ctx *c) { return c->chain_n != 0 && c->d_chain && c->chain_nparts > 1; }
+static const char *const kPartStateWhy =
+    "the chain state covers a row part (rtx_refine_rows, nparts > 1): adaptive refinement of a part is not "
+    "supported; reset, or refine the whole frame";
 // Whether a call continues the context's chain state (else it starts fresh).
 static bool chain_continues(const rtx_ctx *c, int reset) {
     const size_t px = (size_t)c->frame.width * c->frame.height;
-    return !reset && c->chain_n != 0 && c->d_chain && c->chain_pixels == px &&
+    return !reset && c->chain_n != 0 && c->d_chain && c->chain_pixels == px && c->chain_nparts == 1 &&
            std::memcmp(&c->frame, &c->chain_frame, sizeof c->frame) == 0;
 }
 // The argument and state rules the two calls share, decided before any HIP call.
 static int adaptive_check(const rtx_ctx *c, const char *fn, uint32_t samples, float threshold, uint32_t max_samples,
                           int reset) {
-    char buf[160];
+    char buf[256];
     auto bad = [&](int code, const char *why) {
         std::snprintf(buf, sizeof buf, "%s: %s", fn, why);
         return fail(code, buf);
@@ -1277,6 +1360,7 @@ static int adaptive_check(const rtx_ctx *c, const char *fn, uint32_t samples, fl
     if (c->frame.rng_mode == RTX_RNG_PER_SAMPLE) return bad(RTX_ERR_INVALID, "the per-sample RNG has no chain to continue");
     if (c->depth == 0) return bad(RTX_ERR_INVALID, "depth is 0: nothing to estimate an error from");
     if (!rtx::cost_map_fits(samples, c->depth)) return bad(RTX_ERR_INVALID, "samples * depth does not fit 32 bits");
+    if (!reset && part_state(c)) return bad(RTX_ERR_STATE, kPartStateWhy);
     const uint32_t have = chain_continues(c, reset) ? c->chain_n : 0u;
     if (samples > 0xffffffffu - have) return bad(RTX_ERR_INVALID, "more than 2^32 - 1 samples in all");
     return RTX_OK;
@@ -1307,15 +1391,9 @@ int rtx_refine_adaptive(rtx_ctx *c, uint32_t samples, float threshold, uint32_t 
     const uint32_t have = fresh ? 0u : c->chain_n;
     rc = set_device(c);
     if (rc) return rc;
-    if (!c->d_chain || c->chain_pixels != px) {
-        RTX_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_chain);
-        c->d_chain = nullptr;
-        c->chain_pixels = 0;
-        c->chain_n = 0;
-        RTX_HIP(hipMalloc(&c->d_chain, chain_bytes(px)));
-        c->chain_pixels = px;
-    }
+    rc = ensure_chain(c, px);
+    if (rc) return rc;
+    if (fresh) c->chain_tile = 1, c->chain_part = 0, c->chain_nparts = 1;  // its state is a whole frame's
     if (!c->d_adapt || c->adapt_pixels != px) {
         RTX_HIP(hipStreamSynchronize(c->stream));
         (void)hipFree(c->d_adapt);
@@ -1395,6 +1473,7 @@ static int adaptive_read(rtx_ctx *c, const char *fn, int which, void *host, size
         std::snprintf(buf, sizeof buf, "%s: no chain state", fn);
         return fail(RTX_ERR_STATE, buf);
     }
+    if (part_state(c)) return fail(RTX_ERR_STATE, std::string(fn) + ": " + kPartStateWhy);
     if (bytes != c->chain_pixels * sizeof(uint32_t)) {
         std::snprintf(buf, sizeof buf, "%s: bytes != width*height*4", fn);
         return fail(RTX_ERR_INVALID, buf);

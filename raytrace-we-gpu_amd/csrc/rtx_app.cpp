@@ -207,11 +207,8 @@ bool RtxCSApp::Accumulate(uint32_t frames, bool reset) {
 
 bool RtxCSApp::Refine(uint32_t samples, bool reset) {
     if (!m_ok) return false;
-    if (m_group) {
-        m_error = "Refine: one context only (a group does not refine)";
-        return m_ok = false;
-    }
-    if (rtx_refine(m_ctx, samples, reset ? 1 : 0) != RTX_OK) {
+    if ((m_group ? rtx_group_refine(m_group, samples, m_cfg.tile_rows, reset ? 1 : 0)
+                 : rtx_refine(m_ctx, samples, reset ? 1 : 0)) != RTX_OK) {
         m_error = rtx_last_error();
         m_ok = false;
     }
@@ -221,7 +218,7 @@ bool RtxCSApp::Refine(uint32_t samples, bool reset) {
 bool RtxCSApp::RefineAdaptive(uint32_t samples, float threshold, uint32_t max_samples, bool reset, uint32_t *active) {
     if (!m_ok) return false;
     if (m_group) {
-        m_error = "RefineAdaptive: one context only (a group does not refine)";
+        m_error = "RefineAdaptive: one context only (adaptive refinement across a group's row parts is not supported)";
         return m_ok = false;
     }
     if (rtx_refine_adaptive(m_ctx, samples, threshold, max_samples, reset ? 1 : 0, active) != RTX_OK) {
@@ -233,42 +230,54 @@ bool RtxCSApp::RefineAdaptive(uint32_t samples, float threshold, uint32_t max_sa
 
 bool RtxCSApp::SetRefineKeys(int mode) {
     if (!m_ok) return false;
-    if (m_group || !m_ctx) {
-        m_error = "SetRefineKeys: one context only (a group does not refine)";
+    if (!m_ctx) {
+        m_error = "SetRefineKeys: not initialized";
         return false;
     }
-    if (rtx_refine_set_keys(m_ctx, mode) != RTX_OK) {
-        m_error = rtx_last_error();
-        return false;
+    // with a group: every member's launches
+    const uint32_t members = m_group ? rtx_group_size(m_group) : 1u;
+    for (uint32_t m = 0; m < members; ++m) {
+        if (rtx_refine_set_keys(m_group ? rtx_group_ctx(m_group, m) : m_ctx, mode) != RTX_OK) {
+            m_error = rtx_last_error();
+            return false;
+        }
     }
     return true;
 }
 
+uint32_t RtxCSApp::RefinedSamples() const {
+    return m_group ? rtx_group_refined_samples(m_group) : rtx_refined_samples(m_ctx);
+}
+
 bool RtxCSApp::SaveState(const std::string &path) {
-    if (m_group || !m_ctx) {
-        m_error = "SaveState: one context only";
+    if (!m_ctx) {
+        m_error = "SaveState: not initialized";
         return false;
     }
     ChainStateHeader h;
     h.width = m_frame.width;
     h.height = m_frame.height;
-    h.samples = rtx_refined_samples(m_ctx);
+    h.samples = RefinedSamples();
     h.world_hash = chain_world_hash(m_count, m_depth, m_spheres.data(), m_mat_types.data(), m_mat_values.data());
     h.frame_hash = chain_frame_hash(m_frame);
-    // the file holds one N for the frame: after adaptive steps (RefineAdaptive)
-    // the per-pixel counts must still be uniform
-    std::vector<uint32_t> counts((size_t)h.width * h.height);
-    if (rtx_refine_counts(m_ctx, counts.data(), counts.size() * sizeof(uint32_t)) != RTX_OK) {
-        m_error = rtx_last_error();
-        return false;
+    if (!m_group) {
+        // the file holds one N for the frame: after adaptive steps (RefineAdaptive)
+        // the per-pixel counts must still be uniform (a group takes none)
+        std::vector<uint32_t> counts((size_t)h.width * h.height);
+        if (rtx_refine_counts(m_ctx, counts.data(), counts.size() * sizeof(uint32_t)) != RTX_OK) {
+            m_error = rtx_last_error();
+            return false;
+        }
+        if (*std::min_element(counts.begin(), counts.end()) != *std::max_element(counts.begin(), counts.end())) {
+            m_error = "SaveState: the per-pixel sample counts differ after adaptive steps, and the state file holds "
+                      "one count for the frame (a checkpoint of adaptive state is not supported)";
+            return false;
+        }
     }
-    if (*std::min_element(counts.begin(), counts.end()) != *std::max_element(counts.begin(), counts.end())) {
-        m_error = "SaveState: the per-pixel sample counts differ after adaptive steps, and the state file holds one "
-                  "count for the frame (a checkpoint of adaptive state is not supported)";
-        return false;
-    }
+    // a group's parts come back as the one whole-frame state a context exports
     std::vector<float> st(4 * (size_t)h.width * h.height);
-    if (rtx_refine_export(m_ctx, st.data(), st.size() * sizeof(float)) != RTX_OK) {
+    if ((m_group ? rtx_group_refine_export(m_group, st.data(), st.size() * sizeof(float))
+                 : rtx_refine_export(m_ctx, st.data(), st.size() * sizeof(float))) != RTX_OK) {
         m_error = rtx_last_error();
         return false;
     }
@@ -280,8 +289,8 @@ bool RtxCSApp::SaveState(const std::string &path) {
 }
 
 bool RtxCSApp::LoadState(const std::string &path) {
-    if (m_group || !m_ctx) {
-        m_error = "LoadState: one context only";
+    if (!m_ctx) {
+        m_error = "LoadState: not initialized";
         return false;
     }
     ChainStateHeader want;
@@ -292,7 +301,8 @@ bool RtxCSApp::LoadState(const std::string &path) {
     std::vector<float> st;
     uint32_t samples = 0;
     if (!read_chain_state(path, want, st, samples, m_error)) return false;
-    if (rtx_refine_import(m_ctx, st.data(), st.size() * sizeof(float), samples) != RTX_OK) {
+    if ((m_group ? rtx_group_refine_import(m_group, m_cfg.tile_rows, st.data(), st.size() * sizeof(float), samples)
+                 : rtx_refine_import(m_ctx, st.data(), st.size() * sizeof(float), samples)) != RTX_OK) {
         m_error = rtx_last_error();
         return false;
     }

@@ -20,7 +20,7 @@
 // chain state after the last step; --load-state FILE imports one before the
 // first step (a later session continues where an earlier one stopped) and
 // exits nonzero if the file is damaged or belongs to another size, world or
-// frame. One context only. The JSON line then carries "refine" (the steps),
+// frame. The JSON line then carries "refine" (the steps),
 // "refined_samples" and "loaded_samples". --refine-keys carried orders each
 // step's pixel queue by the previous step's measured per-pixel cost instead of
 // a pre-pass per step (rtx_refine_set_keys; the image is the same), and the
@@ -33,6 +33,12 @@
 // counts as a PFM (the count in all three channels). --save-state works while
 // the counts are uniform; a checkpoint of a non-uniform state is refused
 // (RtxCSApp::SaveState).
+// With --gpus / --devices, --refine refines across the group (rtx_group_refine:
+// every member its own rows, tiles of --tile-rows), --save-state / --load-state
+// write and read the same one whole-frame state file (a file saved by one
+// context loads into a group of any size and the other way round),
+// --refine-keys applies to every member, and the JSON line carries the group
+// fields and the refine fields. --refine-adaptive runs on one context only.
 // --gpus N renders each frame across devices 0..N-1 (rtx_group: interleaved
 // tiles of T rows, default 5, one gather to device 0); --devices names them,
 // and a repeated device (0,0,0) rehearses the same split on one GPU, its
@@ -281,8 +287,12 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "rtx_cli: --refine-keys needs --refine\n");
         return 2;
     }
-    if (refining && (grouped || accumulate)) {
-        std::fprintf(stderr, "rtx_cli: --refine runs on one context, without --accumulate\n");
+    if (refining && (accumulate || split_frames)) {
+        std::fprintf(stderr, "rtx_cli: --refine runs without --accumulate and --split frames\n");
+        return 2;
+    }
+    if (adaptive && grouped) {
+        std::fprintf(stderr, "rtx_cli: --refine-adaptive runs on one context (a group refines with --refine)\n");
         return 2;
     }
     if (grouped && cfg.tile_rows == 0) {
@@ -308,7 +318,7 @@ int main(int argc, char **argv) {
                 std::fprintf(stderr, "rtx_cli: --load-state refused: %s\n", app.last_error().c_str());
                 return 1;
             }
-            loaded_samples = rtx_refined_samples(app.context());
+            loaded_samples = app.RefinedSamples();
         }
     } else {
         app.Render();  // warm-up frame (also the reference's single frame, main.cpp:38-39)
@@ -403,16 +413,29 @@ int main(int argc, char **argv) {
         const std::string split = split_frames ? "\"split\": \"frames\", \"accumulated_frames\": " +
                                                      std::to_string(rtx_group_accumulated_frames(grp))
                                                : "\"tile_rows\": " + std::to_string(cfg.tile_rows);
+        // a refining group: the refine line's fields as well
+        std::string ref;
+        if (refining) {
+            std::string steps;
+            for (size_t k = 0; k < refine.size(); ++k) steps += (k ? ", " : "") + std::to_string(refine[k]);
+            ref = ", \"refine\": [" + steps + "], \"loaded_samples\": " + std::to_string(loaded_samples) +
+                  ", \"refined_samples\": " + std::to_string(app.RefinedSamples()) + ", \"refine_keys\": \"" +
+                  (refine_keys == RTX_REFINE_KEYS_CARRIED ? "carried" : "prepass") + "\"";
+        }
         std::printf("{\"width\": %u, \"height\": %u, \"spp\": %u, \"depth\": %u, \"spheres\": %u, "
                     "\"cbuffers\": %s, \"frames\": %d, \"wall_s\": %.6f, \"kernel_ms\": %.4f, "
                     "\"msamples_per_s\": %.3f, \"segments\": %llu, \"sphere_tests\": %llu, "
                     "\"n_gpus\": %u, \"devices\": [%s], \"gather\": \"%s\", \"rccl_version\": %s, "
-                    "%s, \"per_member\": [%s], \"gather_ms\": %.4f, \"%s\": %.4f}\n",
+                    "%s, \"per_member\": [%s], \"gather_ms\": %.4f, \"%s\": %.4f%s}\n",
                     cfg.width, cfg.height, cfg.spp, cfg.depth, app.sphere_count(), cfg.cbuffers ? "true" : "false",
                     frames, wall, st.kernel_ms, (double)st.samples / wall / 1e6, (unsigned long long)st.segments,
                     (unsigned long long)st.sphere_tests, members, devs.c_str(),
                     rtx_group_gather_mode(grp) == RTX_GATHER_RCCL ? "rccl" : "copy", rccl.c_str(), split.c_str(),
-                    per.c_str(), gather_ms, split_frames ? "fold_ms" : "deinterleave_ms", deint_ms);
+                    per.c_str(), gather_ms, split_frames ? "fold_ms" : "deinterleave_ms", deint_ms, ref.c_str());
+        if (!save_state.empty() && !app.SaveState(save_state)) {
+            std::fprintf(stderr, "rtx_cli: --save-state failed: %s\n", app.last_error().c_str());
+            return 1;
+        }
     } else if (refining) {
         if (sync_rc != RTX_OK || rtx_get_stats(app.context(), &st) != RTX_OK) {
             std::fprintf(stderr, "rtx_cli: refine failed: %s\n", rtx_last_error());

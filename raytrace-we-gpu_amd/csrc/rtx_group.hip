@@ -6,6 +6,10 @@
 // rtx_group_accumulate is the second split: whole progressive frames dealt to
 // the members (rtx_render_sum), their sums gathered into the root's slots and
 // folded in frame order (rtx_fold_frames); its plan is in the same header.
+// rtx_group_refine is the row split again with rtx_refine_rows as each member's
+// launch (run_frame is the body all three share): every member keeps the chain
+// state of its own rows, and the group's checkpoint is one whole-frame state,
+// shuffled on the host by the plan header's scatter and gather.
 //
 // RCCL is loaded at run time (dlopen), so librtx.so carries no link
 // dependency on it: a single-GPU user pays nothing, and a process that has
@@ -145,6 +149,9 @@ struct rtx_group {
     bool have_acc_times = false;
     std::vector<double> acc_render_ms;
     double acc_gather_ms = 0.0, fold_ms = 0.0;
+    // rtx_group_refine: the samples in the members' chain states (0: none, the
+    // next call starts everyone fresh) and the tile_rows they were cut by
+    uint32_t ref_n = 0, ref_tile = 0;
 };
 
 namespace {
@@ -298,6 +305,88 @@ void destroy_group(rtx_group *g) {
     delete g;
 }
 
+// One frame of the row split into the image: every row-owning member's launch
+// (launch(i, n, d_out): member i's rows into d_out, asynchronous on its
+// stream), the gather, then the de-interleave on the root's stream.
+// rtx_group_render, rtx_group_refine and rtx_group_refine_import differ in the
+// launch only. The buffers fit (ensure_buffers).
+template <class Launch>
+int run_frame(rtx_group *g, const char *fn, Launch launch) {
+    int rc = RTX_OK;
+    const rtx::GroupPlan &plan = g->plan;
+    const uint32_t n = plan.n;
+    Member &root = g->m[0];
+    g->have_times = false;
+
+    // every member's render, one after the other from this thread: each is
+    // asynchronous on its member's stream
+    for (uint32_t i = 0; i < n; ++i) {
+        Member &mb = g->m[i];
+        mb.rendered = false;
+        if (!plan.renders(i)) continue;
+        RTXG_HIP(hipSetDevice(mb.device));
+        // its send buffer is free once the root has pulled the last frame's rows
+        if (i > 0 && !g->one_device && g->mode == RTX_GATHER_COPY && g->gathered_once)
+            RTXG_HIP(hipStreamWaitEvent(mb.stream, g->ev_g1, 0));
+        void *d_out = i > 0 ? mb.d_send : (g->direct ? g->d_image : g->d_gathered);
+        RTXG_HIP(hipEventRecord(mb.ev_start, mb.stream));
+        rc = launch(i, n, d_out);
+        if (rc != RTX_OK) {
+            const std::string why = rtx_last_error();
+            return fail(rc, std::string(fn) + ": member " + std::to_string(i) + ": " + why);
+        }
+        RTXG_HIP(hipSetDevice(mb.device));
+        RTXG_HIP(hipEventRecord(mb.ev_rendered, mb.stream));
+        mb.rendered = true;
+    }
+
+    // the gather, on the root's stream
+    RTXG_HIP(hipSetDevice(root.device));
+    RTXG_HIP(hipEventRecord(g->ev_g0, root.stream));
+    if (g->mode == RTX_GATHER_COPY) {
+        for (const rtx::GroupOp &op : plan.ops) {
+            if (op.bytes == 0) continue;
+            Member &mb = g->m[op.member];
+            char *dst = static_cast<char *>(g->d_gathered) + op.dst_off;
+            RTXG_HIP(hipStreamWaitEvent(root.stream, mb.ev_rendered, 0));
+            if (mb.device == root.device)
+                RTXG_HIP(hipMemcpyAsync(dst, mb.d_send, op.bytes, hipMemcpyDeviceToDevice, root.stream));
+            else
+                RTXG_HIP(hipMemcpyPeerAsync(dst, root.device, mb.d_send, mb.device, op.bytes, root.stream));
+        }
+    } else {
+        // what ncclGather does inside, with the symbols every RCCL has
+        int nrc = g->rccl.GroupStart();
+        if (nrc != 0) return nccl_fail(g, nrc, (std::string(fn) + ": ncclGroupStart").c_str());
+        for (const rtx::GroupOp &op : plan.ops) {
+            Member &mb = g->m[op.member];
+            const size_t floats = op.bytes / sizeof(float);
+            char *dst = static_cast<char *>(g->d_gathered) + op.dst_off;
+            (void)hipSetDevice(mb.device);
+            if (nrc == 0) nrc = g->rccl.Send(mb.d_send, floats, kNcclFloat, 0, mb.comm, mb.stream);
+            (void)hipSetDevice(root.device);
+            if (nrc == 0) nrc = g->rccl.Recv(dst, floats, kNcclFloat, (int)op.member, root.comm, root.stream);
+        }
+        const int erc = g->rccl.GroupEnd();  // always closed, also after a failed call inside
+        if (nrc != 0) return nccl_fail(g, nrc, (std::string(fn) + ": ncclSend/ncclRecv").c_str());
+        if (erc != 0) return nccl_fail(g, erc, (std::string(fn) + ": ncclGroupEnd").c_str());
+        RTXG_HIP(hipSetDevice(root.device));
+    }
+    RTXG_HIP(hipEventRecord(g->ev_g1, root.stream));
+    g->gathered_once = true;
+
+    // the de-interleave, after the gather on the same stream
+    RTXG_HIP(hipEventRecord(g->ev_d0, root.stream));
+    if (!g->direct) {
+        rc = rtx_deinterleave_rows(root.ctx, g->d_gathered, plan.width, plan.height, plan.tile_rows, n, g->d_image);
+        if (rc != RTX_OK) return rc;
+        RTXG_HIP(hipSetDevice(root.device));
+    }
+    RTXG_HIP(hipEventRecord(g->ev_d1, root.stream));
+    g->launched = true;
+    return RTX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -410,6 +499,7 @@ int rtx_group_rccl_version(rtx_group *g) { return g ? g->rccl_version : 0; }
 
 int rtx_group_upload_world(rtx_group *g, const rtx_world *w) {
     if (!g || !w) return fail(RTX_ERR_INVALID, "rtx_group_upload_world: null argument");
+    g->ref_n = 0;  // a chain state belongs to its world (as every member's falls)
     for (size_t i = 0; i < g->m.size(); ++i) {
         const int rc = rtx_upload_world(g->m[i].ctx, w);
         if (rc != RTX_OK) {
@@ -422,6 +512,8 @@ int rtx_group_upload_world(rtx_group *g, const rtx_world *w) {
 
 int rtx_group_set_frame(rtx_group *g, const rtx_frame *f) {
     if (!g || !f) return fail(RTX_ERR_INVALID, "rtx_group_set_frame: null argument");
+    // ... and to its frame: other bytes restart it, the same bytes again keep it
+    if (!g->have_frame || std::memcmp(f, &g->frame, sizeof *f) != 0) g->ref_n = 0;
     for (size_t i = 0; i < g->m.size(); ++i) {
         const int rc = rtx_set_frame(g->m[i].ctx, f);
         if (rc != RTX_OK) {
@@ -438,80 +530,11 @@ int rtx_group_render(rtx_group *g, uint32_t tile_rows) {
     if (!g) return fail(RTX_ERR_INVALID, "rtx_group_render: null group");
     if (tile_rows == 0) return fail(RTX_ERR_INVALID, "rtx_group_render: tile_rows is 0");
     if (!g->have_frame) return fail(RTX_ERR_STATE, "rtx_group_render: no frame set");
-    int rc = ensure_buffers(g, tile_rows);
+    const int rc = ensure_buffers(g, tile_rows);
     if (rc) return rc;
-    const rtx::GroupPlan &plan = g->plan;
-    const uint32_t n = plan.n;
-    Member &root = g->m[0];
-    g->have_times = false;
-
-    // every member's render, one after the other from this thread: each is
-    // asynchronous on its member's stream
-    for (uint32_t i = 0; i < n; ++i) {
-        Member &mb = g->m[i];
-        mb.rendered = false;
-        if (!plan.renders(i)) continue;
-        RTXG_HIP(hipSetDevice(mb.device));
-        // its send buffer is free once the root has pulled the last frame's rows
-        if (i > 0 && !g->one_device && g->mode == RTX_GATHER_COPY && g->gathered_once)
-            RTXG_HIP(hipStreamWaitEvent(mb.stream, g->ev_g1, 0));
-        void *d_out = i > 0 ? mb.d_send : (g->direct ? g->d_image : g->d_gathered);
-        RTXG_HIP(hipEventRecord(mb.ev_start, mb.stream));
-        rc = rtx_render_rows(mb.ctx, tile_rows, i, n, d_out);
-        if (rc != RTX_OK) {
-            const std::string why = rtx_last_error();
-            return fail(rc, "rtx_group_render: member " + std::to_string(i) + ": " + why);
-        }
-        RTXG_HIP(hipSetDevice(mb.device));
-        RTXG_HIP(hipEventRecord(mb.ev_rendered, mb.stream));
-        mb.rendered = true;
-    }
-
-    // the gather, on the root's stream
-    RTXG_HIP(hipSetDevice(root.device));
-    RTXG_HIP(hipEventRecord(g->ev_g0, root.stream));
-    if (g->mode == RTX_GATHER_COPY) {
-        for (const rtx::GroupOp &op : plan.ops) {
-            if (op.bytes == 0) continue;
-            Member &mb = g->m[op.member];
-            char *dst = static_cast<char *>(g->d_gathered) + op.dst_off;
-            RTXG_HIP(hipStreamWaitEvent(root.stream, mb.ev_rendered, 0));
-            if (mb.device == root.device)
-                RTXG_HIP(hipMemcpyAsync(dst, mb.d_send, op.bytes, hipMemcpyDeviceToDevice, root.stream));
-            else
-                RTXG_HIP(hipMemcpyPeerAsync(dst, root.device, mb.d_send, mb.device, op.bytes, root.stream));
-        }
-    } else {
-        // what ncclGather does inside, with the symbols every RCCL has
-        int nrc = g->rccl.GroupStart();
-        if (nrc != 0) return nccl_fail(g, nrc, "rtx_group_render: ncclGroupStart");
-        for (const rtx::GroupOp &op : plan.ops) {
-            Member &mb = g->m[op.member];
-            const size_t floats = op.bytes / sizeof(float);
-            char *dst = static_cast<char *>(g->d_gathered) + op.dst_off;
-            (void)hipSetDevice(mb.device);
-            if (nrc == 0) nrc = g->rccl.Send(mb.d_send, floats, kNcclFloat, 0, mb.comm, mb.stream);
-            (void)hipSetDevice(root.device);
-            if (nrc == 0) nrc = g->rccl.Recv(dst, floats, kNcclFloat, (int)op.member, root.comm, root.stream);
-        }
-        const int erc = g->rccl.GroupEnd();  // always closed, also after a failed call inside
-        if (nrc != 0) return nccl_fail(g, nrc, "rtx_group_render: ncclSend/ncclRecv");
-        if (erc != 0) return nccl_fail(g, erc, "rtx_group_render: ncclGroupEnd");
-        RTXG_HIP(hipSetDevice(root.device));
-    }
-    RTXG_HIP(hipEventRecord(g->ev_g1, root.stream));
-    g->gathered_once = true;
-
-    // the de-interleave, after the gather on the same stream
-    RTXG_HIP(hipEventRecord(g->ev_d0, root.stream));
-    if (!g->direct) {
-        rc = rtx_deinterleave_rows(root.ctx, g->d_gathered, plan.width, plan.height, plan.tile_rows, n, g->d_image);
-        if (rc != RTX_OK) return rc;
-        RTXG_HIP(hipSetDevice(root.device));
-    }
-    RTXG_HIP(hipEventRecord(g->ev_d1, root.stream));
-    g->launched = true;
-    return RTX_OK;
+    return run_frame(g, "rtx_group_render", [&](uint32_t i, uint32_t n, void *d_out) {
+        return rtx_render_rows(g->m[i].ctx, tile_rows, i, n, d_out);
+    });
 }
 
 int rtx_group_accumulate(rtx_group *g, uint32_t frames, int reset) {
@@ -620,6 +643,136 @@ int rtx_group_accumulate(rtx_group *g, uint32_t frames, int reset) {
 }
 
 uint32_t rtx_group_accumulated_frames(rtx_group *g) { return g ? g->acc_frames : 0; }
+
+// ---- progressive refinement across the members ------------------------------
+namespace {
+
+// What rtx_group_refine and rtx_group_refine_import decide before any HIP call.
+int refine_call_check(rtx_group *g, const char *fn, uint32_t samples, uint32_t tile_rows) {
+    const std::string f(fn);
+    if (!g) return fail(RTX_ERR_INVALID, f + ": null group");
+    if (samples == 0) return fail(RTX_ERR_INVALID, f + ": samples is 0");
+    if (tile_rows == 0) return fail(RTX_ERR_INVALID, f + ": tile_rows is 0");
+    if (!g->have_frame) return fail(RTX_ERR_STATE, f + ": no frame set");
+    for (size_t i = 0; i < g->m.size(); ++i) {
+        uint32_t spp = 0;
+        if (!rtx::ctx_world_spp(g->m[i].ctx, &spp))
+            return fail(RTX_ERR_STATE, f + ": member " + std::to_string(i) + ": no world uploaded");
+    }
+    if (g->frame.rng_mode == RTX_RNG_PER_SAMPLE)
+        return fail(RTX_ERR_INVALID, f + ": the per-sample RNG has no chain to continue (rtx_group_accumulate is its "
+                                         "progressive form)");
+    return RTX_OK;
+}
+
+// Every row-owning member's chain state is the group's: ref_n samples of part
+// i of n in tiles of ref_tile rows. Anything else means someone refined
+// through a borrowed rtx_group_ctx.
+int members_agree(rtx_group *g, const char *fn) {
+    const uint32_t n = (uint32_t)g->m.size();
+    for (uint32_t i = 0; i < n; ++i) {
+        if (rtx::group_part_rows(g->frame.height, g->ref_tile, i, n) == 0) continue;
+        uint32_t t = 0, part = 0, np = 0;
+        const uint32_t have = rtx_refined_samples(g->m[i].ctx);
+        const bool shaped = rtx_refine_shape(g->m[i].ctx, &t, &part, &np) == RTX_OK;
+        const uint32_t want_t = n == 1 ? 1u : g->ref_tile;  // (a whole frame's shape is (1, 0, 1))
+        if (have != g->ref_n || !shaped || t != want_t || part != i || np != n)
+            return fail(RTX_ERR_STATE, std::string(fn) + ": member " + std::to_string(i) + ": its chain state (" +
+                                           std::to_string(have) + " samples) is not the group's (" +
+                                           std::to_string(g->ref_n) + " samples, part " + std::to_string(i) + " of " +
+                                           std::to_string(n) + " in tiles of " + std::to_string(g->ref_tile) +
+                                           " rows): it was refined through rtx_group_ctx; reset the group's refine");
+    }
+    return RTX_OK;
+}
+
+}  // namespace
+
+int rtx_group_refine(rtx_group *g, uint32_t samples, uint32_t tile_rows, int reset) {
+    // arguments and state first: nothing in this block touches HIP
+    int rc = refine_call_check(g, "rtx_group_refine", samples, tile_rows);
+    if (rc) return rc;
+    const bool fresh = reset || g->ref_n == 0 || g->ref_tile != tile_rows;
+    const uint32_t have = fresh ? 0u : g->ref_n;
+    if (samples > 0xffffffffu - have)
+        return fail(RTX_ERR_INVALID, "rtx_group_refine: more than 2^32 - 1 samples in all");
+    if (!fresh) {
+        rc = members_agree(g, "rtx_group_refine");
+        if (rc) return rc;
+    }
+    rc = ensure_buffers(g, tile_rows);
+    if (rc) return rc;
+    // the group decides freshness and every member follows it; N counts again
+    // only once every member's launch and the assembly are enqueued
+    g->ref_n = 0;
+    rc = run_frame(g, "rtx_group_refine", [&](uint32_t i, uint32_t n, void *d_out) {
+        return rtx_refine_rows(g->m[i].ctx, tile_rows, i, n, samples, fresh ? 1 : 0, d_out);
+    });
+    if (rc != RTX_OK) return rc;
+    g->ref_n = have + samples;
+    g->ref_tile = tile_rows;
+    return RTX_OK;
+}
+
+uint32_t rtx_group_refined_samples(rtx_group *g) { return g ? g->ref_n : 0; }
+
+int rtx_group_refine_export(rtx_group *g, float *host_state, size_t bytes) {
+    if (!g || !host_state) return fail(RTX_ERR_INVALID, "rtx_group_refine_export: null argument");
+    if (g->ref_n == 0 || !g->have_frame) return fail(RTX_ERR_STATE, "rtx_group_refine_export: no chain state");
+    const uint32_t n = (uint32_t)g->m.size();
+    // (its own plan: rtx_group_render may have cut the buffers by another tile_rows since)
+    const rtx::GroupPlan plan = rtx::make_group_plan(n, g->frame.width, g->frame.height, g->ref_tile);
+    if (bytes != plan.image_bytes) return fail(RTX_ERR_INVALID, "rtx_group_refine_export: bytes != width*height*16");
+    int rc = members_agree(g, "rtx_group_refine_export");
+    if (rc) return rc;
+    std::vector<std::vector<float>> parts(n);
+    std::vector<const void *> ptrs(n, nullptr);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!plan.renders(i)) continue;
+        const size_t part_bytes = (size_t)plan.rows[i] * plan.width * rtx::kGroupPixelBytes;
+        parts[i].resize(part_bytes / sizeof(float));
+        rc = rtx_refine_export(g->m[i].ctx, parts[i].data(), part_bytes);
+        if (rc != RTX_OK) {
+            const std::string why = rtx_last_error();
+            return fail(rc, "rtx_group_refine_export: member " + std::to_string(i) + ": " + why);
+        }
+        ptrs[i] = parts[i].data();
+    }
+    rtx::group_gather_state(plan, ptrs.data(), host_state);
+    return RTX_OK;
+}
+
+int rtx_group_refine_import(rtx_group *g, uint32_t tile_rows, const float *host_state, size_t bytes,
+                            uint32_t samples) {
+    int rc = refine_call_check(g, "rtx_group_refine_import", samples, tile_rows);
+    if (rc) return rc;
+    if (!host_state) return fail(RTX_ERR_INVALID, "rtx_group_refine_import: null host_state");
+    if (bytes != (size_t)g->frame.width * g->frame.height * rtx::kGroupPixelBytes)
+        return fail(RTX_ERR_INVALID, "rtx_group_refine_import: bytes != width*height*16");
+    rc = ensure_buffers(g, tile_rows);
+    if (rc) return rc;
+    const rtx::GroupPlan &plan = g->plan;
+    const uint32_t n = plan.n;
+    std::vector<std::vector<float>> parts(n);
+    std::vector<void *> ptrs(n, nullptr);
+    for (uint32_t i = 0; i < n; ++i) {
+        parts[i].resize((size_t)plan.rows[i] * plan.width * (rtx::kGroupPixelBytes / sizeof(float)));
+        ptrs[i] = parts[i].data();
+    }
+    rtx::group_scatter_state(plan, host_state, ptrs.data());
+    g->ref_n = 0;
+    // each member's rows, its image rows into its slot; then the image is assembled
+    rc = run_frame(g, "rtx_group_refine_import", [&](uint32_t i, uint32_t np, void *d_out) {
+        return rtx_refine_import_rows(g->m[i].ctx, tile_rows, i, np, parts[i].data(), parts[i].size() * sizeof(float),
+                                      samples, d_out);
+    });
+    if (rc != RTX_OK) return rc;
+    rc = rtx_group_sync(g);  // synchronous, like rtx_refine_import
+    if (rc != RTX_OK) return rc;
+    g->ref_n = samples;
+    g->ref_tile = tile_rows;
+    return RTX_OK;
+}
 
 int rtx_group_get_accumulate_times(rtx_group *g, double *render_ms, double *gather_ms, double *fold_ms) {
     if (!g) return fail(RTX_ERR_INVALID, "rtx_group_get_accumulate_times: null group");

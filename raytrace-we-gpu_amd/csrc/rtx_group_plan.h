@@ -11,6 +11,9 @@
 // [n][max_rows][width]; one transfer per other member moves its rows to the
 // start of slot m; rtx_deinterleave_rows turns the gathered buffer into the
 // image [height][width].
+// group_scatter_state / group_gather_state move a chain state between one
+// whole frame and the members' parts (rtx_group_refine_import / _export),
+// executed on host memory by tests/group_refine_check.cpp too.
 // The second half of the file is the frame split (rtx_group_accumulate):
 // AccumPlan / accum_round, executed on host memory by
 // tests/group_accum_check.cpp.
@@ -19,6 +22,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <cstring>
 #include <vector>
 
 namespace rtx {
@@ -94,6 +98,34 @@ inline void group_row_owner(const GroupPlan &p, uint32_t y, uint32_t *member, ui
     const uint32_t tile = y / p.tile_rows;
     *member = tile % p.n;
     *local_row = (tile / p.n) * p.tile_rows + (y - tile * p.tile_rows);
+}
+
+// ---- a chain state between one whole frame and the members' parts ----------
+// (rtx_group_refine_export / rtx_group_refine_import, on host memory.) A
+// member's chain state covers its own rows in its row order, group_row_owner's
+// (member, local_row); the checkpoint is one whole-frame state
+// [height][width] in framebuffer order. parts[m]: member m's rows[m] * width
+// pixels of `pixel_bytes` each (ignored, and may be null, for a member without
+// rows); whole: height * width pixels.
+inline void group_scatter_state(const GroupPlan &p, const void *whole, void *const *parts,
+                                size_t pixel_bytes = kGroupPixelBytes) {
+    const size_t row_bytes = (size_t)p.width * pixel_bytes;
+    for (uint32_t y = 0; y < p.height; ++y) {
+        uint32_t m, r;
+        group_row_owner(p, y, &m, &r);
+        std::memcpy(static_cast<char *>(parts[m]) + (size_t)r * row_bytes,
+                    static_cast<const char *>(whole) + (size_t)y * row_bytes, row_bytes);
+    }
+}
+inline void group_gather_state(const GroupPlan &p, const void *const *parts, void *whole,
+                               size_t pixel_bytes = kGroupPixelBytes) {
+    const size_t row_bytes = (size_t)p.width * pixel_bytes;
+    for (uint32_t y = 0; y < p.height; ++y) {
+        uint32_t m, r;
+        group_row_owner(p, y, &m, &r);
+        std::memcpy(static_cast<char *>(whole) + (size_t)y * row_bytes,
+                    static_cast<const char *>(parts[m]) + (size_t)r * row_bytes, row_bytes);
+    }
 }
 
 // ---- progressive frames dealt across the members (rtx_group_accumulate) ----

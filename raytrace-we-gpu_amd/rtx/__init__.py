@@ -138,6 +138,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_refine_state": (vp, [ctx]),
         "rtx_refine_export": (C.c_int, [ctx, f, C.c_size_t]),
         "rtx_refine_import": (C.c_int, [ctx, f, C.c_size_t, u32]),
+        "rtx_refine_rows": (C.c_int, [ctx, u32, u32, u32, u32, C.c_int, vp]),
+        "rtx_refine_import_rows": (C.c_int, [ctx, u32, u32, u32, f, C.c_size_t, u32, vp]),
+        "rtx_refine_shape": (C.c_int, [ctx, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
         "rtx_refine_set_keys": (C.c_int, [ctx, C.c_int]),
         "rtx_refine_last_keys": (C.c_int, [ctx]),
         "rtx_refine_cost": (C.c_int, [ctx, C.POINTER(u32), C.c_size_t, C.POINTER(u32)]),
@@ -193,6 +196,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_group_accumulated_frames": (u32, [vp]),
         "rtx_group_get_accumulate_times": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                      C.POINTER(C.c_double)]),
+        "rtx_group_refine": (C.c_int, [vp, u32, u32, C.c_int]),
+        "rtx_group_refined_samples": (u32, [vp]),
+        "rtx_group_refine_export": (C.c_int, [vp, f, C.c_size_t]),
+        "rtx_group_refine_import": (C.c_int, [vp, u32, f, C.c_size_t, u32]),
     }
     # entry points added after 1.0 may be absent from older builds (A/B runs
     # of earlier libraries); calling one then fails with AttributeError
@@ -463,11 +470,48 @@ class Context:
         """Samples per pixel in the chain state (0: none)."""
         return int(self._lib.rtx_refined_samples(self._h))
 
+    def refine_rows(self, tile_rows: int, part: int, nparts: int, samples: int, reset: bool = False,
+                    d_out: Optional[int] = None) -> int:
+        """refine() for the rows of `part` of `nparts` (render_rows' partition)
+        into d_out (device pointer, rows * width float4; None: the framebuffer,
+        nparts == 1 only). The chain state then covers those rows only. With
+        samples and reset bound it has render_rows' signature, so a rank of
+        rtx.dist.FrameGather passes it as its render_part (rtx_refine_rows).
+        Returns the samples refined so far."""
+        _check(self._lib.rtx_refine_rows(self._h, tile_rows, part, nparts, samples, 1 if reset else 0,
+                                         C.c_void_p(d_out or 0)), "rtx_refine_rows", self._lib)
+        return int(self._lib.rtx_refined_samples(self._h))
+
+    def refine_import_rows(self, tile_rows: int, part: int, nparts: int, state: np.ndarray, samples: int,
+                           d_out: Optional[int] = None):
+        """refine_import() for a part: `state` is (rows, W, 4) in the part's row
+        order; its image rows go to d_out (None with nparts > 1: no image)
+        (rtx_refine_import_rows)."""
+        state = np.ascontiguousarray(state, np.float32)
+        _check(self._lib.rtx_refine_import_rows(self._h, tile_rows, part, nparts, _fptr(state), state.nbytes, samples,
+                                                C.c_void_p(d_out or 0)), "rtx_refine_import_rows", self._lib)
+
+    def refine_shape(self) -> tuple:
+        """(tile_rows, part, nparts) of the chain state; the whole frame is
+        (1, 0, 1). RtxError when there is no state (rtx_refine_shape)."""
+        t, p, n = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        _check(self._lib.rtx_refine_shape(self._h, C.byref(t), C.byref(p), C.byref(n)), "rtx_refine_shape", self._lib)
+        return int(t.value), int(p.value), int(n.value)
+
+    def _state_rows(self) -> int:
+        """Rows of the chain state: the frame's, or a part state's own."""
+        t, p, n = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        if hasattr(self._lib, "rtx_refine_shape") and \
+                self._lib.rtx_refine_shape(self._h, C.byref(t), C.byref(p), C.byref(n)) == RTX_OK:
+            return int(self._lib.rtx_part_rows(self.frame.height, t.value, p.value, n.value))
+        return int(self.frame.height)
+
     def refine_export(self) -> np.ndarray:
         """The chain state, (H, W, 4) float32: xyz the pixel's linear sample
-        sum, w its seed after its last sample (rtx_refine_export)."""
+        sum, w its seed after its last sample (rtx_refine_export). A part
+        state (refine_rows): (rows, W, 4) in the part's row order."""
         f = self.frame
-        out = np.empty((f.height, f.width, 4), np.float32)
+        out = np.empty((self._state_rows(), f.width, 4), np.float32)
         _check(self._lib.rtx_refine_export(self._h, _fptr(out), out.nbytes), "rtx_refine_export", self._lib)
         return out
 
@@ -498,9 +542,10 @@ class Context:
 
     def refine_cost(self):
         """The last refine launch's cost map and the samples it covers:
-        ((H, W) uint32 ray segments per pixel, samples) (rtx_refine_cost)."""
+        ((H, W) uint32 ray segments per pixel, samples) (rtx_refine_cost); a
+        part state's map is (rows, W) in the part's row order."""
         f = self.frame
-        out = np.empty((f.height, f.width), np.uint32)
+        out = np.empty((self._state_rows(), f.width), np.uint32)
         n = C.c_uint32(0)
         _check(self._lib.rtx_refine_cost(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.nbytes, C.byref(n)),
                "rtx_refine_cost", self._lib)
@@ -774,6 +819,39 @@ class Group:
     @property
     def accumulated_frames(self) -> int:
         return int(self._lib.rtx_group_accumulated_frames(self._h))
+
+    def refine(self, samples: int, tile_rows: int = 5, reset: bool = False) -> int:
+        """`samples` more samples of every pixel along the reference's own RNG
+        chain, each member refining its own rows (Context.refine_rows), then the
+        gather and the de-interleave: the image of as many Context.refine
+        calls, bit for bit. Returns the samples refined so far
+        (rtx_group_refine)."""
+        _check(self._lib.rtx_group_refine(self._h, samples, tile_rows, 1 if reset else 0), "rtx_group_refine",
+               self._lib)
+        return self.refined_samples
+
+    @property
+    def refined_samples(self) -> int:
+        """Samples per pixel in the group's chain state (0: none)."""
+        return int(self._lib.rtx_group_refined_samples(self._h))
+
+    def refine_export(self) -> np.ndarray:
+        """The group's chain state as one whole-frame state, (H, W, 4) float32:
+        what Context.refine_export gives on one context at the same N
+        (rtx_group_refine_export)."""
+        f = self.frame
+        out = np.empty((f.height, f.width, 4), np.float32)
+        _check(self._lib.rtx_group_refine_export(self._h, _fptr(out), out.nbytes), "rtx_group_refine_export",
+               self._lib)
+        return out
+
+    def refine_import(self, state: np.ndarray, samples: int, tile_rows: int = 5):
+        """Install a whole-frame chain state of `samples` samples per pixel,
+        every member its rows, and assemble its image; the next refine() with
+        this tile_rows continues from it (rtx_group_refine_import)."""
+        state = np.ascontiguousarray(state, np.float32)
+        _check(self._lib.rtx_group_refine_import(self._h, tile_rows, _fptr(state), state.nbytes, samples),
+               "rtx_group_refine_import", self._lib)
 
     def accumulate_times(self) -> dict:
         """HIP-event times of the last round of the last accumulate(), after
