@@ -40,6 +40,13 @@ extern "C" {
 
 #define RTX_VERSION 145 /* 1.4.5 */
 /* ABI notes.
+ *  1.4.5 (later builds, no version bump): rtx_refine_adaptive_rows,
+ *         rtx_refine_pending_rows, rtx_refine_edges, rtx_refine_counts_rows and
+ *         rtx_refine_error_rows (adaptive refinement of a row part on a
+ *         context), rtx_group_refine_adaptive, rtx_group_refine_pending,
+ *         rtx_group_refine_counts and rtx_group_refine_error (... across a
+ *         group's members); purely additive again: probe for the symbol
+ *         (dlsym "rtx_refine_adaptive_rows").
  *  1.4.5 (later builds, no version bump): rtx_refine_rows,
  *         rtx_refine_import_rows and rtx_refine_shape (refinement of a row
  *         part on a context), rtx_group_refine, rtx_group_refined_samples,
@@ -411,8 +418,9 @@ RTX_API int rtx_fold_frames(rtx_ctx *ctx, void *d_accum, const void *d_sums, uin
  * spp (frame_index * spp + s), so "continue" has no single meaning there;
  * rtx_accumulate is that mode's progressive form. RTX_ERR_STATE: no world or
  * no frame.
- * Row parts: rtx_refine_rows below; a group-wide refine: rtx_group_refine.
- * Not covered (a later change): adaptive refinement across row parts.
+ * Row parts: rtx_refine_rows below; a group-wide refine: rtx_group_refine;
+ * adaptive refinement of a part and of a group: rtx_refine_adaptive_rows and
+ * rtx_group_refine_adaptive.
  * The pixel queue's order: see rtx_refine_set_keys below. */
 RTX_API int rtx_refine(rtx_ctx *ctx, uint32_t samples, int reset);
 /* rtx_refine for the rows of partition `part` of `nparts` (rtx_render_rows'
@@ -435,10 +443,13 @@ RTX_API int rtx_refine(rtx_ctx *ctx, uint32_t samples, int reset);
  * state's own pixel count (rows * width). Carried keys (rtx_refine_set_keys)
  * work on a part unchanged, the map in part order; the key's 3 x 3 window runs
  * over the part's local rows, which affects the queue's order only.
- * Adaptive refinement of a part state is not supported: on a context whose
- * state has nparts > 1, rtx_refine_adaptive with reset == 0, rtx_refine_pending,
+ * Adaptive refinement of a part state goes through the _rows entry points
+ * (rtx_refine_adaptive_rows below): on a context whose state has nparts > 1,
+ * the whole-frame rtx_refine_adaptive with reset == 0, rtx_refine_pending,
  * rtx_refine_counts and rtx_refine_error return RTX_ERR_STATE before any GPU
- * work; rtx_refine_adaptive with reset != 0 starts its whole-frame state.
+ * work; rtx_refine_adaptive with reset != 0 starts its whole-frame state. On a
+ * part state whose counts differ after adaptive steps rtx_refine_rows without
+ * reset returns RTX_ERR_STATE, as rtx_refine does on a whole frame.
  * RTX_ERR_INVALID, before any HIP call: a null ctx, samples == 0,
  * tile_rows == 0, nparts == 0, part >= nparts, d_out == NULL with nparts > 1,
  * N + samples above 2^32 - 1, a per-sample-RNG frame. RTX_ERR_STATE: no world
@@ -567,6 +578,56 @@ RTX_API int rtx_refine_pending(rtx_ctx *ctx, uint32_t samples, float threshold,
  * call has touched yet reads as count N and err +inf. */
 RTX_API int rtx_refine_counts(rtx_ctx *ctx, uint32_t *host_counts, size_t bytes);
 RTX_API int rtx_refine_error(rtx_ctx *ctx, float *host_err, size_t bytes);
+/* ---- adaptive refinement of a row part --------------------------------------
+ * (later builds, no version bump: probe with dlsym "rtx_refine_adaptive_rows").
+ * rtx_refine_adaptive for the rows of `part` of `nparts` (rtx_render_rows'
+ * partition): the chain state, count, err and the cost map cover the part's
+ * rows in its row order, and the state restarts under rtx_refine_rows' rules
+ * (reset, other frame bytes, another shape, a new world). The parts of a
+ * frame, each with its own state, hold bit for bit the rows of what
+ * rtx_refine_adaptive gives on one context for the same calls — provided each
+ * call sees its neighbours' edges: a pixel's 3 x 3 window crosses tile edges.
+ *
+ * d_halo: device pointer, two planes [2][tiles_of_part][width] fp32. Plane 0,
+ * slot j: the err row just below local tile j's first row (the last err row
+ * of tile k - 1, k = part + j * nparts); plane 1, slot j: the err row just
+ * above its last row (the first err row of tile k + 1). A slot whose row lies
+ * outside the image is never read. d_halo may be NULL only when nparts == 1
+ * (the rule reads the local map), or when the state is fresh or uniform (every
+ * err is +inf, so only max_samples decides; a non-NULL d_halo is not read).
+ * rtx_refine_edges writes a state's own edges in the same layout — plane 0
+ * each local tile's first err row, plane 1 its last (one row twice for a
+ * 1-row tile; the ragged final tile's last row is the image's top row), +inf
+ * for a uniform state whose maps are not filled yet — asynchronously on the
+ * context stream; d_edges: 2 * tiles * width floats, tiles = the state's
+ * ceil(rows / tile_rows) (a whole-frame state: tile_rows 1). The caller moves
+ * edge rows into the neighbours' halos (rtx_group_refine_adaptive does).
+ *
+ * d_out receives the part's rows. Every pixel of the part is written by every
+ * call that traces anything: the traced ones by the launch, the others from
+ * the state (toGamma(sum / (float)count), w = 1), so whatever overwrote the
+ * buffer between two calls does not matter. A call with no active pixel
+ * launches no render, leaves the state, the maps and N alone and does not touch
+ * d_out. d_out == NULL is allowed only with nparts == 1 and selects the
+ * context framebuffer; the call is then exactly rtx_refine_adaptive (inactive
+ * pixels untouched). A part that owns no rows returns RTX_OK with *active = 0.
+ * RTX_ERR_INVALID, before any HIP call: rtx_refine_adaptive's rules,
+ * tile_rows == 0, nparts == 0, part >= nparts, d_out == NULL with nparts > 1,
+ * d_halo == NULL where it is needed. RTX_ERR_STATE: no world or no frame. */
+RTX_API int rtx_refine_adaptive_rows(rtx_ctx *ctx, uint32_t tile_rows, uint32_t part, uint32_t nparts,
+                                     uint32_t samples, float threshold, uint32_t max_samples, int reset,
+                                     const void *d_halo, void *d_out, uint32_t *active);
+/* rtx_refine_pending for a part: the mask only. *active must not be NULL. */
+RTX_API int rtx_refine_pending_rows(rtx_ctx *ctx, uint32_t tile_rows, uint32_t part, uint32_t nparts,
+                                    uint32_t samples, float threshold, uint32_t max_samples,
+                                    const void *d_halo, uint32_t *active);
+/* See above. RTX_ERR_STATE when there is no chain state; RTX_ERR_INVALID for
+ * a null argument. */
+RTX_API int rtx_refine_edges(rtx_ctx *ctx, void *d_edges);
+/* rtx_refine_counts / rtx_refine_error for a state of any shape: bytes == the
+ * state's rows * width * 4, in the part's row order (as rtx_refine_export). */
+RTX_API int rtx_refine_counts_rows(rtx_ctx *ctx, uint32_t *host_counts, size_t bytes);
+RTX_API int rtx_refine_error_rows(rtx_ctx *ctx, float *host_err, size_t bytes);
 /* Device pointer of the chain state (width*height float4; a part state: its
  * rows * width), NULL if none. */
 RTX_API void *rtx_refine_state(rtx_ctx *ctx);
@@ -748,6 +809,45 @@ RTX_API int rtx_group_refine_export(rtx_group *g, float *host_state, size_t byte
  * a null host_state or other bytes. */
 RTX_API int rtx_group_refine_import(rtx_group *g, uint32_t tile_rows, const float *host_state,
                                     size_t bytes, uint32_t samples);
+/* Adaptive refinement across the members (later builds, no version bump: probe
+ * with dlsym "rtx_refine_adaptive_rows"): rtx_refine_adaptive with the rows
+ * split as in rtx_group_refine. The image, the counts, the errors and the
+ * chain state are bit for bit what rtx_refine_adaptive gives on one context
+ * for the same calls, whatever n and tile_rows. Two phases from the calling
+ * thread. Phase 1: every row-owning member packs its tiles' edge rows of err
+ * (rtx_refine_edges), the edge rows travel into the neighbours' halo buffers
+ * (stream-ordered copies on one device, hipMemcpyPeerAsync ordered by events
+ * between devices, one ncclGroupStart/End of send/recv in an RCCL group), every
+ * member computes its mask (rtx_refine_pending_rows) and *active (may be NULL)
+ * receives the sum. If that is 0 nothing else happens: N, the image, the
+ * states and the maps stay. Phase 2: every member with active pixels launches
+ * (rtx_refine_adaptive_rows) into its slot; a member with rows but no active
+ * pixel launches no render, writes its current rows from its state, and keeps
+ * its own N; the usual gather and de-interleave follow. The call is
+ * synchronous up to the masks' 4-byte readbacks, asynchronous after.
+ * Freshness is the group's decision, as in rtx_group_refine; a fresh call
+ * traces every pixel without an exchange. rtx_group_refined_samples is the sum
+ * of the steps that traced anything. The group remembers each member's N and
+ * refuses (RTX_ERR_STATE, naming the member) when one was refined through
+ * rtx_group_ctx. After a call that left the counts non-uniform,
+ * rtx_group_refine without reset returns RTX_ERR_STATE (continue with
+ * rtx_group_refine_adaptive); rtx_group_refine_export still copies the sums
+ * and seeds, rtx_group_refine_import installs a uniform state.
+ * rtx_group_render between two calls overwrites the image, not the states.
+ * RTX_ERR_INVALID, before any HIP call: a null group, rtx_refine_adaptive's
+ * argument rules, tile_rows == 0. RTX_ERR_STATE: no frame or no world. */
+RTX_API int rtx_group_refine_adaptive(rtx_group *g, uint32_t samples, float threshold,
+                                      uint32_t max_samples, uint32_t tile_rows, int reset,
+                                      uint32_t *active);
+/* Phase 1 alone: the number of pixels the same call would trace now.
+ * *active must not be NULL. */
+RTX_API int rtx_group_refine_pending(rtx_group *g, uint32_t samples, float threshold,
+                                     uint32_t max_samples, uint32_t tile_rows, uint32_t *active);
+/* The members' count and err maps as whole-frame maps in framebuffer order,
+ * bytes == width*height*4 (what rtx_refine_counts / rtx_refine_error give on
+ * one context). Synchronous. RTX_ERR_STATE without a chain state. */
+RTX_API int rtx_group_refine_counts(rtx_group *g, uint32_t *host_counts, size_t bytes);
+RTX_API int rtx_group_refine_error(rtx_group *g, float *host_err, size_t bytes);
 
 /* ---- device buffers (for callers without their own allocator) ----------
  * Ordered on the context stream; copies are synchronous. d_ptr from

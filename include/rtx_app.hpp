@@ -132,9 +132,10 @@ public:
     // `samples` more samples of the pixels that are still noisy
     // (rtx_refine_adaptive: an error estimate >= threshold in the pixel's
     // 3 x 3 neighbourhood, and its count within max_samples; 0: no cap);
-    // *active (may be NULL): how many were traced. One context only: with a
-    // group it returns false with a message (a pixel's neighbourhood crosses
-    // the members' tile edges).
+    // *active (may be NULL): how many were traced. With a group every member
+    // refines the noisy pixels of its own rows after the members exchanged
+    // their tiles' edge rows of the error map (rtx_group_refine_adaptive,
+    // AppConfig::tile_rows): the image and the counts are the same.
     bool RefineAdaptive(uint32_t samples, float threshold, uint32_t max_samples, bool reset, uint32_t *active);
     // What orders a scheduled Refine's pixel queue: RTX_REFINE_KEYS_PREPASS (a
     // cost pre-pass per step, the default) or RTX_REFINE_KEYS_CARRIED (the

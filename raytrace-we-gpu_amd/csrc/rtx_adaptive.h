@@ -1,8 +1,10 @@
 // rtx_adaptive.h — the rule of adaptive refinement (include/rtx.h
 // rtx_refine_adaptive): a pixel's error estimate after a step and which pixels
-// a call traces. HIP-free: the kernels (rtx_kernels.hip write_pixel,
-// k_adaptive_mask), the host (rtx_api.hip rtx_adaptive_error) and a CPU
-// checker (tests/adaptive_check.cpp) all run this one text.
+// a call traces, on the whole frame and on a row part of it. HIP-free: the
+// kernels (rtx_kernels.hip write_pixel, k_adaptive_mask, k_adaptive_mask_rows),
+// the host (rtx_api.hip rtx_adaptive_error) and the CPU checkers
+// (tests/adaptive_check.cpp, tests/group_adaptive_check.cpp) all run this one
+// text.
 #pragma once
 
 #include <math.h>
@@ -69,6 +71,60 @@ RTX_ADAPT_HD bool adaptive_active(const float *err, const uint32_t *count, uint3
             const int xx = x + dx;
             if (xx < 0 || xx >= (int)width) continue;
             if (err[(uint64_t)(uint32_t)yy * width + (uint32_t)xx] >= threshold) return true;
+        }
+    }
+    return false;
+}
+
+// ---- the rule on a row part (rtx_refine_adaptive_rows) ----------------------
+// A frame of `height` rows in tiles of `tile_rows`; tile k belongs to part
+// k % nparts as its local tile k / nparts (rtx_render_rows' partition). A
+// part's maps hold its own rows only, so the err row just outside one of its
+// tiles comes from a halo buffer the caller filled from the neighbours:
+//   halo[2][tiles_of_part][width] fp32
+//   plane 0, slot j: the err row just below local tile j's first row
+//   plane 1, slot j: the err row just above its last row
+// A slot whose row lies outside the image is never read. The same layout is a
+// part's edges (k_adaptive_edges): plane 0 each tile's first err row, plane 1
+// its last (one row twice for a 1-row tile).
+
+// Tiles of `part`: tiles part, part + nparts, ... below ceil(height / tile_rows).
+RTX_ADAPT_HD uint32_t adaptive_part_tiles(uint32_t height, uint32_t tile_rows, uint32_t part, uint32_t nparts) {
+    const uint32_t tiles = (uint32_t)(((uint64_t)height + tile_rows - 1u) / tile_rows);
+    return part >= tiles ? 0u : (tiles - part + nparts - 1u) / nparts;
+}
+
+// adaptive_active for local pixel i of part `part` (err, count: the part's
+// maps in its row order). nparts == 1 reads the local maps alone and is
+// adaptive_active. halo == NULL with nparts > 1 skips the rows outside a tile:
+// right only where every err is +inf (a fresh or uniform state), since then
+// the pixel's own entry already decides.
+RTX_ADAPT_HD bool adaptive_active_rows(const float *err, const uint32_t *count, const float *halo, uint32_t i,
+                                       uint32_t width, uint32_t height, uint32_t tile_rows, uint32_t part,
+                                       uint32_t nparts, uint32_t samples, float threshold, uint32_t max_samples) {
+    if (max_samples != 0u && (uint64_t)count[i] + samples > max_samples) return false;
+    const uint32_t lr = i / width, j = lr / tile_rows, r = lr - j * tile_rows;
+    const int x = (int)(i - lr * width);
+    const uint32_t y0 = (part + j * nparts) * tile_rows;  // the tile's first row in the image
+    const uint32_t left = height - y0;
+    const uint32_t trows = left < tile_rows ? left : tile_rows;  // (the ragged final tile)
+    const uint64_t plane = (uint64_t)adaptive_part_tiles(height, tile_rows, part, nparts) * width;
+    for (int dy = -1; dy <= 1; ++dy) {
+        const float *row;
+        if (dy < 0 && r == 0u) {
+            if (y0 == 0u) continue;  // below the image
+            row = nparts == 1u ? err + (uint64_t)(lr - 1u) * width : halo ? halo + (uint64_t)j * width : nullptr;
+        } else if (dy > 0 && r == trows - 1u) {
+            if (y0 + trows >= height) continue;  // above the image
+            row = nparts == 1u ? err + (uint64_t)(lr + 1u) * width : halo ? halo + plane + (uint64_t)j * width : nullptr;
+        } else {
+            row = err + (uint64_t)(uint32_t)((int)lr + dy) * width;
+        }
+        if (!row) continue;
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int xx = x + dx;
+            if (xx < 0 || xx >= (int)width) continue;
+            if (row[xx] >= threshold) return true;
         }
     }
     return false;

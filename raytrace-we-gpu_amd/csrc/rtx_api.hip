@@ -1333,36 +1333,54 @@ static rtx::KAdaptive adapt_maps(const rtx_ctx *c) {
     a.flags = reinterpret_cast<uint8_t *>(c->d_adapt + 2 * c->adapt_pixels + 4);
     return a;
 }
-// A chain state of a row part (rtx_refine_rows with nparts > 1): the adaptive
-// entry points refuse it (a pixel's 3 x 3 neighbourhood crosses tile edges).
+// A chain state of a row part (nparts > 1): the whole-frame entry points
+// refuse it (their maps and their 3 x 3 window are a whole frame's).
 static bool part_state(const rtx_ctx *c) { return c->chain_n != 0 && c->d_chain && c->chain_nparts > 1; }
 static const char *const kPartStateWhy =
-    "the chain state covers a row part (rtx_refine_rows, nparts > 1): adaptive refinement of a part is not "
-    "supported; reset, or refine the whole frame";
+    "the chain state covers a row part (nparts > 1): continue it with rtx_refine_adaptive_rows / "
+    "rtx_refine_pending_rows and read it with rtx_refine_counts_rows / rtx_refine_error_rows; or reset";
+// A call's partition: part `part` of `nparts` in tiles of `tile_rows` (the
+// whole frame: (1, 0, 1) whatever tile_rows, as rtx_refine_rows).
+struct AdaptShape {
+    uint32_t tile_rows, part, nparts;
+    bool whole_only;  // rtx_refine_adaptive / rtx_refine_pending: a part state is refused, not restarted
+};
+static const AdaptShape kWholeFrame = {1u, 0u, 1u, true};
+static uint32_t shape_rows(const rtx_ctx *c, const AdaptShape &s) {
+    return rtx_part_rows(c->frame.height, s.tile_rows, s.part, s.nparts);
+}
 // Whether a call continues the context's chain state (else it starts fresh).
-static bool chain_continues(const rtx_ctx *c, int reset) {
-    const size_t px = (size_t)c->frame.width * c->frame.height;
-    return !reset && c->chain_n != 0 && c->d_chain && c->chain_pixels == px && c->chain_nparts == 1 &&
+static bool chain_continues(const rtx_ctx *c, const AdaptShape &s, int reset) {
+    const size_t px = (size_t)c->frame.width * shape_rows(c, s);
+    return !reset && c->chain_n != 0 && c->d_chain && c->chain_pixels == px &&
+           chain_shape_is(c, s.tile_rows, s.part, s.nparts) &&
            std::memcmp(&c->frame, &c->chain_frame, sizeof c->frame) == 0;
 }
-// The argument and state rules the two calls share, decided before any HIP call.
-static int adaptive_check(const rtx_ctx *c, const char *fn, uint32_t samples, float threshold, uint32_t max_samples,
-                          int reset) {
-    char buf[256];
+// The argument and state rules the calls share, decided before any HIP call.
+// *s: the call's partition, normalised here. need_out: rtx_refine_adaptive_rows.
+static int adaptive_check(const rtx_ctx *c, const char *fn, AdaptShape *s, uint32_t samples, float threshold,
+                          uint32_t max_samples, int reset, const void *d_halo, bool need_out, const void *d_out) {
+    char buf[320];
     auto bad = [&](int code, const char *why) {
         std::snprintf(buf, sizeof buf, "%s: %s", fn, why);
         return fail(code, buf);
     };
     if (!c) return bad(RTX_ERR_INVALID, "null ctx");
     if (const char *why = rtx::adaptive_args_error(samples, threshold, max_samples)) return bad(RTX_ERR_INVALID, why);
+    if (s->tile_rows == 0 || s->nparts == 0 || s->part >= s->nparts)
+        return bad(RTX_ERR_INVALID, "bad partition (tile_rows, part, nparts)");
+    if (need_out && !d_out && s->nparts > 1) return bad(RTX_ERR_INVALID, "d_out NULL needs nparts == 1");
+    if (s->nparts == 1) s->tile_rows = 1;
     if (!c->have_world) return bad(RTX_ERR_STATE, "no world uploaded");
     if (!c->have_frame) return bad(RTX_ERR_STATE, "no frame set");
     if (c->frame.rng_mode == RTX_RNG_PER_SAMPLE) return bad(RTX_ERR_INVALID, "the per-sample RNG has no chain to continue");
-    if (c->depth == 0) return bad(RTX_ERR_INVALID, "depth is 0: nothing to estimate an error from");
-    if (!rtx::cost_map_fits(samples, c->depth)) return bad(RTX_ERR_INVALID, "samples * depth does not fit 32 bits");
-    if (!reset && part_state(c)) return bad(RTX_ERR_STATE, kPartStateWhy);
-    const uint32_t have = chain_continues(c, reset) ? c->chain_n : 0u;
-    if (samples > 0xffffffffu - have) return bad(RTX_ERR_INVALID, "more than 2^32 - 1 samples in all");
+    if (const char *why = rtx::ctx_adaptive_refusal(c, samples)) return bad(RTX_ERR_INVALID, why);
+    if (s->whole_only && !reset && part_state(c)) return bad(RTX_ERR_STATE, kPartStateWhy);
+    const bool goes_on = chain_continues(c, *s, reset);
+    if (samples > 0xffffffffu - (goes_on ? c->chain_n : 0u)) return bad(RTX_ERR_INVALID, "more than 2^32 - 1 samples in all");
+    // (a fresh or uniform state reads no halo: every err is +inf)
+    if (s->nparts > 1 && !d_halo && goes_on && c->adapt_valid)
+        return bad(RTX_ERR_INVALID, "d_halo NULL needs nparts == 1, or a fresh or uniform state");
     return RTX_OK;
 }
 // What a uniform state of `have` samples answers without its maps: every error
@@ -1371,29 +1389,40 @@ static uint32_t uniform_active(size_t px, uint32_t have, uint32_t samples, uint3
     return max_samples == 0u || (uint64_t)have + samples <= max_samples ? (uint32_t)px : 0u;
 }
 // The flags of a call over valid maps and their number (synchronous: the
-// 4-byte count comes back to the host, which sizes the launch by it).
-static int adaptive_mask(rtx_ctx *c, uint32_t samples, float threshold, uint32_t max_samples, rtx::KAdaptive *a) {
+// 4-byte count comes back to the host, which sizes the launch by it). The
+// whole frame takes k_adaptive_mask, a part k_adaptive_mask_rows with d_halo.
+static int adaptive_mask(rtx_ctx *c, const AdaptShape &s, uint32_t samples, float threshold, uint32_t max_samples,
+                         const void *d_halo, rtx::KAdaptive *a) {
     *a = adapt_maps(c);
-    hipError_t e = rtx::launch_adaptive_mask(*a, c->frame.width, c->frame.height, samples, threshold, max_samples,
-                                             c->stream);
+    hipError_t e;
+    if (s.nparts == 1)
+        e = rtx::launch_adaptive_mask(*a, c->frame.width, c->frame.height, samples, threshold, max_samples, c->stream);
+    else
+        e = rtx::launch_adaptive_mask_rows(*a, static_cast<const float *>(d_halo), c->frame.width, shape_rows(c, s),
+                                           c->frame.height, s.tile_rows, s.part, s.nparts, samples, threshold,
+                                           max_samples, c->stream);
     if (e != hipSuccess) return hip_fail(e, "launch_adaptive_mask");
     RTX_HIP(hipMemcpyAsync(&a->active, a->n_active, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     RTX_HIP(hipStreamSynchronize(c->stream));
     return RTX_OK;
 }
 
-int rtx_refine_adaptive(rtx_ctx *c, uint32_t samples, float threshold, uint32_t max_samples, int reset,
-                        uint32_t *active) {
-    int rc = adaptive_check(c, "rtx_refine_adaptive", samples, threshold, max_samples, reset);
-    if (rc) return rc;
-    const size_t px = (size_t)c->frame.width * c->frame.height;
-    const bool fresh = !chain_continues(c, reset);
+// rtx_refine_adaptive and rtx_refine_adaptive_rows (checked already).
+static int adaptive_impl(rtx_ctx *c, const AdaptShape &s, uint32_t samples, float threshold, uint32_t max_samples,
+                         int reset, const void *d_halo, void *d_out, uint32_t *active) {
+    const uint32_t rows = shape_rows(c, s);
+    if (rows == 0) {  // a part without rows: nothing to launch, the state stays
+        if (active) *active = 0;
+        return RTX_OK;
+    }
+    const size_t px = (size_t)c->frame.width * rows;
+    const bool fresh = !chain_continues(c, s, reset);
     const uint32_t have = fresh ? 0u : c->chain_n;
-    rc = set_device(c);
+    int rc = set_device(c);
     if (rc) return rc;
     rc = ensure_chain(c, px);
     if (rc) return rc;
-    if (fresh) c->chain_tile = 1, c->chain_part = 0, c->chain_nparts = 1;  // its state is a whole frame's
+    if (fresh) c->chain_tile = s.tile_rows, c->chain_part = s.part, c->chain_nparts = s.nparts;
     if (!c->d_adapt || c->adapt_pixels != px) {
         RTX_HIP(hipStreamSynchronize(c->stream));
         (void)hipFree(c->d_adapt);
@@ -1403,7 +1432,8 @@ int rtx_refine_adaptive(rtx_ctx *c, uint32_t samples, float threshold, uint32_t 
         RTX_HIP(hipMalloc(&c->d_adapt, adapt_bytes(px)));
         c->adapt_pixels = px;
     }
-    if (fresh || !c->adapt_valid) {  // a uniform state of `have` samples, no estimate yet
+    const bool uniform = fresh || !c->adapt_valid;
+    if (uniform) {  // a uniform state of `have` samples, no estimate yet
         const rtx::KAdaptive m = adapt_maps(c);
         RTX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m.count), (int)have, px, c->stream));
         RTX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m.err), 0x7f800000, px, c->stream));
@@ -1411,12 +1441,20 @@ int rtx_refine_adaptive(rtx_ctx *c, uint32_t samples, float threshold, uint32_t 
         c->adapt_mixed = false;
     }
     rtx::KAdaptive ka;
-    rc = adaptive_mask(c, samples, threshold, max_samples, &ka);
+    // (a uniform state reads no halo: a caller's buffer may hold anything then)
+    rc = adaptive_mask(c, s, samples, threshold, max_samples, uniform ? nullptr : d_halo, &ka);
     if (rc) return rc;
     if (active) *active = ka.active;
     if (ka.active == 0) {  // (never a fresh start: its errors are +inf and its counts 0)
         c->last_keys = RTX_REFINE_KEYS_UNSCHEDULED;
         return RTX_OK;
+    }
+    // a caller's d_out holds every pixel of the part after the call, whatever
+    // was in it: the pixels this call leaves alone come from the state
+    if (d_out && ka.active != px) {
+        hipError_t e = rtx::launch_chain_image_counts(c->d_chain, ka.count, ka.flags, reinterpret_cast<float4 *>(d_out),
+                                                      px, c->stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_chain_image_counts");
     }
     // keyed by the cost map wherever it is valid, whatever rtx_refine_set_keys
     // says and however few samples it covers; else every key is equal
@@ -1432,7 +1470,7 @@ int rtx_refine_adaptive(rtx_ctx *c, uint32_t samples, float threshold, uint32_t 
     a.samples = samples;
     a.out_n = 0;  // (each pixel divides by its own count)
     a.adaptive = &ka;
-    rc = render_impl(c, 1, 0, 1, nullptr, nullptr, 0, c->frame.frame_index, &a);
+    rc = render_impl(c, s.tile_rows, s.part, s.nparts, d_out, nullptr, 0, c->frame.frame_index, &a);
     if (rc != RTX_OK) return rc;
     c->chain_n = have + samples;
     c->chain_frame = c->frame;
@@ -1443,28 +1481,79 @@ int rtx_refine_adaptive(rtx_ctx *c, uint32_t samples, float threshold, uint32_t 
     return RTX_OK;
 }
 
-int rtx_refine_pending(rtx_ctx *c, uint32_t samples, float threshold, uint32_t max_samples, uint32_t *active) {
-    int rc = adaptive_check(c, "rtx_refine_pending", samples, threshold, max_samples, 0);
-    if (rc) return rc;
-    if (!active) return fail(RTX_ERR_INVALID, "rtx_refine_pending: null active");
-    const size_t px = (size_t)c->frame.width * c->frame.height;
-    const bool fresh = !chain_continues(c, 0);
-    if (fresh || !c->adapt_valid || !c->d_adapt || c->adapt_pixels != px) {
+// rtx_refine_pending and rtx_refine_pending_rows (checked already).
+static int pending_impl(rtx_ctx *c, const AdaptShape &s, uint32_t samples, float threshold, uint32_t max_samples,
+                        const void *d_halo, uint32_t *active) {
+    const size_t px = (size_t)c->frame.width * shape_rows(c, s);
+    const bool fresh = !chain_continues(c, s, 0);
+    if (px == 0 || fresh || !c->adapt_valid || !c->d_adapt || c->adapt_pixels != px) {
         *active = uniform_active(px, fresh ? 0u : c->chain_n, samples, max_samples);
         return RTX_OK;
     }
-    rc = set_device(c);
+    int rc = set_device(c);
     if (rc) return rc;
     rtx::KAdaptive ka;
-    rc = adaptive_mask(c, samples, threshold, max_samples, &ka);
+    rc = adaptive_mask(c, s, samples, threshold, max_samples, d_halo, &ka);
     if (rc) return rc;
     *active = ka.active;
     return RTX_OK;
 }
 
-// rtx_refine_counts / rtx_refine_error: map 0 / 1, or a uniform state's value.
-static int adaptive_read(rtx_ctx *c, const char *fn, int which, void *host, size_t bytes) {
-    char buf[96];
+int rtx_refine_adaptive(rtx_ctx *c, uint32_t samples, float threshold, uint32_t max_samples, int reset,
+                        uint32_t *active) {
+    AdaptShape s = kWholeFrame;
+    const int rc = adaptive_check(c, "rtx_refine_adaptive", &s, samples, threshold, max_samples, reset, nullptr, false,
+                                  nullptr);
+    if (rc) return rc;
+    return adaptive_impl(c, s, samples, threshold, max_samples, reset, nullptr, nullptr, active);
+}
+
+int rtx_refine_adaptive_rows(rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t nparts, uint32_t samples,
+                             float threshold, uint32_t max_samples, int reset, const void *d_halo, void *d_out,
+                             uint32_t *active) {
+    AdaptShape s = {tile_rows, part, nparts, false};
+    const int rc = adaptive_check(c, "rtx_refine_adaptive_rows", &s, samples, threshold, max_samples, reset, d_halo, true,
+                                  d_out);
+    if (rc) return rc;
+    return adaptive_impl(c, s, samples, threshold, max_samples, reset, d_halo, d_out, active);
+}
+
+int rtx_refine_pending(rtx_ctx *c, uint32_t samples, float threshold, uint32_t max_samples, uint32_t *active) {
+    AdaptShape s = kWholeFrame;
+    const int rc = adaptive_check(c, "rtx_refine_pending", &s, samples, threshold, max_samples, 0, nullptr, false, nullptr);
+    if (rc) return rc;
+    if (!active) return fail(RTX_ERR_INVALID, "rtx_refine_pending: null active");
+    return pending_impl(c, s, samples, threshold, max_samples, nullptr, active);
+}
+
+int rtx_refine_pending_rows(rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t nparts, uint32_t samples,
+                            float threshold, uint32_t max_samples, const void *d_halo, uint32_t *active) {
+    AdaptShape s = {tile_rows, part, nparts, false};
+    const int rc = adaptive_check(c, "rtx_refine_pending_rows", &s, samples, threshold, max_samples, 0, d_halo, false,
+                                  nullptr);
+    if (rc) return rc;
+    if (!active) return fail(RTX_ERR_INVALID, "rtx_refine_pending_rows: null active");
+    return pending_impl(c, s, samples, threshold, max_samples, d_halo, active);
+}
+
+int rtx_refine_edges(rtx_ctx *c, void *d_edges) {
+    if (!c || !d_edges) return fail(RTX_ERR_INVALID, "rtx_refine_edges: null argument");
+    if (c->chain_n == 0 || !c->d_chain) return fail(RTX_ERR_STATE, "rtx_refine_edges: no chain state");
+    int rc = set_device(c);
+    if (rc) return rc;
+    const bool maps = c->adapt_valid && c->d_adapt && c->adapt_pixels == c->chain_pixels;
+    const uint32_t width = c->chain_frame.width;  // (the state's frame: c->frame may have moved on)
+    const uint32_t rows = (uint32_t)(c->chain_pixels / width);
+    hipError_t e = rtx::launch_adaptive_edges(maps ? adapt_maps(c).err : nullptr, width, rows, c->chain_tile,
+                                              static_cast<float *>(d_edges), c->stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_adaptive_edges");
+    return RTX_OK;
+}
+
+// The four readers: map 0 / 1, or a uniform state's value. `rows`: a state of
+// any shape in its own row order; else a part state is refused.
+static int adaptive_read(rtx_ctx *c, const char *fn, int which, bool rows, void *host, size_t bytes) {
+    char buf[128];
     if (!c || !host) {
         std::snprintf(buf, sizeof buf, "%s: null argument", fn);
         return fail(RTX_ERR_INVALID, buf);
@@ -1473,9 +1562,10 @@ static int adaptive_read(rtx_ctx *c, const char *fn, int which, void *host, size
         std::snprintf(buf, sizeof buf, "%s: no chain state", fn);
         return fail(RTX_ERR_STATE, buf);
     }
-    if (part_state(c)) return fail(RTX_ERR_STATE, std::string(fn) + ": " + kPartStateWhy);
+    if (!rows && part_state(c)) return fail(RTX_ERR_STATE, std::string(fn) + ": " + kPartStateWhy);
     if (bytes != c->chain_pixels * sizeof(uint32_t)) {
-        std::snprintf(buf, sizeof buf, "%s: bytes != width*height*4", fn);
+        std::snprintf(buf, sizeof buf, rows ? "%s: bytes != the state's rows * width * 4" : "%s: bytes != width*height*4",
+                      fn);
         return fail(RTX_ERR_INVALID, buf);
     }
     if (!c->adapt_valid || !c->d_adapt || c->adapt_pixels != c->chain_pixels) {
@@ -1490,8 +1580,42 @@ static int adaptive_read(rtx_ctx *c, const char *fn, int which, void *host, size
     RTX_HIP(hipStreamSynchronize(c->stream));
     return check_errors(c, fn);
 }
-int rtx_refine_counts(rtx_ctx *c, uint32_t *host, size_t bytes) { return adaptive_read(c, "rtx_refine_counts", 0, host, bytes); }
-int rtx_refine_error(rtx_ctx *c, float *host, size_t bytes) { return adaptive_read(c, "rtx_refine_error", 1, host, bytes); }
+int rtx_refine_counts(rtx_ctx *c, uint32_t *host, size_t bytes) {
+    return adaptive_read(c, "rtx_refine_counts", 0, false, host, bytes);
+}
+int rtx_refine_error(rtx_ctx *c, float *host, size_t bytes) {
+    return adaptive_read(c, "rtx_refine_error", 1, false, host, bytes);
+}
+int rtx_refine_counts_rows(rtx_ctx *c, uint32_t *host, size_t bytes) {
+    return adaptive_read(c, "rtx_refine_counts_rows", 0, true, host, bytes);
+}
+int rtx_refine_error_rows(rtx_ctx *c, float *host, size_t bytes) {
+    return adaptive_read(c, "rtx_refine_error_rows", 1, true, host, bytes);
+}
+
+extern "C++" {
+namespace rtx {  // for rtx_group.hip (rtx_internal.h)
+const char *ctx_adaptive_refusal(const ::rtx_ctx *c, uint32_t samples) {
+    if (c->depth == 0) return "depth is 0: nothing to estimate an error from";
+    if (!cost_map_fits(samples, c->depth)) return "samples * depth does not fit 32 bits";
+    return nullptr;
+}
+int ctx_state_image(::rtx_ctx *c, void *d_out) {
+    if (!c || !d_out) return fail(RTX_ERR_INVALID, "ctx_state_image: null argument");
+    if (c->chain_n == 0 || !c->d_chain) return fail(RTX_ERR_STATE, "ctx_state_image: no chain state");
+    int rc = set_device(c);
+    if (rc) return rc;
+    float4 *out = reinterpret_cast<float4 *>(d_out);
+    hipError_t e;
+    if (c->adapt_valid && c->d_adapt && c->adapt_pixels == c->chain_pixels)
+        e = launch_chain_image_counts(c->d_chain, adapt_maps(c).count, nullptr, out, c->chain_pixels, c->stream);
+    else  // a uniform state
+        e = launch_chain_image(c->d_chain, out, c->chain_pixels, c->chain_n, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_chain_image");
+    return RTX_OK;
+}
+}  // namespace rtx
+}  // extern "C++"
 
 int rtx_deinterleave_rows(rtx_ctx *c, const void *d_gathered, uint32_t width, uint32_t height,
                           uint32_t tile_rows, uint32_t nparts, void *d_image) {

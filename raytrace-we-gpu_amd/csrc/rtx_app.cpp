@@ -217,11 +217,9 @@ bool RtxCSApp::Refine(uint32_t samples, bool reset) {
 
 bool RtxCSApp::RefineAdaptive(uint32_t samples, float threshold, uint32_t max_samples, bool reset, uint32_t *active) {
     if (!m_ok) return false;
-    if (m_group) {
-        m_error = "RefineAdaptive: one context only (adaptive refinement across a group's row parts is not supported)";
-        return m_ok = false;
-    }
-    if (rtx_refine_adaptive(m_ctx, samples, threshold, max_samples, reset ? 1 : 0, active) != RTX_OK) {
+    if ((m_group ? rtx_group_refine_adaptive(m_group, samples, threshold, max_samples, m_cfg.tile_rows, reset ? 1 : 0,
+                                             active)
+                 : rtx_refine_adaptive(m_ctx, samples, threshold, max_samples, reset ? 1 : 0, active)) != RTX_OK) {
         m_error = rtx_last_error();
         m_ok = false;
     }
@@ -260,11 +258,13 @@ bool RtxCSApp::SaveState(const std::string &path) {
     h.samples = RefinedSamples();
     h.world_hash = chain_world_hash(m_count, m_depth, m_spheres.data(), m_mat_types.data(), m_mat_values.data());
     h.frame_hash = chain_frame_hash(m_frame);
-    if (!m_group) {
+    {
         // the file holds one N for the frame: after adaptive steps (RefineAdaptive)
-        // the per-pixel counts must still be uniform (a group takes none)
+        // the per-pixel counts must still be uniform
         std::vector<uint32_t> counts((size_t)h.width * h.height);
-        if (rtx_refine_counts(m_ctx, counts.data(), counts.size() * sizeof(uint32_t)) != RTX_OK) {
+        const size_t bytes = counts.size() * sizeof(uint32_t);
+        if ((m_group ? rtx_group_refine_counts(m_group, counts.data(), bytes)
+                     : rtx_refine_counts(m_ctx, counts.data(), bytes)) != RTX_OK) {
             m_error = rtx_last_error();
             return false;
         }

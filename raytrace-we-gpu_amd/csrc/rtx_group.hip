@@ -10,6 +10,9 @@
 // launch (run_frame is the body all three share): every member keeps the chain
 // state of its own rows, and the group's checkpoint is one whole-frame state,
 // shuffled on the host by the plan header's scatter and gather.
+// rtx_group_refine_adaptive puts a phase in front of that launch: the members'
+// edge rows of the error map, exchanged by the plan header's halo plan, and
+// the members' masks.
 //
 // RCCL is loaded at run time (dlopen), so librtx.so carries no link
 // dependency on it: a single-GPU user pays nothing, and a process that has
@@ -115,6 +118,11 @@ struct Member {
     hipEvent_t ev_sum0 = nullptr, ev_sum1 = nullptr;
     bool summed = false;           // the last accumulate round launched a render for it
     nccl_comm comm = nullptr;
+    // rtx_group_refine_adaptive: its tiles' edge rows of err and its neighbours'
+    // (rtx_group_plan.h HaloPlan), the N the group expects of its chain state
+    void *d_edges = nullptr, *d_halo = nullptr;
+    hipEvent_t ev_edges = nullptr;
+    uint32_t ref_n = 0;
 };
 
 }  // namespace
@@ -152,6 +160,10 @@ struct rtx_group {
     // rtx_group_refine: the samples in the members' chain states (0: none, the
     // next call starts everyone fresh) and the tile_rows they were cut by
     uint32_t ref_n = 0, ref_tile = 0;
+    // rtx_group_refine_adaptive: some call traced a proper subset (the counts
+    // may differ), and the plan of the members' edge and halo buffers
+    bool ref_mixed = false;
+    rtx::HaloPlan hplan;
 };
 
 namespace {
@@ -189,6 +201,16 @@ void free_accum_buffers(rtx_group *g) {
     g->d_accum = g->d_sums = nullptr;
     g->aplan = rtx::AccumPlan();
     g->acc_frames = 0;
+}
+
+void free_halo_buffers(rtx_group *g) {
+    for (Member &mb : g->m) {
+        if (mb.d_edges || mb.d_halo) (void)hipSetDevice(mb.device);
+        (void)hipFree(mb.d_edges);
+        (void)hipFree(mb.d_halo);
+        mb.d_edges = mb.d_halo = nullptr;
+    }
+    g->hplan = rtx::HaloPlan();
 }
 
 void free_image(rtx_group *g) {
@@ -285,6 +307,7 @@ void destroy_group(rtx_group *g) {
         if (mb.comm) (void)g->rccl.CommDestroy(mb.comm);
     free_buffers(g);
     free_accum_buffers(g);
+    free_halo_buffers(g);
     free_image(g);
     if (!g->m.empty() && g->m[0].ctx) (void)hipSetDevice(g->m[0].device);
     for (hipEvent_t e : {g->ev_g0, g->ev_g1, g->ev_d0, g->ev_d1, g->ev_a0, g->ev_a1, g->ev_f0, g->ev_f1})
@@ -298,6 +321,7 @@ void destroy_group(rtx_group *g) {
         if (mb.ev_rendered) (void)hipEventDestroy(mb.ev_rendered);
         if (mb.ev_sum0) (void)hipEventDestroy(mb.ev_sum0);
         if (mb.ev_sum1) (void)hipEventDestroy(mb.ev_sum1);
+        if (mb.ev_edges) (void)hipEventDestroy(mb.ev_edges);
         (void)rtx_use_own_stream(mb.ctx);
         rtx_destroy(mb.ctx);
     }
@@ -445,6 +469,7 @@ int rtx_group_create(const int *devices, uint32_t n, int gather_mode, rtx_group 
         if (e == hipSuccess) e = hipEventCreate(&mb.ev_rendered);
         if (e == hipSuccess) e = hipEventCreate(&mb.ev_sum0);
         if (e == hipSuccess) e = hipEventCreate(&mb.ev_sum1);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&mb.ev_edges, hipEventDisableTiming);
         if (e != hipSuccess) rc = hip_fail(e, "rtx_group_create: hipEventCreate");
     }
     if (rc == RTX_OK) {
@@ -665,8 +690,9 @@ int refine_call_check(rtx_group *g, const char *fn, uint32_t samples, uint32_t t
     return RTX_OK;
 }
 
-// Every row-owning member's chain state is the group's: ref_n samples of part
-// i of n in tiles of ref_tile rows. Anything else means someone refined
+// Every row-owning member's chain state is the group's: the member's ref_n
+// samples (the group's, unless an adaptive step traced nothing of its rows) of
+// part i of n in tiles of ref_tile rows. Anything else means someone refined
 // through a borrowed rtx_group_ctx.
 int members_agree(rtx_group *g, const char *fn) {
     const uint32_t n = (uint32_t)g->m.size();
@@ -676,10 +702,10 @@ int members_agree(rtx_group *g, const char *fn) {
         const uint32_t have = rtx_refined_samples(g->m[i].ctx);
         const bool shaped = rtx_refine_shape(g->m[i].ctx, &t, &part, &np) == RTX_OK;
         const uint32_t want_t = n == 1 ? 1u : g->ref_tile;  // (a whole frame's shape is (1, 0, 1))
-        if (have != g->ref_n || !shaped || t != want_t || part != i || np != n)
+        if (have != g->m[i].ref_n || !shaped || t != want_t || part != i || np != n)
             return fail(RTX_ERR_STATE, std::string(fn) + ": member " + std::to_string(i) + ": its chain state (" +
                                            std::to_string(have) + " samples) is not the group's (" +
-                                           std::to_string(g->ref_n) + " samples, part " + std::to_string(i) + " of " +
+                                           std::to_string(g->m[i].ref_n) + " samples, part " + std::to_string(i) + " of " +
                                            std::to_string(n) + " in tiles of " + std::to_string(g->ref_tile) +
                                            " rows): it was refined through rtx_group_ctx; reset the group's refine");
     }
@@ -696,6 +722,9 @@ int rtx_group_refine(rtx_group *g, uint32_t samples, uint32_t tile_rows, int res
     const uint32_t have = fresh ? 0u : g->ref_n;
     if (samples > 0xffffffffu - have)
         return fail(RTX_ERR_INVALID, "rtx_group_refine: more than 2^32 - 1 samples in all");
+    if (!fresh && g->ref_mixed)
+        return fail(RTX_ERR_STATE, "rtx_group_refine: the state's per-pixel sample counts differ after adaptive steps: "
+                                   "continue with rtx_group_refine_adaptive, or reset");
     if (!fresh) {
         rc = members_agree(g, "rtx_group_refine");
         if (rc) return rc;
@@ -705,12 +734,14 @@ int rtx_group_refine(rtx_group *g, uint32_t samples, uint32_t tile_rows, int res
     // the group decides freshness and every member follows it; N counts again
     // only once every member's launch and the assembly are enqueued
     g->ref_n = 0;
+    g->ref_mixed = false;
     rc = run_frame(g, "rtx_group_refine", [&](uint32_t i, uint32_t n, void *d_out) {
         return rtx_refine_rows(g->m[i].ctx, tile_rows, i, n, samples, fresh ? 1 : 0, d_out);
     });
     if (rc != RTX_OK) return rc;
     g->ref_n = have + samples;
     g->ref_tile = tile_rows;
+    for (Member &mb : g->m) mb.ref_n = g->ref_n;
     return RTX_OK;
 }
 
@@ -771,7 +802,222 @@ int rtx_group_refine_import(rtx_group *g, uint32_t tile_rows, const float *host_
     if (rc != RTX_OK) return rc;
     g->ref_n = samples;
     g->ref_tile = tile_rows;
+    g->ref_mixed = false;  // an installed state is uniform
+    for (Member &mb : g->m) mb.ref_n = samples;
     return RTX_OK;
+}
+
+// ---- adaptive refinement across the members ----------------------------------
+namespace {
+
+// The members' edge and halo buffers for this frame and tile_rows (none for a
+// one-member group: its rule reads the local map).
+int ensure_halo_buffers(rtx_group *g, uint32_t tile_rows) {
+    const uint32_t n = (uint32_t)g->m.size();
+    if (g->hplan.same(n, g->frame.width, g->frame.height, tile_rows)) return RTX_OK;
+    int rc = drain(g);
+    if (rc) return rc;
+    free_halo_buffers(g);
+    const rtx::HaloPlan plan = rtx::make_halo_plan(n, g->frame.width, g->frame.height, tile_rows);
+    for (uint32_t i = 0; n > 1 && i < n; ++i) {
+        Member &mb = g->m[i];
+        RTXG_HIP(hipSetDevice(mb.device));
+        // a member without rows keeps (small) buffers: nothing names them
+        const size_t bytes = plan.buffer_bytes(i) ? plan.buffer_bytes(i) : sizeof(float);
+        RTXG_HIP(hipMalloc(&mb.d_edges, bytes));
+        RTXG_HIP(hipMalloc(&mb.d_halo, bytes));
+    }
+    g->hplan = plan;
+    return RTX_OK;
+}
+
+// What rtx_group_refine_adaptive and rtx_group_refine_pending decide before any HIP call.
+int adaptive_call_check(rtx_group *g, const char *fn, uint32_t samples, float threshold, uint32_t max_samples,
+                        uint32_t tile_rows) {
+    const std::string f(fn);
+    if (!g) return fail(RTX_ERR_INVALID, f + ": null group");
+    if (const char *why = rtx::adaptive_args_error(samples, threshold, max_samples)) return fail(RTX_ERR_INVALID, f + ": " + why);
+    const int rc = refine_call_check(g, fn, samples, tile_rows);
+    if (rc) return rc;
+    for (size_t i = 0; i < g->m.size(); ++i)
+        if (const char *why = rtx::ctx_adaptive_refusal(g->m[i].ctx, samples))
+            return fail(RTX_ERR_INVALID, f + ": member " + std::to_string(i) + ": " + why);
+    return RTX_OK;
+}
+
+// Phase 1: the members' edges, the exchange, the members' masks. act[i]: the
+// pixels member i would trace. A fresh call traces everything and exchanges
+// nothing (every err is +inf, and max_samples >= samples).
+int adaptive_phase1(rtx_group *g, const char *fn, uint32_t samples, float threshold, uint32_t max_samples,
+                    uint32_t tile_rows, bool fresh, std::vector<uint32_t> &act) {
+    const uint32_t n = (uint32_t)g->m.size();
+    act.assign(n, 0u);
+    if (fresh) {
+        for (uint32_t i = 0; i < n; ++i)
+            act[i] = rtx::group_part_rows(g->frame.height, tile_rows, i, n) * g->frame.width;
+        return RTX_OK;
+    }
+    int rc = members_agree(g, fn);
+    if (rc) return rc;
+    rc = ensure_halo_buffers(g, tile_rows);
+    if (rc) return rc;
+    const rtx::HaloPlan &hp = g->hplan;
+    auto member_fail = [&](int code, uint32_t i) {
+        const std::string why = rtx_last_error();
+        return fail(code, std::string(fn) + ": member " + std::to_string(i) + ": " + why);
+    };
+    if (n > 1) {
+        for (uint32_t i = 0; i < n; ++i) {
+            Member &mb = g->m[i];
+            if (hp.tiles[i] == 0) continue;
+            rc = rtx_refine_edges(mb.ctx, mb.d_edges);
+            if (rc != RTX_OK) return member_fail(rc, i);
+            RTXG_HIP(hipSetDevice(mb.device));
+            RTXG_HIP(hipEventRecord(mb.ev_edges, mb.stream));
+        }
+        if (g->mode == RTX_GATHER_COPY) {
+            // into each receiver's halo on the receiver's stream, after the sender's pack
+            for (const rtx::HaloOp &op : hp.ops) {
+                Member &src = g->m[op.src], &dst = g->m[op.dst];
+                const char *from = static_cast<const char *>(src.d_edges) + op.src_off;
+                char *to = static_cast<char *>(dst.d_halo) + op.dst_off;
+                RTXG_HIP(hipSetDevice(dst.device));
+                if (src.stream != dst.stream) RTXG_HIP(hipStreamWaitEvent(dst.stream, src.ev_edges, 0));
+                if (src.device == dst.device)
+                    RTXG_HIP(hipMemcpyAsync(to, from, op.bytes, hipMemcpyDeviceToDevice, dst.stream));
+                else
+                    RTXG_HIP(hipMemcpyPeerAsync(to, dst.device, from, src.device, op.bytes, dst.stream));
+            }
+        } else if (!hp.ops.empty()) {
+            int nrc = g->rccl.GroupStart();
+            if (nrc != 0) return nccl_fail(g, nrc, (std::string(fn) + ": ncclGroupStart").c_str());
+            for (const rtx::HaloOp &op : hp.ops) {
+                Member &src = g->m[op.src], &dst = g->m[op.dst];
+                const size_t floats = op.bytes / sizeof(float);
+                (void)hipSetDevice(src.device);
+                if (nrc == 0)
+                    nrc = g->rccl.Send(static_cast<const char *>(src.d_edges) + op.src_off, floats, kNcclFloat, (int)op.dst,
+                                       src.comm, src.stream);
+                (void)hipSetDevice(dst.device);
+                if (nrc == 0)
+                    nrc = g->rccl.Recv(static_cast<char *>(dst.d_halo) + op.dst_off, floats, kNcclFloat, (int)op.src,
+                                       dst.comm, dst.stream);
+            }
+            const int erc = g->rccl.GroupEnd();  // always closed, also after a failed call inside
+            if (nrc != 0) return nccl_fail(g, nrc, (std::string(fn) + ": ncclSend/ncclRecv").c_str());
+            if (erc != 0) return nccl_fail(g, erc, (std::string(fn) + ": ncclGroupEnd").c_str());
+        }
+    }
+    // every member's mask; its 4-byte count comes back (one small sync each)
+    for (uint32_t i = 0; i < n; ++i) {
+        Member &mb = g->m[i];
+        if (hp.tiles[i] == 0) continue;
+        rc = rtx_refine_pending_rows(mb.ctx, tile_rows, i, n, samples, threshold, max_samples, mb.d_halo, &act[i]);
+        if (rc != RTX_OK) return member_fail(rc, i);
+    }
+    return RTX_OK;
+}
+
+bool adaptive_fresh(const rtx_group *g, uint32_t tile_rows, int reset) {
+    return reset || g->ref_n == 0 || g->ref_tile != tile_rows;
+}
+
+// rtx_group_refine_counts / _error: the members' maps (which: 0 / 1) as one
+// whole-frame map, assembled on the host.
+int group_read(rtx_group *g, const char *fn, int which, void *host, size_t bytes) {
+    const std::string f(fn);
+    if (!g || !host) return fail(RTX_ERR_INVALID, f + ": null argument");
+    if (g->ref_n == 0 || !g->have_frame) return fail(RTX_ERR_STATE, f + ": no chain state");
+    const uint32_t n = (uint32_t)g->m.size();
+    const rtx::GroupPlan plan = rtx::make_group_plan(n, g->frame.width, g->frame.height, g->ref_tile);
+    if (bytes != (size_t)plan.width * plan.height * sizeof(uint32_t))
+        return fail(RTX_ERR_INVALID, f + ": bytes != width*height*4");
+    int rc = members_agree(g, fn);
+    if (rc) return rc;
+    std::vector<std::vector<uint32_t>> parts(n);
+    std::vector<const void *> ptrs(n, nullptr);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!plan.renders(i)) continue;
+        parts[i].resize((size_t)plan.rows[i] * plan.width);
+        const size_t part_bytes = parts[i].size() * sizeof(uint32_t);
+        rc = which == 0 ? rtx_refine_counts_rows(g->m[i].ctx, parts[i].data(), part_bytes)
+                        : rtx_refine_error_rows(g->m[i].ctx, reinterpret_cast<float *>(parts[i].data()), part_bytes);
+        if (rc != RTX_OK) {
+            const std::string why = rtx_last_error();
+            return fail(rc, f + ": member " + std::to_string(i) + ": " + why);
+        }
+        ptrs[i] = parts[i].data();
+    }
+    rtx::group_gather_state(plan, ptrs.data(), host, sizeof(uint32_t));
+    return RTX_OK;
+}
+
+}  // namespace
+
+int rtx_group_refine_adaptive(rtx_group *g, uint32_t samples, float threshold, uint32_t max_samples,
+                              uint32_t tile_rows, int reset, uint32_t *active) {
+    // arguments and state first: nothing in this block touches HIP
+    int rc = adaptive_call_check(g, "rtx_group_refine_adaptive", samples, threshold, max_samples, tile_rows);
+    if (rc) return rc;
+    const bool fresh = adaptive_fresh(g, tile_rows, reset);
+    const uint32_t have = fresh ? 0u : g->ref_n;
+    if (samples > 0xffffffffu - have)
+        return fail(RTX_ERR_INVALID, "rtx_group_refine_adaptive: more than 2^32 - 1 samples in all");
+    std::vector<uint32_t> act;
+    rc = adaptive_phase1(g, "rtx_group_refine_adaptive", samples, threshold, max_samples, tile_rows, fresh, act);
+    if (rc) return rc;
+    uint64_t total = 0;
+    for (uint32_t a : act) total += a;
+    if (active) *active = (uint32_t)total;
+    if (total == 0) return RTX_OK;  // nothing to trace: N, the image, the states and the maps stay
+    rc = ensure_buffers(g, tile_rows);
+    if (rc) return rc;
+    const uint32_t n = (uint32_t)g->m.size();
+    std::vector<uint32_t> member_n(n);
+    for (uint32_t i = 0; i < n; ++i) member_n[i] = fresh ? 0u : g->m[i].ref_n;
+    g->ref_n = 0;  // until every member's launch and the assembly are enqueued
+    rc = run_frame(g, "rtx_group_refine_adaptive", [&](uint32_t i, uint32_t np, void *d_out) {
+        Member &mb = g->m[i];
+        // a member with rows but nothing to trace: its slot takes its rows as they are
+        if (act[i] == 0) return rtx::ctx_state_image(mb.ctx, d_out);
+        uint32_t got = 0;
+        const int r = rtx_refine_adaptive_rows(mb.ctx, tile_rows, i, np, samples, threshold, max_samples, fresh ? 1 : 0,
+                                               mb.d_halo, d_out, &got);
+        if (r == RTX_OK && got != act[i])
+            return fail(RTX_ERR_STATE, "its mask changed between the two phases (" + std::to_string(act[i]) + " then " +
+                                           std::to_string(got) + " active pixels)");
+        if (r == RTX_OK) member_n[i] += samples;
+        return r;
+    });
+    if (rc != RTX_OK) return rc;
+    g->ref_n = have + samples;
+    g->ref_tile = tile_rows;
+    for (uint32_t i = 0; i < n; ++i) g->m[i].ref_n = member_n[i];
+    if (fresh) g->ref_mixed = false;
+    if (total != (uint64_t)g->frame.width * g->frame.height) g->ref_mixed = true;
+    return RTX_OK;
+}
+
+int rtx_group_refine_pending(rtx_group *g, uint32_t samples, float threshold, uint32_t max_samples, uint32_t tile_rows,
+                             uint32_t *active) {
+    int rc = adaptive_call_check(g, "rtx_group_refine_pending", samples, threshold, max_samples, tile_rows);
+    if (rc) return rc;
+    if (!active) return fail(RTX_ERR_INVALID, "rtx_group_refine_pending: null active");
+    std::vector<uint32_t> act;
+    rc = adaptive_phase1(g, "rtx_group_refine_pending", samples, threshold, max_samples, tile_rows,
+                         adaptive_fresh(g, tile_rows, 0), act);
+    if (rc) return rc;
+    uint64_t total = 0;
+    for (uint32_t a : act) total += a;
+    *active = (uint32_t)total;
+    return RTX_OK;
+}
+
+int rtx_group_refine_counts(rtx_group *g, uint32_t *host_counts, size_t bytes) {
+    return group_read(g, "rtx_group_refine_counts", 0, host_counts, bytes);
+}
+int rtx_group_refine_error(rtx_group *g, float *host_err, size_t bytes) {
+    return group_read(g, "rtx_group_refine_error", 1, host_err, bytes);
 }
 
 int rtx_group_get_accumulate_times(rtx_group *g, double *render_ms, double *gather_ms, double *fold_ms) {

@@ -14,7 +14,10 @@
 // group_scatter_state / group_gather_state move a chain state between one
 // whole frame and the members' parts (rtx_group_refine_import / _export),
 // executed on host memory by tests/group_refine_check.cpp too.
-// The second half of the file is the frame split (rtx_group_accumulate):
+// make_halo_plan lists the transfers of adaptive refinement's halo exchange
+// (rtx_group_refine_adaptive), executed on host memory by
+// tests/group_adaptive_check.cpp.
+// The last part of the file is the frame split (rtx_group_accumulate):
 // AccumPlan / accum_round, executed on host memory by
 // tests/group_accum_check.cpp.
 #pragma once
@@ -126,6 +129,70 @@ inline void group_gather_state(const GroupPlan &p, const void *const *parts, voi
         std::memcpy(static_cast<char *>(whole) + (size_t)y * row_bytes,
                     static_cast<const char *>(parts[m]) + (size_t)r * row_bytes, row_bytes);
     }
+}
+
+// ---- the halo exchange of adaptive refinement (rtx_group_refine_adaptive) ---
+// The activity rule reads a 3 x 3 window of err, which crosses tile edges
+// (rtx_adaptive.h adaptive_active_rows). Every member packs its tiles' first
+// and last err rows into an edge buffer [2][tiles][width] fp32 (plane 0: first
+// rows, plane 1: last rows) and receives its halo buffer, same layout (plane
+// 0: the row below each tile, plane 1: the row above). Tile k = m + j * n is
+// member m's local tile j, so the row below it is the last row of member
+// m - 1's local tile j (member n - 1's local tile j - 1 for m == 0) and the
+// row above it the first row of member m + 1's local tile j (member 0's local
+// tile j + 1 for m == n - 1): per member and direction one contiguous slab.
+// A slot whose row lies outside the image is named by no transfer.
+struct HaloOp {
+    uint32_t src, dst;        // members: from src's edge buffer into dst's halo buffer
+    size_t src_off, dst_off;  // bytes
+    size_t bytes;
+};
+
+struct HaloPlan {
+    uint32_t n = 0, width = 0, height = 0, tile_rows = 0;
+    std::vector<uint32_t> tiles;  // [n] tiles of member m (0: it owns no rows)
+    std::vector<HaloOp> ops;      // none for n == 1: the rule reads the local map
+
+    // Bytes of member m's edge buffer, and of its halo buffer.
+    size_t buffer_bytes(uint32_t m) const { return 2 * (size_t)tiles[m] * width * sizeof(float); }
+    size_t slot_off(uint32_t m, uint32_t plane, uint32_t j) const {
+        return ((size_t)plane * tiles[m] + j) * width * sizeof(float);
+    }
+    bool same(uint32_t n_, uint32_t w, uint32_t h, uint32_t t) const {
+        return n == n_ && width == w && height == h && tile_rows == t;
+    }
+};
+
+// n >= 1, tile_rows >= 1.
+inline HaloPlan make_halo_plan(uint32_t n, uint32_t width, uint32_t height, uint32_t tile_rows) {
+    HaloPlan p;
+    p.n = n;
+    p.width = width;
+    p.height = height;
+    p.tile_rows = tile_rows;
+    const uint32_t tiles = (uint32_t)(((uint64_t)height + tile_rows - 1) / tile_rows);
+    p.tiles.resize(n);
+    for (uint32_t m = 0; m < n; ++m) p.tiles[m] = m >= tiles ? 0u : (tiles - m + n - 1) / n;
+    if (n == 1) return p;
+    const size_t row = (size_t)width * sizeof(float);
+    for (uint32_t m = 0; m < n; ++m) {
+        const uint32_t tm = p.tiles[m];
+        if (tm == 0) continue;
+        // below: the last rows (plane 1) of the member before
+        if (m > 0)
+            p.ops.push_back(HaloOp{m - 1, m, p.slot_off(m - 1, 1, 0), p.slot_off(m, 0, 0), tm * row});
+        else if (tm > 1)  // (tile 0 has nothing below it)
+            p.ops.push_back(HaloOp{n - 1, 0, p.slot_off(n - 1, 1, 0), p.slot_off(0, 0, 1), (tm - 1) * row});
+        // above: the first rows (plane 0) of the member after, as far as its tiles go
+        if (m + 1 < n) {
+            if (p.tiles[m + 1] > 0)
+                p.ops.push_back(HaloOp{m + 1, m, p.slot_off(m + 1, 0, 0), p.slot_off(m, 1, 0), p.tiles[m + 1] * row});
+        } else {
+            const uint32_t cnt = tm < p.tiles[0] - 1 ? tm : p.tiles[0] - 1;
+            if (cnt > 0) p.ops.push_back(HaloOp{0, m, p.slot_off(0, 0, 1), p.slot_off(m, 1, 0), cnt * row});
+        }
+    }
+    return p;
 }
 
 // ---- progressive frames dealt across the members (rtx_group_accumulate) ----

@@ -270,6 +270,15 @@ struct KAdaptive {
 // number in *n_active (zeroed here first).
 hipError_t launch_adaptive_mask(const KAdaptive &a, uint32_t width, uint32_t rows, uint32_t samples, float threshold,
                                 uint32_t max_samples, hipStream_t stream);
+// k_adaptive_mask_rows: the same through adaptive_active_rows for a row part
+// of rows_local rows (halo: rtx_adaptive.h's layout, device; NULL: unread).
+hipError_t launch_adaptive_mask_rows(const KAdaptive &a, const float *halo, uint32_t width, uint32_t rows_local,
+                                     uint32_t height, uint32_t tile_rows, uint32_t part, uint32_t nparts,
+                                     uint32_t samples, float threshold, uint32_t max_samples, hipStream_t stream);
+// k_adaptive_edges: the first and last err row of each of a part's local tiles
+// into edges [2][ceil(rows_local / tile_rows)][width] (err NULL: +inf).
+hipError_t launch_adaptive_edges(const float *err, uint32_t width, uint32_t rows_local, uint32_t tile_rows,
+                                 float *edges, hipStream_t stream);
 // The scheduled render over the a.active flagged pixels: a carried-style
 // launch (no pre-pass, no resume state; keys from sched.cost_map when
 // sched.carry_spp != 0, else all equal), sized like a row part of a.active
@@ -289,6 +298,9 @@ hipError_t launch_fold_frames(float4 *accum, const float4 *sums, uint32_t m, siz
                               uint32_t divisor, float4 *image, hipStream_t stream);
 // k_chain_image (include/rtx.h rtx_refine_import): image[p] = toGamma(chain[p].xyz / n), w = 1.
 hipError_t launch_chain_image(const float4 *chain, float4 *image, size_t pixels, uint32_t n, hipStream_t stream);
+// k_chain_image_counts: image[p] = toGamma(chain[p].xyz / count[p]), w = 1, where skip[p] == 0 (skip NULL: everywhere).
+hipError_t launch_chain_image_counts(const float4 *chain, const uint32_t *count, const uint8_t *skip, float4 *image,
+                                     size_t pixels, hipStream_t stream);
 hipError_t launch_debug_hit_world(const KScene &s, const float *rays, uint32_t nrays,
                                   float t_min, float t_max, uint32_t start_block, float *out,
                                   hipStream_t stream);
@@ -306,5 +318,14 @@ int api_fail(int code, const char *msg);
 hipStream_t ctx_stream(const ::rtx_ctx *c);
 // Whether a world is uploaded, and its samples per pixel (the group's divisor).
 bool ctx_world_spp(const ::rtx_ctx *c, uint32_t *spp);
+// Why an adaptive step of `samples` cannot run on the context's world (depth 0,
+// or samples * depth past 32 bits), NULL if it can: rtx_refine_adaptive's
+// rules that need the world, for a group to decide before any HIP call.
+const char *ctx_adaptive_refusal(const ::rtx_ctx *c, uint32_t samples);
+// The image of the context's chain state, each pixel at its own count, into
+// d_out (the state's rows * width float4), asynchronous on its stream: what a
+// group member that traces nothing in a step puts into its slot. No launch
+// counts in the stats. RTX_ERR_STATE without a chain state.
+int ctx_state_image(::rtx_ctx *c, void *d_out);
 
 }  // namespace rtx

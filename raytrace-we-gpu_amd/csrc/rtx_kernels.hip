@@ -3204,6 +3204,40 @@ __global__ void __launch_bounds__(kBlock) k_adaptive_mask(const float *__restric
     const uint64_t b = __ballot(on);
     if (b != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(n_active, (uint32_t)__popcll(b));
 }
+// k_adaptive_mask for a row part (adaptive_active_rows): err and count are the
+// part's rows_local * width entries, halo its neighbours' edge rows
+// [2][tiles][width] (NULL: a uniform state, nothing outside a tile is read).
+__global__ void __launch_bounds__(kBlock) k_adaptive_mask_rows(const float *__restrict__ err,
+                                                               const uint32_t *__restrict__ count,
+                                                               const float *__restrict__ halo, uint32_t width,
+                                                               uint32_t rows_local, uint32_t height, uint32_t tile_rows,
+                                                               uint32_t part, uint32_t nparts, uint32_t samples,
+                                                               float threshold, uint32_t max_samples,
+                                                               uint8_t *__restrict__ flags,
+                                                               uint32_t *__restrict__ n_active) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const bool in = i < width * rows_local;
+    const bool on = in && adaptive_active_rows(err, count, halo, i, width, height, tile_rows, part, nparts, samples,
+                                               threshold, max_samples);
+    if (in) flags[i] = on ? 1u : 0u;
+    const uint64_t b = __ballot(on);
+    if (b != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(n_active, (uint32_t)__popcll(b));
+}
+// A part's edge rows of err into its edge buffer [2][tiles][width] (plane 0:
+// each local tile's first row, plane 1: its last; the last local tile may be
+// ragged), one thread per (tile, x): coalesced along x. err NULL (a uniform
+// state whose maps are not filled yet): +inf.
+__global__ void __launch_bounds__(kBlock) k_adaptive_edges(const float *__restrict__ err, uint32_t width,
+                                                           uint32_t rows_local, uint32_t tile_rows, uint32_t tiles,
+                                                           float *__restrict__ edges) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= tiles * width) return;
+    const uint32_t j = i / width, x = i - j * width;
+    const uint32_t first = j * tile_rows;
+    const uint32_t last = min(first + tile_rows, rows_local) - 1u;
+    edges[i] = err ? err[(uint64_t)first * width + x] : INFINITY;
+    edges[(uint64_t)tiles * width + i] = err ? err[(uint64_t)last * width + x] : INFINITY;
+}
 // k_carried_hist's and k_carried_scatter's siblings for an adaptive launch:
 // only flagged pixels are keyed and placed, so perm has as many entries as
 // there are flags and inv marks an unflagged pixel as having no slot (~0u).
@@ -3574,6 +3608,22 @@ __global__ void __launch_bounds__(kBlock) k_chain_image(const float4 *__restrict
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
     for (uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x; p < pixels; p += stride) {
         const float4 a = chain[p];
+        image[p] = make_float4(to_gamma(a.x / n), to_gamma(a.y / n), to_gamma(a.z / n), 1.0f);
+    }
+}
+
+// ... with a count per pixel (after adaptive steps), for the pixels a call
+// does not trace (skip[p] != 0: the launch writes that one; skip NULL: every
+// pixel): a part's d_out holds all its rows whatever was there before.
+__global__ void __launch_bounds__(kBlock) k_chain_image_counts(const float4 *__restrict__ chain,
+                                                               const uint32_t *__restrict__ count,
+                                                               const uint8_t *__restrict__ skip,
+                                                               float4 *__restrict__ image, uint64_t pixels) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x; p < pixels; p += stride) {
+        if (skip && skip[p] != 0u) continue;
+        const float4 a = chain[p];
+        const float n = (float)count[p];
         image[p] = make_float4(to_gamma(a.x / n), to_gamma(a.y / n), to_gamma(a.z / n), 1.0f);
     }
 }
@@ -4199,6 +4249,27 @@ hipError_t launch_adaptive_mask(const KAdaptive &a, uint32_t width, uint32_t row
     return hipGetLastError();
 }
 
+hipError_t launch_adaptive_mask_rows(const KAdaptive &a, const float *halo, uint32_t width, uint32_t rows_local,
+                                     uint32_t height, uint32_t tile_rows, uint32_t part, uint32_t nparts,
+                                     uint32_t samples, float threshold, uint32_t max_samples, hipStream_t stream) {
+    const uint64_t npix = (uint64_t)width * rows_local;
+    hipError_t e = hipMemsetAsync(a.n_active, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess || npix == 0) return e;
+    hipLaunchKernelGGL(k_adaptive_mask_rows, dim3(ceil_div(npix, kBlock)), dim3(kBlock), 0, stream, a.err, a.count, halo,
+                       width, rows_local, height, tile_rows, part, nparts, samples, threshold, max_samples, a.flags,
+                       a.n_active);
+    return hipGetLastError();
+}
+
+hipError_t launch_adaptive_edges(const float *err, uint32_t width, uint32_t rows_local, uint32_t tile_rows,
+                                 float *edges, hipStream_t stream) {
+    if (rows_local == 0 || width == 0) return hipSuccess;
+    const uint32_t tiles = ceil_div(rows_local, tile_rows);
+    hipLaunchKernelGGL(k_adaptive_edges, dim3(ceil_div((uint64_t)tiles * width, kBlock)), dim3(kBlock), 0, stream, err,
+                       width, rows_local, tile_rows, tiles, edges);
+    return hipGetLastError();
+}
+
 // the adaptive instance of the persistent refine render, by scene class
 static const void *adaptive_fn(const KScene &s) {
     return !use_pf(s)   ? (const void *)k_render<true, false, false, false, true, true>
@@ -4340,6 +4411,15 @@ hipError_t launch_chain_image(const float4 *chain, float4 *image, size_t pixels,
     if (pixels == 0) return hipSuccess;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)pixels - 1) / kBlock + 1, kFoldBlocks);
     hipLaunchKernelGGL(k_chain_image, dim3(blocks), dim3(kBlock), 0, stream, chain, image, (uint64_t)pixels, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_chain_image_counts(const float4 *chain, const uint32_t *count, const uint8_t *skip, float4 *image,
+                                     size_t pixels, hipStream_t stream) {
+    if (pixels == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)pixels - 1) / kBlock + 1, kFoldBlocks);
+    hipLaunchKernelGGL(k_chain_image_counts, dim3(blocks), dim3(kBlock), 0, stream, chain, count, skip, image,
+                       (uint64_t)pixels);
     return hipGetLastError();
 }
 

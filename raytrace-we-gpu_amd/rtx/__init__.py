@@ -149,6 +149,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_refine_pending": (C.c_int, [ctx, u32, C.c_float, u32, C.POINTER(u32)]),
         "rtx_refine_counts": (C.c_int, [ctx, C.POINTER(u32), C.c_size_t]),
         "rtx_refine_error": (C.c_int, [ctx, f, C.c_size_t]),
+        "rtx_refine_adaptive_rows": (C.c_int, [ctx, u32, u32, u32, u32, C.c_float, u32, C.c_int, vp, vp,
+                                               C.POINTER(u32)]),
+        "rtx_refine_pending_rows": (C.c_int, [ctx, u32, u32, u32, u32, C.c_float, u32, vp, C.POINTER(u32)]),
+        "rtx_refine_edges": (C.c_int, [ctx, vp]),
+        "rtx_refine_counts_rows": (C.c_int, [ctx, C.POINTER(u32), C.c_size_t]),
+        "rtx_refine_error_rows": (C.c_int, [ctx, f, C.c_size_t]),
         "rtx_camera_set_aperture": (C.c_int, [C.POINTER(rtx_frame), C.c_float]),
         "rtx_part_rows": (u32, [u32, u32, u32, u32]),
         "rtx_deinterleave_rows": (C.c_int, [ctx, vp, u32, u32, u32, u32, vp]),
@@ -200,6 +206,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_group_refined_samples": (u32, [vp]),
         "rtx_group_refine_export": (C.c_int, [vp, f, C.c_size_t]),
         "rtx_group_refine_import": (C.c_int, [vp, u32, f, C.c_size_t, u32]),
+        "rtx_group_refine_adaptive": (C.c_int, [vp, u32, C.c_float, u32, u32, C.c_int, C.POINTER(u32)]),
+        "rtx_group_refine_pending": (C.c_int, [vp, u32, C.c_float, u32, u32, C.POINTER(u32)]),
+        "rtx_group_refine_counts": (C.c_int, [vp, C.POINTER(u32), C.c_size_t]),
+        "rtx_group_refine_error": (C.c_int, [vp, f, C.c_size_t]),
     }
     # entry points added after 1.0 may be absent from older builds (A/B runs
     # of earlier libraries); calling one then fails with AttributeError
@@ -586,6 +596,55 @@ class Context:
         _check(self._lib.rtx_refine_error(self._h, _fptr(out), out.nbytes), "rtx_refine_error", self._lib)
         return out
 
+    def refine_adaptive_rows(self, tile_rows: int, part: int, nparts: int, samples: int, threshold: float,
+                             max_samples: int = 0, reset: bool = False, d_halo: int = 0, d_out: int = 0) -> int:
+        """refine_adaptive() for the rows of `part` of `nparts`: the state and
+        its maps cover the part's rows. d_halo: the neighbours' edge rows of
+        err, [2][tiles][W] float32 on the device (0: one part, or a fresh or
+        uniform state); d_out: device pointer for the part's rows, every one
+        of them written by a call that traces anything. Returns the number of
+        pixels traced (rtx_refine_adaptive_rows)."""
+        n = C.c_uint32(0)
+        _check(self._lib.rtx_refine_adaptive_rows(self._h, tile_rows, part, nparts, samples, threshold, max_samples,
+                                                  1 if reset else 0, C.c_void_p(d_halo or 0), C.c_void_p(d_out or 0),
+                                                  C.byref(n)), "rtx_refine_adaptive_rows", self._lib)
+        return int(n.value)
+
+    def refine_pending_rows(self, tile_rows: int, part: int, nparts: int, samples: int, threshold: float,
+                            max_samples: int = 0, d_halo: int = 0) -> int:
+        """The number of pixels refine_adaptive_rows with these arguments would
+        trace now (rtx_refine_pending_rows)."""
+        n = C.c_uint32(0)
+        _check(self._lib.rtx_refine_pending_rows(self._h, tile_rows, part, nparts, samples, threshold, max_samples,
+                                                 C.c_void_p(d_halo or 0), C.byref(n)), "rtx_refine_pending_rows",
+               self._lib)
+        return int(n.value)
+
+    def refine_edges(self, d_edges: int):
+        """The first and last err row of each of the state's tiles into
+        d_edges, [2][tiles][W] float32 on the device, asynchronously: what the
+        neighbouring parts take their halos from (rtx_refine_edges)."""
+        _check(self._lib.rtx_refine_edges(self._h, C.c_void_p(d_edges or 0)), "rtx_refine_edges", self._lib)
+
+    def _state_rows(self) -> int:
+        t, p, n = self.refine_shape()
+        return part_rows(self.frame.height, t, p, n)
+
+    def refine_counts_rows(self) -> np.ndarray:
+        """refine_counts() for a state of any shape: (rows, W) uint32 in the
+        part's row order (rtx_refine_counts_rows)."""
+        out = np.empty((self._state_rows(), self.frame.width), np.uint32)
+        _check(self._lib.rtx_refine_counts_rows(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.nbytes),
+               "rtx_refine_counts_rows", self._lib)
+        return out
+
+    def refine_error_rows(self) -> np.ndarray:
+        """refine_error() for a state of any shape: (rows, W) float32
+        (rtx_refine_error_rows)."""
+        out = np.empty((self._state_rows(), self.frame.width), np.float32)
+        _check(self._lib.rtx_refine_error_rows(self._h, _fptr(out), out.nbytes), "rtx_refine_error_rows", self._lib)
+        return out
+
     def deinterleave(self, d_gathered: int, width: int, height: int, tile_rows: int, nparts: int,
                      d_image: int):
         _check(self._lib.rtx_deinterleave_rows(self._h, C.c_void_p(d_gathered), width, height,
@@ -852,6 +911,43 @@ class Group:
         state = np.ascontiguousarray(state, np.float32)
         _check(self._lib.rtx_group_refine_import(self._h, tile_rows, _fptr(state), state.nbytes, samples),
                "rtx_group_refine_import", self._lib)
+
+    def refine_adaptive(self, samples: int, threshold: float, max_samples: int = 0, tile_rows: int = 5,
+                        reset: bool = False) -> int:
+        """Context.refine_adaptive across the members: each refines the noisy
+        pixels of its own rows after the members exchanged their tiles' edge
+        rows of the error map, so the image, counts, errors and state are those
+        of one context, bit for bit. Returns the number of pixels traced
+        (rtx_group_refine_adaptive)."""
+        n = C.c_uint32(0)
+        _check(self._lib.rtx_group_refine_adaptive(self._h, samples, threshold, max_samples, tile_rows,
+                                                   1 if reset else 0, C.byref(n)), "rtx_group_refine_adaptive",
+               self._lib)
+        return int(n.value)
+
+    def refine_pending(self, samples: int, threshold: float, max_samples: int = 0, tile_rows: int = 5) -> int:
+        """The number of pixels refine_adaptive with these arguments would
+        trace now; nothing is traced (rtx_group_refine_pending)."""
+        n = C.c_uint32(0)
+        _check(self._lib.rtx_group_refine_pending(self._h, samples, threshold, max_samples, tile_rows, C.byref(n)),
+               "rtx_group_refine_pending", self._lib)
+        return int(n.value)
+
+    def refine_counts(self) -> np.ndarray:
+        """(H, W) uint32: the samples in every pixel's sum (rtx_group_refine_counts)."""
+        f = self.frame
+        out = np.empty((f.height, f.width), np.uint32)
+        _check(self._lib.rtx_group_refine_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.nbytes),
+               "rtx_group_refine_counts", self._lib)
+        return out
+
+    def refine_error(self) -> np.ndarray:
+        """(H, W) float32: the error estimate of every pixel's last step
+        (rtx_group_refine_error)."""
+        f = self.frame
+        out = np.empty((f.height, f.width), np.float32)
+        _check(self._lib.rtx_group_refine_error(self._h, _fptr(out), out.nbytes), "rtx_group_refine_error", self._lib)
+        return out
 
     def accumulate_times(self) -> dict:
         """HIP-event times of the last round of the last accumulate(), after
