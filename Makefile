@@ -11,7 +11,7 @@ BINDIR    := $(PKG)/bin
 HIPFLAGS  := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fvisibility=hidden -ffp-contract=off -Wall -Wno-unused-function
 LIB       := $(LIBDIR)/librtx.so
 CLI       := $(BINDIR)/rtx_cli
-HDRS      := include/rtx.h $(SRC)/rtx_internal.h $(SRC)/rtx_refine_keys.h $(SRC)/rtx_adaptive.h $(SRC)/rtx_device_math.h $(SRC)/rtx_prefilter.h $(SRC)/rtx_grid.h
+HDRS      := include/rtx.h $(SRC)/rtx_internal.h $(SRC)/rtx_refine_keys.h $(SRC)/rtx_adaptive.h $(SRC)/rtx_device_math.h $(SRC)/rtx_prefilter.h $(SRC)/rtx_grid.h $(SRC)/rtx_layout.h
 # Build provenance (rtx_build_info): the library records the hash of the
 # sources it was built from; bench.py compares it with the tree's
 # (tools/src_sha.py computes the same hash).
@@ -76,6 +76,7 @@ clean:
 #   rays   - a sample of lane-mode wave iterations' rays (tools/ray_sample.py)
 # Ad-hoc A/B builds for tools/variant_bench.py:
 #   make adhoc V=name VFLAGS="-DRTX_...=..."   -> lib/variants/librtx_name.so
+#   (e.g. -DRTX_LAYOUT=0: small scenes scanned in scene order, no spatial layout)
 VARIANTS := stress prof ptime cprof rays
 VFLAGS_stress        := -DRTX_CAND=1 -DRTX_CAND_PF=1 -DRTX_GF_STEPS=1 -DRTX_PROM_VALVE_TICKS=2000000ull -DRTX_CHECK_KERNARG=1
 VFLAGS_prof          := -DRTX_DIAG_PROF=1

@@ -916,10 +916,16 @@ RTX_API int rtx_debug_hit_world(rtx_ctx *ctx, const float *rays, uint32_t nrays,
  * values only for positive roots), t_max not NaN. t_max < t_min: no ray
  * hits (no root lies in [t_min, t_max]).
  * rtx_debug_hit_world_from: the same, with the prefiltered scan starting at
- * 8-sphere block start_block % ceil(count / 8) and wrapping round — the
- * start the large-scene kernels take from their workgroup's position word
- * (DESIGN.md §3 "pack start"); the result is the in-order scan's for every
- * start (ties between spheres on either side of the wrap included).
+ * 8-sphere block start_block % (its number of blocks) and wrapping round —
+ * the start the large-scene kernels take from their workgroup's position
+ * word (DESIGN.md §3 "pack start"). The blocks are counted in whichever
+ * order the scan visits the spheres: scene order (ceil(count / 8) blocks),
+ * or, for a small world with a sphere layer, the spatial layout built at
+ * rtx_upload_world (off-layer spheres, then the layer in
+ * compact blocks, each section padded to whole blocks). The answer does not
+ * depend on it: the result is the in-order scan's for every start (ties
+ * between spheres on either side of the wrap included), and the sphere index
+ * reported is always the scene's.
  * start_block = RTX_DEBUG_CULLED: for a world of more than 1,024 spheres
  * (after padding to 8), the culled scan the render's lane mode runs on such
  * scenes (a spatially ordered copy of the spheres whose 8-sphere blocks are

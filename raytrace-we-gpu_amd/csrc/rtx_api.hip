@@ -17,6 +17,7 @@
 
 #include "../../include/rtx.h"
 #include "rtx_internal.h"
+#include "rtx_layout.h"
 #include "rtx_prefilter.h"
 
 namespace {
@@ -749,8 +750,25 @@ int rtx_upload_world(rtx_ctx *c, const rtx_world *w) {
     // the small-scene lane-mode scan's layer grid over the flat run (rtx_grid.h)
     rtx::LayerGrid grid{};
     std::vector<unsigned long long> gcell;
-    const bool has_grid = RTX_GRID_UPLOAD && !linear && n_pad <= rtx::kScanPfMin && flat_hi > flat_lo &&
-                          rtx::build_layer_grid(w->spheres, 8 * flat_lo, std::min(8 * flat_hi, n), grid, gcell);
+    // ... and its spatial layout (rtx_layout.h): the lane-mode scan's own copy
+    // of the spheres, the layer in compact blocks. It takes the culled
+    // layout's fields (cpre, cperm, n_cpad, cflat_lo: never both, a scene is
+    // small or large), and the flat run and the grid then describe its blocks.
+    rtx::SceneLayout lay;
+    if (RTX_LAYOUT && !linear && n != 0 && n_pad <= rtx::kScanPfMin) {
+        lay = rtx::build_scene_layout(w->spheres, n, rtx::kLayoutDefault, RTX_GRID_UPLOAD != 0);
+        if (lay.valid && !rtx::layout_lds_ok(n, (uint32_t)lay.perm.size())) lay = rtx::SceneLayout();
+    }
+    bool has_grid;
+    if (lay.valid) {
+        flat_lo = lay.flat_lo, flat_hi = lay.flat_hi, flat_cy = lay.flat_cy;
+        has_grid = lay.has_grid;
+        grid = lay.grid;
+        gcell.swap(lay.cell);
+    } else {
+        has_grid = RTX_GRID_UPLOAD && !linear && n_pad <= rtx::kScanPfMin && flat_hi > flat_lo &&
+                   rtx::build_layer_grid(w->spheres, 8 * flat_lo, std::min(8 * flat_hi, n), grid, gcell);
+    }
     RTX_HIP(hipStreamSynchronize(c->stream));
     free_world(c);
     const size_t cap = n ? n : 1;
@@ -792,6 +810,16 @@ int rtx_upload_world(rtx_ctx *c, const rtx_world *w) {
         RTX_HIP(hipStreamSynchronize(c->stream));
         c->n_cpad = (uint32_t)cl.perm.size();
         c->cflat_lo = cl.flat_lo;
+    }
+    if (lay.valid) {
+        RTX_HIP(hipMalloc(&c->d_cpre, lay.pre.size() * sizeof(float)));
+        RTX_HIP(hipMalloc(&c->d_cperm, lay.perm.size() * sizeof(uint32_t)));
+        RTX_HIP(hipMemcpyAsync(c->d_cpre, lay.pre.data(), lay.pre.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        RTX_HIP(hipMemcpyAsync(c->d_cperm, lay.perm.data(), lay.perm.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                               c->stream));
+        RTX_HIP(hipStreamSynchronize(c->stream));
+        c->n_cpad = (uint32_t)lay.perm.size();
+        c->cflat_lo = lay.flat_lo;
     }
     if (has_grid) {
         static_assert(sizeof(rtx::LayerGrid) % 8 == 0, "the cells follow the LayerGrid, 8-byte aligned");

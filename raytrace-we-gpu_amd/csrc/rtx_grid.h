@@ -378,4 +378,26 @@ inline bool build_layer_grid(const float *sph, uint32_t i_lo, uint32_t i_hi, Lay
     return true;
 }
 
+// Host: the same grid over the positions [p_lo, p_hi) of a layout
+// (rtx_layout.h; p_lo a multiple of 8): position p holds sphere perm[p] of
+// `sph`, and bit (p - p_lo) / 8 of a cell's mask is its block. The geometry
+// comes from the same build_layer_grid_cells; only the block numbering differs.
+template <typename Vec>
+inline bool build_layer_grid_pos(const float *sph, const uint32_t *perm, uint32_t p_lo, uint32_t p_hi, LayerGrid &G,
+                                 Vec &cell) {
+    const uint32_t m = p_hi - p_lo;
+    if (m == 0 || (m + 7) / 8 > 64) return false;
+    std::vector<float> lay(4 * (size_t)m);
+    for (uint32_t j = 0; j < m; ++j)
+        for (int k = 0; k < 4; ++k) lay[4 * (size_t)j + k] = sph[4 * (size_t)perm[p_lo + j] + k];
+    std::vector<std::pair<uint32_t, uint32_t>> hits;
+    if (!build_layer_grid_cells(lay.data(), m, kGridMaxCells, G,
+                                [&](uint32_t k, uint32_t j) { hits.emplace_back(k, j); }))
+        return false;
+    G.nblk = (m + 7) / 8;
+    cell.assign((size_t)G.nx * G.nz, 0ull);
+    for (const auto &h : hits) cell[h.first] |= 1ull << (h.second / 8);
+    return true;
+}
+
 }  // namespace rtx

@@ -55,6 +55,12 @@ struct KScene {
     //   ccen  float4[n_cpad]   cen in position order (the resolve's sphere data)
     //   cperm uint32[n_cpad]   position -> scene index (a pad: a copy with R = -inf)
     // Blocks [cflat_lo, n_cpad/8) hold only spheres at height flat_cy.
+    // Small scenes (n_pad <= kScanPfMin) with a layer keep their spatial
+    // layout (rtx_layout.h) in the same fields: cpre and cperm as above (a pad:
+    // a copy of its section's last sphere with R = -inf), n_cpad positions, the
+    // layer's blocks [cflat_lo, n_cpad/8); cbnd, cbnd2, cbnd3 and ccen are
+    // NULL. flat_lo, flat_hi, flat_cy and grid then describe the layout's
+    // blocks, which only the lane-mode scan reads (hit_world_pre_ld).
     const float *cpre;
     const float *cbnd;
     const float *cbnd2;
@@ -73,6 +79,9 @@ struct KScene {
 #endif
 #ifndef RTX_GRID  // A/B build: 0 = no layer grid (every block of the flat layer is scanned, or culled)
 #define RTX_GRID 1
+#endif
+#ifndef RTX_LAYOUT  // A/B build: 0 = no spatial layout of small scenes (the scan visits the layer in scene order)
+#define RTX_LAYOUT 1
 #endif
 #ifndef RTX_CULL_LEVELS  // bound levels above the blocks: 2 (groups, super-groups) or 3 (+ 512-block ranges)
 #define RTX_CULL_LEVELS 3
@@ -258,6 +267,10 @@ constexpr uint32_t kSchedWords = 16;
 constexpr uint32_t kBlock = 256;    // threads per block of the auxiliary kernels (4 waves)
 
 hipError_t launch_render(const KParams &p, const KSchedule &sched, hipStream_t stream);
+// Whether a small scene of n spheres can keep a layout of n_lpad positions:
+// its position map shares the render workgroup's LDS with the sphere copy and
+// must leave the kernel's 5 workgroups per CU (rtx_kernels.hip layout_lds_bytes).
+bool layout_lds_ok(uint32_t n, uint32_t n_lpad);
 // An adaptive refine launch's per-pixel maps (the context's, width * rows each).
 struct KAdaptive {
     uint8_t *flags;    // k_adaptive_mask: 1 where the call traces the pixel

@@ -674,6 +674,36 @@ __device__ __forceinline__ void resolve_one(float4 sc, int g, bool live, f3 o, f
 struct GiIdentity {
     __device__ __forceinline__ uint32_t operator()(uint32_t p) const { return p; }
 };
+// The small-scene layout (rtx_layout.h; KScene::cpre of a scene up to
+// kScanPfMin): whether scene S has one, and its position map. The map is read
+// from the workgroup's LDS copy (lds_pos_map: uint16, a scene index is below
+// 1,024) where the kernel keeps one, else from KScene::cperm. A position past
+// the layout (a lane without a candidate decodes whatever its list column
+// held) is clamped before the lookup. `on` false: the identity.
+#if RTX_LAYOUT && RTX_SCAN_LDS
+static_assert(false, "RTX_SCAN_LDS scans the LDS sphere copy, which is in scene order: build it with -DRTX_LAYOUT=0");
+#endif
+__device__ __forceinline__ bool layout_on(const KScene &S) {
+    return RTX_LAYOUT && S.cpre != nullptr && S.n_pad <= kScanPfMin;
+}
+struct MapGlobal {  // no LDS copy: KScene::cperm
+    __device__ __forceinline__ uint32_t at(const uint32_t *gmap, uint32_t p) const { return gmap[p]; }
+};
+struct MapLds {  // the workgroup's LDS copy
+    const uint16_t *m;
+    __device__ __forceinline__ uint32_t at(const uint32_t *, uint32_t p) const { return (uint32_t)m[p]; }
+};
+template <typename Map>
+struct GiLayout {
+    Map map;
+    const uint32_t *gmap;
+    uint32_t last;
+    bool on;
+    __device__ __forceinline__ uint32_t operator()(uint32_t p) const {
+        if (!on) return p;
+        return map.at(gmap, min(p, last));
+    }
+};
 // kPos: ld takes the list position (clamped to n - 1) instead of the scene
 // index (the culled layout keeps a copy of the spheres in position order, so
 // the data load and the index load are independent).
@@ -1094,13 +1124,22 @@ __device__ __forceinline__ uint64_t grid_wave_mask(const KScene &S, f3 o, f3 d, 
 // waves that trail it, instead of every wave missing on every block.
 // start (no pack word): the block to start at (rtx_debug_hit_world_from),
 // wave-uniform.
-template <bool kPF, typename Ld, bool kTile = false, bool kGridOk = true>
+template <bool kPF, typename Ld, bool kTile = false, bool kGridOk = true, typename Map = MapGlobal>
 __device__ __forceinline__ int hit_world_pre_ld(const KScene &S, Ld ld, f3 o, f3 d, float a, float inv_a,
                                                 float t_min, float &best, uint32_t *list, uint32_t *pack = nullptr,
                                                 uint32_t start = 0, const float *lds_pr = nullptr,
-                                                bool live = true) {
-    const cfloat_p pre = (cfloat_p)S.pre;
-    const uint32_t nblk = S.n_pad / 8;
+                                                bool live = true, Map map = Map()) {
+    // a small scene with a layout (rtx_layout.h): the scan reads the layout's
+    // blocks (the flat run and the grid describe them), list entries hold
+    // positions, and the resolve maps each to its scene index (map: the
+    // workgroup's LDS copy of the map, lds_pos_map, or KScene::cperm)
+    // (never in a large-scene kernel: kGridOk false is its exact fallback)
+    constexpr bool kLay = !kPF && kGridOk;
+    bool lay = false;
+    if constexpr (kLay) lay = layout_on(S);
+    const cfloat_p pre = (cfloat_p)(lay ? S.cpre : S.pre);
+    const uint32_t nblk = (lay ? S.n_cpad : S.n_pad) / 8;
+    const GiLayout<Map> gi{map, S.cperm, S.n_cpad - 1u, lay};
     RTX_DIAG_HW_BEGIN();
     LineTest T = line_test_setup(o.x, o.y, o.z, d.x, d.y, d.z, a, S.smag);
     if (!live) {  // a lane without a ray (RTX_PF_LDS: every lane fills the tile): nothing is flagged
@@ -1126,7 +1165,10 @@ __device__ __forceinline__ int hit_world_pre_ld(const KScene &S, Ld ld, f3 o, f3
         uint32_t cnt;
         b = scan_prefilter<kPF, kTile>(pre, b, end, T, S, list, cnt, pack, lds_pr, gm);
         RTX_DIAG_HW(1);
-        ok = resolve_pre_t(ld, S.n, list, cnt, o, d, a, inv_a, t_min, best, idx, cand_of<kPF>()) && ok;
+        if constexpr (!kLay)
+            ok = resolve_pre_t(ld, S.n, list, cnt, o, d, a, inv_a, t_min, best, idx, cand_of<kPF>()) && ok;
+        else
+            ok = resolve_pre_t(ld, S.n, list, cnt, o, d, a, inv_a, t_min, best, idx, cand_of<kPF>(), gi) && ok;
         RTX_DIAG_HW(2);
         if (b < end) continue;
         if (end == nblk && b0 != 0u) {  // wrap round to the start
@@ -1139,7 +1181,7 @@ __device__ __forceinline__ int hit_world_pre_ld(const KScene &S, Ld ld, f3 o, f3
     if (!ok) {
         RTX_DIAG_ADD(3, (uint32_t)__popcll(__ballot(1)));
         best = best0;
-        idx = hit_blocks_seq((cfloat_p)S.soa, nblk, 0, o, d, a, inv_a, t_min, best, -1);
+        idx = hit_blocks_seq((cfloat_p)S.soa, S.n_pad / 8, 0, o, d, a, inv_a, t_min, best, -1);
     }
     return idx;
 }
@@ -1181,6 +1223,15 @@ __host__ __device__ constexpr uint32_t coop_lds_bytes(uint32_t n) {
     return coop_npad(n) * 4u * (uint32_t)sizeof(float) + n * (uint32_t)sizeof(float);
 }
 static_assert(coop_lds_bytes(kCoopLds) <= 12800, "LDS copy of the scene: 5 render blocks per CU");
+// The layout's position map (rtx_layout.h) follows the sphere copy in the
+// render kernels' LDS: uint16 per position. Together they stay within the
+// same 12,800 bytes (layout_lds_ok: a scene they would not fit gets no
+// layout; a small scene without the sphere copy resolves from cen and maps
+// through cperm in memory).
+__host__ __device__ constexpr uint32_t layout_lds_bytes(uint32_t n_lpad) { return (2u * n_lpad + 15u) & ~15u; }
+static_assert(coop_lds_bytes(486) + layout_lds_bytes(496) <= 12800,
+              "the RTIOW world's sphere copy and position map: 5 render blocks per CU");
+static_assert(kCoopLds + 16u <= 65536u, "the LDS position map holds scene indices in 16 bits");
 
 struct SphLds {
     static constexpr bool kPadded = true;  // npairs is a multiple of 64: every group's steps stay inside
@@ -1238,6 +1289,15 @@ __device__ __forceinline__ SphLds lds_copy(const KScene &S, float *base, bool on
         }
     }
     return l;
+}
+// Build the block's LDS copy of the layout's position map (all threads of the
+// block; the caller synchronises). Unwritten, and never read, when the scene
+// has no layout.
+__device__ __forceinline__ MapLds lds_pos_map(const KScene &S, void *base, uint32_t nthreads = kRB) {
+    uint16_t *m = reinterpret_cast<uint16_t *>(base);
+    if (layout_on(S))
+        for (uint32_t p = threadIdx.x; p < S.n_cpad; p += nthreads) m[p] = (uint16_t)S.cperm[p];
+    return MapLds{m};
 }
 __device__ __forceinline__ SphGlobal sph_global(const KScene &S) {
     SphGlobal g;
@@ -2648,6 +2708,10 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
     const bool coop_lds = P.scene.n <= kCoopLds;
     const SphLds sl = lds_copy(P.scene, reinterpret_cast<float *>(s_mem + kLB + kCoopBytes), coop_lds);
     const SphGlobal sg = sph_global(P.scene);
+    // scenes with the sphere copy: the layout's position map, after it
+    // (larger small scenes resolve from cen and map through cperm)
+    const MapLds lmap = kPF || !coop_lds ? MapLds{nullptr}
+                                         : lds_pos_map(P.scene, s_mem + kLB + kCoopBytes + coop_lds_bytes(P.scene.n));
     // kPF scenes never fit the LDS copy: its place holds the scan's pack word
     uint32_t *pack = kPF ? reinterpret_cast<uint32_t *>(s_mem + kLB + kCoopBytes) : nullptr;
     const float *pf_tile = kPF && (RTX_PF_LDS || RTX_PF_RING) ? reinterpret_cast<const float *>(s_mem + kLB + kCoopBytes + 16) : nullptr;
@@ -2796,7 +2860,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
             const int hit = (!kPF && coop_lds)  // kPF scenes (> kScanPfMin) never fit
                                 ? hit_world_pre_ld<kPF>(P.scene, [sl](uint32_t i) { return sl.sphere(i); }, L.o, L.d,
                                                         L.a, L.inv_a, kTMin, best, list, nullptr, 0,
-                                                        RTX_SCAN_LDS ? sl.pr : nullptr)
+                                                        RTX_SCAN_LDS ? sl.pr : nullptr, true, lmap)
                                 : hit_world_pre<kPF>(P.scene, L.o, L.d, L.a, L.inv_a, kTMin, best, list, pack);
             D.section(1);
             promoted = shade<kCost, kRefine, kAdapt>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
@@ -3476,6 +3540,9 @@ __global__ void RTX_PS_BOUNDS_T(kPF) k_render_ps(const KParams P) {
     uint32_t *st = reinterpret_cast<uint32_t *>(s_mem + kLB + kCoopBytes) + (threadIdx.x / 64) * kPsSlots * 4;
     const bool sph_lds = !kPF && P.scene.n <= kCoopLds;
     const SphLds sl = lds_copy(P.scene, reinterpret_cast<float *>(s_mem + kLB + kCoopBytes + kPsStateBytes), sph_lds);
+    const MapLds lmap = !sph_lds ? MapLds{nullptr}
+                                 : lds_pos_map(P.scene, s_mem + kLB + kCoopBytes + kPsStateBytes +
+                                                            coop_lds_bytes(P.scene.n));
     const SphGlobal sg = sph_global(P.scene);
     const uint32_t lane = threadIdx.x & 63u;
     if (lane < kPsSlots * 4) st[lane] = 0u;
@@ -3550,7 +3617,7 @@ __global__ void RTX_PS_BOUNDS_T(kPF) k_render_ps(const KParams P) {
         } else if (L.active) {  // (the SGPR scan: the LDS tile measured slower here)
             hit = kCulled ? hit_world_culled(P.scene, L.o, L.d, L.a, L.inv_a, kTMin, best, list)
                   : sph_lds ? hit_world_pre_ld<kPF>(P.scene, [sl](uint32_t i) { return sl.sphere(i); }, L.o, L.d, L.a,
-                                                    L.inv_a, kTMin, best, list)
+                                                    L.inv_a, kTMin, best, list, nullptr, 0, nullptr, true, lmap)
                             : hit_world_pre<kPF>(P.scene, L.o, L.d, L.a, L.inv_a, kTMin, best, list);
         }
         if (L.active) {
@@ -3759,7 +3826,7 @@ __global__ void __launch_bounds__(kRB) k_debug_hit_world(const KScene S, const f
     const float inv_a = 1.0f / a;
     float best = t_max;
     const int idx =
-        min((start == kDebugCulled && S.cpre)
+        min((start == kDebugCulled && S.cpre && S.n_pad > kScanPfMin)  // (a small scene's cpre is its layout)
                 ? hit_world_culled(S, o, d, a, inv_a, t_min, best, list)
             : S.n_pad > kScanPfMin ? hit_world_pre<true>(S, o, d, a, inv_a, t_min, best, list, nullptr, start)
                                    : hit_world_pre<false>(S, o, d, a, inv_a, t_min, best, list, nullptr, start),
@@ -3816,6 +3883,7 @@ __global__ void RTX_RENDER_BOUNDS k_debug_scan_rate(const KParams P, uint32_t re
     extern __shared__ __attribute__((aligned(16))) unsigned char s_mem[];
     uint32_t *list = reinterpret_cast<uint32_t *>(s_mem);
     const SphLds sl = lds_copy(P.scene, reinterpret_cast<float *>(s_mem + kListBytes + kCoopBytes), true);
+    const MapLds lmap = lds_pos_map(P.scene, s_mem + kListBytes + kCoopBytes + coop_lds_bytes(P.scene.n));
     __syncthreads();
     const uint32_t npix = P.rows_local * P.width;
     const uint32_t gid = blockIdx.x * kRB + threadIdx.x;
@@ -3831,7 +3899,8 @@ __global__ void RTX_RENDER_BOUNDS k_debug_scan_rate(const KParams P, uint32_t re
     for (uint32_t r = 0; r < reps; ++r) {
         float best = __uint_as_float(0x7f800000u);
         const int hit = hit_world_pre_ld<false>(P.scene, [sl](uint32_t i) { return sl.sphere(i); }, o, d, a, inv_a,
-                                                kTMin, best, list, nullptr, 0, RTX_SCAN_LDS ? sl.pr : nullptr);
+                                                kTMin, best, list, nullptr, 0, RTX_SCAN_LDS ? sl.pr : nullptr, true,
+                                                lmap);
         acc += (uint32_t)hit ^ __float_as_uint(best);
     }
 #pragma unroll
@@ -3950,9 +4019,16 @@ static void launch_kr(const KScene &s, uint32_t blocks, size_t lds, hipStream_t 
 
 // Dynamic LDS of the chain-RNG kernels: candidate lists + coop ray slots +
 // the block's copy of the spheres for scenes up to kCoopLds.
+// ... and a small scene's position map (lds_pos_map)
+static size_t scene_map_lds(const KScene &s) {
+    return RTX_LAYOUT && s.n <= kCoopLds && s.cpre != nullptr ? (size_t)layout_lds_bytes(s.n_cpad) : 0;
+}
+bool layout_lds_ok(uint32_t n, uint32_t n_lpad) {
+    return n > kCoopLds || coop_lds_bytes(n) + layout_lds_bytes(n_lpad) <= 12800u;
+}
 static size_t render_lds(const KScene &s) {
     return (use_pf(s) ? list_bytes<true>() + 16 + (use_lin(s) ? kPfLdsBytes : 0u) : kListBytes) + kCoopBytes +  // kPF: the pack word (and the tile scan's tile)
-           (s.n <= kCoopLds ? (size_t)coop_lds_bytes(s.n) : 0);
+           (s.n <= kCoopLds ? (size_t)coop_lds_bytes(s.n) : 0) + scene_map_lds(s);
 }
 
 hipError_t launch_cost(const KParams &p, hipStream_t stream) {
@@ -3977,7 +4053,7 @@ constexpr uint32_t kPsItems = RTX_PS_ITEMS;
 constexpr uint32_t kPsBatchesPerWave = RTX_PS_BPW;
 static size_t ps_lds(const KScene &s) {
     return (use_pf(s) ? list_bytes<true>() : kListBytes) + kCoopBytes + kPsStateBytes +
-           (!use_pf(s) && s.n <= kCoopLds ? (size_t)coop_lds_bytes(s.n) : 0);
+           (!use_pf(s) && s.n <= kCoopLds ? (size_t)coop_lds_bytes(s.n) : 0) + scene_map_lds(s);
 }
 static const void *ps_fn(const KScene &s) {
     return !use_pf(s)   ? (const void *)k_render_ps<false>
@@ -4428,7 +4504,7 @@ hipError_t launch_debug_hit_world(const KScene &s, const float *rays, uint32_t n
     if (nrays == 0) return hipSuccess;
     const uint32_t q = start_block & 0xffu;
     const uint32_t sel = start_block & ~0xffu;
-    if ((sel == kDebugCulledCoop || sel == kDebugCulledCoopLane) && q >= 1u && q <= 64u && s.cpre) {
+    if ((sel == kDebugCulledCoop || sel == kDebugCulledCoopLane) && q >= 1u && q <= 64u && s.cpre && use_pf(s)) {
         const uint32_t waves = ceil_div(nrays, q);
         if (sel == kDebugCulledCoop)
             hipLaunchKernelGGL(k_debug_hit_world_coop<true>, dim3(ceil_div(waves, kRB / 64u)), dim3(kRB), 0, stream, s,
@@ -4450,7 +4526,7 @@ bool debug_scan_rate_supported(const KParams &p) {
 hipError_t launch_debug_scan_rate(const KParams &p, uint32_t reps, unsigned long long *sink, uint32_t *waves,
                                   hipStream_t stream) {
     if (!debug_scan_rate_supported(p)) return hipErrorInvalidValue;
-    const size_t lds = kListBytes + kCoopBytes + (size_t)coop_lds_bytes(p.scene.n);
+    const size_t lds = kListBytes + kCoopBytes + (size_t)coop_lds_bytes(p.scene.n) + scene_map_lds(p.scene);
     const uint32_t blocks = resident_blocks((const void *)k_debug_scan_rate, lds);
     *waves = blocks * (kRB / 64);
     hipLaunchKernelGGL(k_debug_scan_rate, dim3(blocks), dim3(kRB), lds, stream, p, reps, sink);
