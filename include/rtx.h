@@ -40,6 +40,8 @@ extern "C" {
 
 #define RTX_VERSION 145 /* 1.4.5 */
 /* ABI notes.
+ *  1.4.5 (later builds, no version bump): rtx_debug_scene_info (what
+ *         rtx_upload_world built; dlsym "rtx_debug_scene_info").
  *  1.4.5 (later builds, no version bump): rtx_refine_adaptive_rows,
  *         rtx_refine_pending_rows, rtx_refine_edges, rtx_refine_counts_rows and
  *         rtx_refine_error_rows (adaptive refinement of a row part on a
@@ -980,6 +982,24 @@ RTX_API int rtx_debug_pixel_cost(rtx_ctx *ctx, uint32_t spp, uint32_t *host_cost
  * ceiling for the render's hit_world section. Scenes up to 640 spheres (the
  * render's LDS-copy scenes); needs a world and a frame. Synchronous. */
 RTX_API int rtx_debug_scan_rate(rtx_ctx *ctx, uint32_t reps, float *ms, unsigned long long *wave_segments);
+/* What rtx_upload_world built for the uploaded world, and which kernels and
+ * scan path the launches will take for it (1.4.5, later builds, no version
+ * bump: probe with dlsym "rtx_debug_scene_info"): the context's fields and
+ * the predicates the launches themselves use, so a test can assert the path
+ * a scene takes. Launches nothing, touches no device memory.
+ * RTX_ERR_STATE without a world; RTX_ERR_INVALID for a null argument. */
+typedef struct rtx_scene_info {
+    uint32_t count, n_pad;        /* spheres, padded to 8 */
+    uint32_t kernels;             /* 0 small (n_pad <= 1024), 1 large culled, 2 large linear */
+    uint32_t sphere_copy_lds;     /* the render keeps the LDS sphere copy (count <= 640) */
+    uint32_t layout;              /* a small-scene layout is uploaded */
+    uint32_t layout_positions;    /* its padded position count, else 0 */
+    uint32_t map_in_lds;          /* the render reads the position map from LDS */
+    uint32_t flat_lo, flat_hi;    /* blocks of the flat run the scan uses (positions when layout) */
+    uint32_t grid, grid_nx, grid_nz; /* a layer grid is uploaded, its size */
+    uint32_t reserved[4];
+} rtx_scene_info;
+RTX_API int rtx_debug_scene_info(rtx_ctx *ctx, rtx_scene_info *out);
 
 #ifdef __cplusplus
 }

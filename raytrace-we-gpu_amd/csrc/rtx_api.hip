@@ -90,6 +90,7 @@ struct rtx_ctx {
     // layer grid of the flat run (small scenes; rtx_grid.h; none: null):
     // its LayerGrid, then the cells' block masks
     rtx::LayerGrid *d_grid = nullptr;
+    uint32_t grid_nx = 0, grid_nz = 0;  // its size, for rtx_debug_scene_info (0: none)
     int scan_mode = RTX_SCAN_AUTO;  // rtx_set_scan_mode: applied by rtx_upload_world
     float4 *d_cen = nullptr;
     int *d_mtype = nullptr;
@@ -225,6 +226,7 @@ void free_world(rtx_ctx *c) {
     (void)hipFree(c->d_ccen);
     (void)hipFree(c->d_grid);
     c->d_grid = nullptr;
+    c->grid_nx = c->grid_nz = 0;
     c->d_cpre = c->d_cbnd = c->d_cbnd2 = c->d_cbnd3 = nullptr;
     c->d_cperm = nullptr;
     c->d_ccen = nullptr;
@@ -830,6 +832,8 @@ int rtx_upload_world(rtx_ctx *c, const rtx_world *w) {
         RTX_HIP(hipMemcpyAsync(c->d_grid, buf.data(), buf.size() * sizeof(unsigned long long), hipMemcpyHostToDevice,
                                c->stream));
         RTX_HIP(hipStreamSynchronize(c->stream));
+        c->grid_nx = grid.nx;
+        c->grid_nz = grid.nz;
     }
     if (c->n != n) c->n_changed = true;
     c->n = n;
@@ -842,6 +846,29 @@ int rtx_upload_world(rtx_ctx *c, const rtx_world *w) {
     c->spp = w->spp;
     c->have_world = true;
     c->chain_n = 0;  // a chain state belongs to the world it was traced in
+    return RTX_OK;
+}
+
+// What the upload above built and what the launches will take for it: the
+// context's fields and rtx::scene_kernels, no launch.
+int rtx_debug_scene_info(rtx_ctx *c, rtx_scene_info *out) {
+    if (!c || !out) return fail(RTX_ERR_INVALID, "rtx_debug_scene_info: null argument");
+    if (!c->have_world) return fail(RTX_ERR_STATE, "rtx_debug_scene_info: no world uploaded");
+    const rtx::KScene s = scene_of(c);
+    const rtx::SceneKernels k = rtx::scene_kernels(s);
+    std::memset(out, 0, sizeof *out);
+    out->count = s.n;
+    out->n_pad = s.n_pad;
+    out->kernels = k.kernels;
+    out->sphere_copy_lds = k.sphere_copy_lds;
+    out->layout = k.kernels == 0 && s.cpre != nullptr;  // a small scene holds only a layout in these fields
+    out->layout_positions = out->layout ? s.n_cpad : 0;
+    out->map_in_lds = k.map_in_lds;
+    out->flat_lo = s.flat_lo;
+    out->flat_hi = s.flat_hi;
+    out->grid = s.grid != nullptr;
+    out->grid_nx = c->grid_nx;
+    out->grid_nz = c->grid_nz;
     return RTX_OK;
 }
 

@@ -271,6 +271,15 @@ hipError_t launch_render(const KParams &p, const KSchedule &sched, hipStream_t s
 // its position map shares the render workgroup's LDS with the sphere copy and
 // must leave the kernel's 5 workgroups per CU (rtx_kernels.hip layout_lds_bytes).
 bool layout_lds_ok(uint32_t n, uint32_t n_lpad);
+// What the launches decide from a scene, by the predicates they use themselves
+// (rtx_kernels.hip use_pf, use_lin, kCoopLds, scene_map_lds): for
+// rtx_debug_scene_info, which launches nothing.
+struct SceneKernels {
+    uint32_t kernels;      // 0 small (n_pad <= kScanPfMin), 1 large culled, 2 large linear
+    bool sphere_copy_lds;  // the render keeps the LDS copy of the spheres
+    bool map_in_lds;       // ... and reads a layout's position map from LDS (lds_pos_map)
+};
+SceneKernels scene_kernels(const KScene &s);
 // An adaptive refine launch's per-pixel maps (the context's, width * rows each).
 struct KAdaptive {
     uint8_t *flags;    // k_adaptive_mask: 1 where the call traces the pixel

@@ -4026,6 +4026,14 @@ static size_t scene_map_lds(const KScene &s) {
 bool layout_lds_ok(uint32_t n, uint32_t n_lpad) {
     return n > kCoopLds || coop_lds_bytes(n) + layout_lds_bytes(n_lpad) <= 12800u;
 }
+// What the launches above decide from a scene (rtx_debug_scene_info).
+SceneKernels scene_kernels(const KScene &s) {
+    SceneKernels k;
+    k.kernels = !use_pf(s) ? 0u : use_lin(s) ? 2u : 1u;
+    k.sphere_copy_lds = !use_pf(s) && s.n <= kCoopLds;
+    k.map_in_lds = scene_map_lds(s) != 0;
+    return k;
+}
 static size_t render_lds(const KScene &s) {
     return (use_pf(s) ? list_bytes<true>() + 16 + (use_lin(s) ? kPfLdsBytes : 0u) : kListBytes) + kCoopBytes +  // kPF: the pack word (and the tile scan's tile)
            (s.n <= kCoopLds ? (size_t)coop_lds_bytes(s.n) : 0) + scene_map_lds(s);

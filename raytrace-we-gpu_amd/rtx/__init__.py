@@ -100,6 +100,15 @@ class rtx_stats(C.Structure):
                 ("segments", C.c_uint64), ("sphere_tests", C.c_uint64)]
 
 
+class rtx_scene_info(C.Structure):
+    """What rtx_upload_world built (include/rtx.h rtx_scene_info)."""
+    _fields_ = [("count", C.c_uint32), ("n_pad", C.c_uint32), ("kernels", C.c_uint32),
+                ("sphere_copy_lds", C.c_uint32), ("layout", C.c_uint32), ("layout_positions", C.c_uint32),
+                ("map_in_lds", C.c_uint32), ("flat_lo", C.c_uint32), ("flat_hi", C.c_uint32),
+                ("grid", C.c_uint32), ("grid_nx", C.c_uint32), ("grid_nz", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
 _lib = None
 
 
@@ -184,6 +193,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_debug_wave_times": (C.c_int, [ctx, C.c_size_t, C.POINTER(C.c_uint64)]),
         "rtx_debug_pixel_cost": (C.c_int, [ctx, u32, C.POINTER(C.c_uint32)]),
         "rtx_debug_scan_rate": (C.c_int, [ctx, u32, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
+        "rtx_debug_scene_info": (C.c_int, [ctx, C.POINTER(rtx_scene_info)]),
         "rtx_group_create": (C.c_int, [C.POINTER(C.c_int), u32, C.c_int, C.POINTER(C.c_void_p)]),
         "rtx_group_destroy": (None, [vp]),
         "rtx_group_size": (u32, [vp]),
@@ -214,7 +224,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     # entry points added after 1.0 may be absent from older builds (A/B runs
     # of earlier libraries); calling one then fails with AttributeError
     optional = {"rtx_schedule_defaults", "rtx_set_schedule", "rtx_get_schedule", "rtx_debug_hit_world_from",
-                "rtx_build_info", "rtx_debug_scan_rate", "rtx_set_scan_mode"}
+                "rtx_build_info", "rtx_debug_scan_rate", "rtx_set_scan_mode", "rtx_debug_scene_info"}
     optional |= {n for n in sig if n.startswith("rtx_group_")}  # arrived without a version bump
     optional |= {"rtx_render_sum", "rtx_fold_frames"}            # ... with rtx_group_accumulate
     optional |= {n for n in sig if n.startswith("rtx_refine")}   # ... probe "rtx_refine"
@@ -713,6 +723,15 @@ class Context:
                                                       start_block, _fptr(out)), "rtx_debug_hit_world_from",
                    self._lib)
         return out
+
+    def scene_info(self) -> dict:
+        """What upload_world built and which path the launches take for it
+        (rtx_debug_scene_info): count, n_pad, kernels (0 small, 1 large culled,
+        2 large linear), sphere_copy_lds, layout, layout_positions, map_in_lds,
+        flat_lo, flat_hi, grid, grid_nx, grid_nz. Nothing is launched."""
+        info = rtx_scene_info()
+        _check(self._lib.rtx_debug_scene_info(self._h, C.byref(info)), "rtx_debug_scene_info", self._lib)
+        return {name: int(getattr(info, name)) for name, _ in rtx_scene_info._fields_ if name != "reserved"}
 
     def arm_wave_times(self, max_waves: int):
         _check(self._lib.rtx_debug_wave_times(self._h, max_waves, None), "rtx_debug_wave_times", self._lib)

@@ -58,6 +58,8 @@ def test_version_and_error_paths(rtx):
     assert lib.rtx_render_rows(None, 1, 0, 1, None) == -1
     assert lib.rtx_sync(None) == -1
     assert lib.rtx_get_stats(None, None) == -1
+    assert lib.rtx_debug_scene_info(None, None) == -1
+    assert b"rtx_debug_scene_info" in lib.rtx_last_error()
     f = rtx.rtx_frame()
     assert lib.rtx_camera_look_at(None, None, None, 20.0, 1.0, 0.0, 0.0, 4, 4, C.byref(f)) == -1
 
@@ -137,7 +139,7 @@ def test_ctypes_mirror_matches_header_layout(rtx, tmp_path):
     silently shift the mirror."""
     import rtx as R
     structs = {"rtx_world": R.rtx_world, "rtx_frame": R.rtx_frame, "rtx_schedule": R.rtx_schedule,
-               "rtx_stats": R.rtx_stats}
+               "rtx_stats": R.rtx_stats, "rtx_scene_info": R.rtx_scene_info}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "rtx.h"', 'int main(void) {']
     for name, cls in structs.items():
         lines.append(f'  printf("{name} size %zu\\n", sizeof({name}));')
