@@ -76,7 +76,9 @@ clean:
 #   rays   - a sample of lane-mode wave iterations' rays (tools/ray_sample.py)
 # Ad-hoc A/B builds for tools/variant_bench.py:
 #   make adhoc V=name VFLAGS="-DRTX_...=..."   -> lib/variants/librtx_name.so
-#   (e.g. -DRTX_LAYOUT=0: small scenes scanned in scene order, no spatial layout)
+#   (e.g. -DRTX_LAYOUT=0: small scenes scanned in scene order, no spatial layout;
+#    -DRTX_FINISH_IN_LOOP=1: staged pixels divided and gamma-mapped by the
+#    render lane that ends them, not by k_unpermute)
 VARIANTS := stress prof ptime cprof rays
 VFLAGS_stress        := -DRTX_CAND=1 -DRTX_CAND_PF=1 -DRTX_GF_STEPS=1 -DRTX_PROM_VALVE_TICKS=2000000ull -DRTX_CHECK_KERNARG=1
 VFLAGS_prof          := -DRTX_DIAG_PROF=1

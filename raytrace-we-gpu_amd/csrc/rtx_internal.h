@@ -133,7 +133,7 @@ constexpr uint32_t kErrDiagWords = 1;
 struct KParams {
     KScene scene;
     float4 *out;                   // part's rows, contiguous, row-major
-    float4 *out_slot;              // cost-ordered render: the image by queue slot (k_unpermute), or NULL
+    float4 *out_slot;              // cost-ordered render: the pixels' linear sums by queue slot (k_unpermute finishes them), or NULL
     uint32_t stage_tag;            // ... the launch's tag in a staged pixel's w (k_unpermute moves only those)
     unsigned long long *counters;  // [0] += ray segments (hit_world calls)
     uint32_t *queue;               // pixel queue head (zeroed before each launch)
@@ -240,7 +240,7 @@ struct KSchedule {
     uint32_t *cost;     // [npix]
     uint32_t *perm;     // [npix]
     float4 *state;      // [npix] (acc.xyz, seed) after the pre-pass's samples
-    float4 *stage;      // [npix] the render's image by queue slot (NULL: written in place)
+    float4 *stage;      // [npix] the render's linear sums by queue slot, the launch's tag in w (NULL: written in place)
     uint32_t *inv;      // [npix] pixel -> queue slot (k_cost_scatter; k_unpermute)
     uint32_t *buckets;  // [2 * nbuckets + kSchedWords]: counts, cursors, heavy[8], prom[8] (zeroed per launch)
     uint32_t npix;      // capacity of cost / perm

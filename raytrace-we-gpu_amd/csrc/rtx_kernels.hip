@@ -1755,10 +1755,17 @@ __device__ __forceinline__ void begin_sample(const KParams &P, const Frame &F, u
 // cost-ordered render with a slot-ordered staging image (KParams::out_slot):
 // the pixel goes to out_slot[slot] and k_unpermute moves it to out[gid] with
 // coalesced stores; ~0u (or no staging): straight to out[gid].
+// A staged pixel is staged as its linear sum: the divide and the gamma run
+// once per pixel for one lane of a wave here, and for 64 lanes per instruction
+// in k_unpermute, which has the launch's divisor (finish_staged). A pixel
+// without a slot (no staging image, or a promoted pixel) is finished here.
 // kRefine (the refine launch's kernel instances, KParams::chain_in): the
 // divisor is the chain's samples so far (out_n), not this launch's.
 // kAdapt (the adaptive refine launch's instances): the pixel's own count
 // after the launch, n_new.
+#ifndef RTX_FINISH_IN_LOOP  // A/B: 1 = a staged pixel is finished here too, and k_unpermute only moves it
+#define RTX_FINISH_IN_LOOP 0
+#endif
 template <bool kRefine = false, bool kAdapt = false>
 __device__ __forceinline__ void output_pixel(const KParams &P, uint32_t gid, f3 sum, uint32_t slot = ~0u,
                                              uint32_t n_new = 0u) {
@@ -1771,6 +1778,11 @@ __device__ __forceinline__ void output_pixel(const KParams &P, uint32_t gid, f3 
         P.accum[gid] = a;
         sum = mk3(a.x, a.y, a.z);
         n = (float)(P.accum_frames * P.spp);
+    }
+    if (!RTX_FINISH_IN_LOOP && P.out_slot && slot != ~0u) {
+        // this launch's staged pixel: the tag in w, k_unpermute divides by n (stage_divisor; kAdapt: count[gid])
+        P.out_slot[slot] = make_float4(sum.x, sum.y, sum.z, __uint_as_float(P.stage_tag));
+        return;
     }
     float4 o;
     o.x = to_gamma(sum.x / n);
@@ -3767,24 +3779,42 @@ __global__ void __launch_bounds__(kBlock) k_fold_frames(float4 *__restrict__ acc
 // KParams::stage_tag): a promoted pixel (stage w = 0) was written to out[i] by
 // whoever finished it, and a slot a launch left unwritten (the valve fired:
 // RTX_ERR_INCOMPLETE) keeps out[i] as it was, never another frame's pixel.
+// A staged pixel is its linear sum (output_pixel): the rest of
+// accColor /= n; toGamma; float4(c, 1) happens here, one pixel per lane, on
+// the same fp32 inputs with the same operations. n is the divisor
+// output_pixel would have used (stage_divisor).
+__device__ __forceinline__ float4 finish_staged(float4 v, uint32_t divisor) {
+    if (RTX_FINISH_IN_LOOP) return make_float4(v.x, v.y, v.z, 1.0f);
+    const float n = (float)divisor;
+    return make_float4(to_gamma(v.x / n), to_gamma(v.y / n), to_gamma(v.z / n), 1.0f);
+}
 __global__ void __launch_bounds__(kBlock) k_unpermute(const float4 *__restrict__ stage, const uint32_t *__restrict__ inv,
-                                                      uint32_t npix, uint32_t tag, float4 *__restrict__ out) {
+                                                      uint32_t npix, uint32_t tag, uint32_t divisor,
+                                                      float4 *__restrict__ out) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= npix) return;
     const float4 v = stage[inv[i]];
-    if (__float_as_uint(v.w) == tag) out[i] = make_float4(v.x, v.y, v.z, 1.0f);
+    if (__float_as_uint(v.w) == tag) out[i] = finish_staged(v, divisor);
 }
 // ... after an adaptive launch: a pixel without a slot (inv ~0u: inactive)
-// keeps its framebuffer value.
+// keeps its framebuffer value; a staged one divides by its own count after
+// the launch (write_pixel<kAdapt> stored it, in pixel order).
 __global__ void __launch_bounds__(kBlock) k_unpermute_adaptive(const float4 *__restrict__ stage,
-                                                               const uint32_t *__restrict__ inv, uint32_t npix,
+                                                               const uint32_t *__restrict__ inv,
+                                                               const uint32_t *__restrict__ count, uint32_t npix,
                                                                uint32_t tag, float4 *__restrict__ out) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= npix) return;
     const uint32_t g = inv[i];
     if (g == ~0u) return;
     const float4 v = stage[g];
-    if (__float_as_uint(v.w) == tag) out[i] = make_float4(v.x, v.y, v.z, 1.0f);
+    if (__float_as_uint(v.w) == tag) out[i] = finish_staged(v, count[i]);
+}
+// The divisor of a launch's staged pixels, as output_pixel picks it: the
+// accumulator's samples for a progressive frame, the chain's for a refine
+// launch (the kRefine instances: chain_out set), else the launch's own.
+static uint32_t stage_divisor(const KParams &q) {
+    return q.accum ? q.accum_frames * q.spp : q.chain_out ? q.out_n : q.spp;
 }
 
 // One hit record of rtx_debug_hit_world (include/rtx.h): hit, t, p, normal,
@@ -4316,7 +4346,7 @@ hipError_t launch_render(const KParams &p_in, const KSchedule &sched, hipStream_
     if (e == hipSuccess && trace_waves > 0) e = hipStreamWaitEvent(stream, sched.ev_join, 0);
     if (e == hipSuccess && sched.stage) {
         hipLaunchKernelGGL(k_unpermute, dim3(ceil_div(lanes, kBlock)), dim3(kBlock), 0, stream, sched.stage, sched.inv,
-                           (uint32_t)lanes, q.stage_tag, p.out);
+                           (uint32_t)lanes, q.stage_tag, stage_divisor(q), p.out);
         e = hipGetLastError();
     }
     return e;
@@ -4466,7 +4496,7 @@ hipError_t launch_render_adaptive(const KParams &p_in, const KSchedule &sched, c
     if (e == hipSuccess && trace_waves > 0) e = hipStreamWaitEvent(stream, sched.ev_join, 0);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_unpermute_adaptive, dim3(ceil_div(image, kBlock)), dim3(kBlock), 0, stream, sched.stage,
-                           sched.inv, (uint32_t)image, q.stage_tag, p.out);
+                           sched.inv, a.count, (uint32_t)image, q.stage_tag, p.out);
         e = hipGetLastError();
     }
     return e;
