@@ -79,6 +79,8 @@ clean:
 #   (e.g. -DRTX_LAYOUT=0: small scenes scanned in scene order, no spatial layout;
 #    -DRTX_FINISH_IN_LOOP=1: staged pixels divided and gamma-mapped by the
 #    render lane that ends them, not by k_unpermute)
+#   (the switches of decided experiments are retired: DESIGN.md §7 lists them,
+#    tools/build_commit_variant.sh builds one from the last commit that has it)
 VARIANTS := stress prof ptime cprof rays
 VFLAGS_stress        := -DRTX_CAND=1 -DRTX_CAND_PF=1 -DRTX_GF_STEPS=1 -DRTX_PROM_VALVE_TICKS=2000000ull -DRTX_CHECK_KERNARG=1
 VFLAGS_prof          := -DRTX_DIAG_PROF=1

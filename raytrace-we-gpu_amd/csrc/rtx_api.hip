@@ -61,13 +61,6 @@ constexpr size_t kCounterWords = kErrDiag + rtx::kErrDiagWords;
 
 }  // namespace
 
-#ifndef RTX_FLAT
-#define RTX_FLAT 1
-#endif
-#ifndef RTX_GRID_UPLOAD  // A/B build: 0 = no layer grid (every block of the flat run is scanned)
-#define RTX_GRID_UPLOAD 1
-#endif
-
 struct rtx_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -723,7 +716,7 @@ int rtx_upload_world(rtx_ctx *c, const rtx_world *w) {
                 if (bits(b, k) != bits(b, 0)) return false;
             return true;
         };
-        const uint32_t nblk = RTX_FLAT ? n_pad / 8 : 0;  // RTX_FLAT=0: A/B build without flat runs
+        const uint32_t nblk = n_pad / 8;
         for (uint32_t b = 0; b < nblk;) {
             if (!flat(b)) {
                 ++b;
@@ -747,7 +740,7 @@ int rtx_upload_world(rtx_ctx *c, const rtx_world *w) {
     }
     CullLayout cl;
     const bool linear = c->scan_mode == RTX_SCAN_LINEAR;  // every block of every segment: no grid, no culled copy
-    const bool cull = RTX_CULL && !linear && n_pad > rtx::kScanPfMin;  // the large-scene (kPF) kernels scan it
+    const bool cull = !linear && n_pad > rtx::kScanPfMin;  // the large-scene (kPF) kernels scan it
     if (cull) cl = build_cull(w, pre4, flat_hi > flat_lo, flat_cy);
     // the small-scene lane-mode scan's layer grid over the flat run (rtx_grid.h)
     rtx::LayerGrid grid{};
@@ -758,7 +751,7 @@ int rtx_upload_world(rtx_ctx *c, const rtx_world *w) {
     // small or large), and the flat run and the grid then describe its blocks.
     rtx::SceneLayout lay;
     if (RTX_LAYOUT && !linear && n != 0 && n_pad <= rtx::kScanPfMin) {
-        lay = rtx::build_scene_layout(w->spheres, n, rtx::kLayoutDefault, RTX_GRID_UPLOAD != 0);
+        lay = rtx::build_scene_layout(w->spheres, n, rtx::kLayoutDefault);
         if (lay.valid && !rtx::layout_lds_ok(n, (uint32_t)lay.perm.size())) lay = rtx::SceneLayout();
     }
     bool has_grid;
@@ -768,7 +761,7 @@ int rtx_upload_world(rtx_ctx *c, const rtx_world *w) {
         grid = lay.grid;
         gcell.swap(lay.cell);
     } else {
-        has_grid = RTX_GRID_UPLOAD && !linear && n_pad <= rtx::kScanPfMin && flat_hi > flat_lo &&
+        has_grid = !linear && n_pad <= rtx::kScanPfMin && flat_hi > flat_lo &&
                    rtx::build_layer_grid(w->spheres, 8 * flat_lo, std::min(8 * flat_hi, n), grid, gcell);
     }
     RTX_HIP(hipStreamSynchronize(c->stream));

@@ -74,30 +74,14 @@ struct KScene {
     const LayerGrid *grid;
 };
 
-#ifndef RTX_CULL  // A/B build: 0 = no culled layout (the large-scene lane-mode scan visits every block)
-#define RTX_CULL 1
-#endif
-#ifndef RTX_GRID  // A/B build: 0 = no layer grid (every block of the flat layer is scanned, or culled)
-#define RTX_GRID 1
-#endif
 #ifndef RTX_LAYOUT  // A/B build: 0 = no spatial layout of small scenes (the scan visits the layer in scene order)
 #define RTX_LAYOUT 1
 #endif
-#ifndef RTX_CULL_LEVELS  // bound levels above the blocks: 2 (groups, super-groups) or 3 (+ 512-block ranges)
-#define RTX_CULL_LEVELS 3
-#endif
-// the flat section of the culled layout starts at a multiple of this many
-// blocks: no bound test (8 entries) mixes flat and non-flat bounds
-constexpr uint32_t kCullAlign = RTX_CULL_LEVELS >= 3 ? 512u : 64u;
-#ifndef RTX_CULL_HALF  // culled scan: a bound wholly behind the origin fails too (rtx_prefilter.h HalfTest)
-#define RTX_CULL_HALF 1
-#endif
-#ifndef RTX_CULL_HALF_SPHERES  // 1: also drop a flagged sphere wholly behind it (measured slower: R9s)
-#define RTX_CULL_HALF_SPHERES 0
-#endif
-#ifndef RTX_CULL_BFS  // the one-ray culled coop walks the levels breadth first (0: each lane its subtree)
-#define RTX_CULL_BFS 1
-#endif
+// The culled layout has three bound levels above the blocks (groups,
+// super-groups, 512-block ranges; two levels: 187.5 vs 128.8 ms, RESULTS R9zb),
+// and its flat section starts at a multiple of this many blocks: no bound test
+// (8 entries) mixes flat and non-flat bounds
+constexpr uint32_t kCullAlign = 512u;
 #ifndef RTX_SCAN_PF_MIN  // (A/B builds: 0 sends every scene to the kPF kernels)
 #define RTX_SCAN_PF_MIN 1024
 #endif

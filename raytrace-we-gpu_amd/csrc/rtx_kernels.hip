@@ -189,27 +189,22 @@ constexpr uint32_t kRB = 256;           // threads per render workgroup
                               // dwords to scratch) sit in per-segment and coop code, none in the scan loop
 #endif
 #define RTX_RENDER_BOUNDS __launch_bounds__(kRB, RTX_WAVES_PER_SIMD)
-// The large-scene chain kernels (kPF). With the full scan (RTX_CULL=0: lists
-// of RTX_CAND_PF entries and a 1-KiB scan tile per wave, ~34 KB of LDS per
-// workgroup) 4 workgroups fit a CU's 160 KB of LDS, i.e. 4 waves per SIMD:
-// compiled for 5 they spilled 134 VGPRs for occupancy they never got, for 4
-// they had 128. The culled scan (no tile) is latency-bound and its two line
-// bases (the stretched one for flat bounds) spill 63 VGPRs at 128: compiled
-// for 3 waves (166 VGPRs, no spills) the C5 frame is 2.5 % faster than at 4
-// and writes no spill lines (R8u).
+// The large-scene chain kernels (kPF). The culled scan (no tile) is
+// latency-bound and its two line bases (the stretched one for flat bounds)
+// spill 63 VGPRs at 128: compiled for 3 waves (166 VGPRs, no spills) the C5
+// frame is 2.5 % faster than at 4 and writes no spill lines (R8u).
 #ifndef RTX_WAVES_PER_SIMD_PF
-#define RTX_WAVES_PER_SIMD_PF (RTX_CULL ? 3 : 4)
+#define RTX_WAVES_PER_SIMD_PF 3
 #endif
 #define RTX_RENDER_BOUNDS_T(kPF) __launch_bounds__(kRB, (kPF) ? RTX_WAVES_PER_SIMD_PF : RTX_WAVES_PER_SIMD)
 // kLin (the linear-scan mode, rtx_set_scan_mode: a large scene without the
-// culled layout scans every block through the per-wave LDS tile): 4 waves per
-// SIMD, what its LDS allows
+// culled layout scans every block through the per-wave LDS tile): lists of
+// RTX_CAND_PF entries and a 1-KiB scan tile per wave, ~34 KB of LDS per
+// workgroup, so 4 workgroups fit a CU's 160 KB of LDS, i.e. 4 waves per SIMD
+// (compiled for 5 it spilled 134 VGPRs for occupancy it never got; for 4 it
+// has 128)
 #define RTX_RENDER_BOUNDS_T2(kPF, kLin) \
     __launch_bounds__(kRB, (kPF) ? ((kLin) ? 4 : RTX_WAVES_PER_SIMD_PF) : RTX_WAVES_PER_SIMD)
-#ifndef RTX_PS_WAVES_PF  // the per-sample kernel's large-scene instance (A/B: 4 = 128 VGPRs)
-#define RTX_PS_WAVES_PF RTX_WAVES_PER_SIMD
-#endif
-#define RTX_PS_BOUNDS_T(kPF) __launch_bounds__(kRB, (kPF) ? RTX_PS_WAVES_PF : RTX_WAVES_PER_SIMD)
 
 // Candidate list: per lane kCand slots in LDS, slot-major
 // (slot j of lane t at [j * kRB + t]: conflict-free), plus one dump slot
@@ -318,9 +313,6 @@ __device__ __forceinline__ f2v fma2(f2v a, f2v b, f2v c) { return __builtin_elem
 // Scalar loads return out of order, so the wait is lgkmcnt(0); it names the
 // loaded registers ("+s") so that nothing reads them before it. Every path
 // out of the loop body passes a wait, so no load is in flight at exit.
-#ifndef RTX_PACK  // kPF scans start where the workgroup's other waves are (hit_world_pre_ld)
-#define RTX_PACK 1
-#endif
 #ifndef RTX_PACK_EVERY
 #define RTX_PACK_EVERY 16
 #endif
@@ -342,37 +334,21 @@ __device__ __forceinline__ void sload_blk(cfloat_p p, f16v &lo, f16v &hi, f2v &d
 __device__ __forceinline__ void sload_wait(f16v &lo, f16v &hi) {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(lo), "+s"(hi));
 }
+// The large-scene lane-mode scan (kTile) streams the scene through a per-wave
+// LDS tile of RTX_PF_LDS KiB: C5 1,880-1,907 -> 1,811-1,847 ms against the
+// SGPR double buffer (profiles/R3w_*, R3x_*). (The tile stream as a ring of
+// LDS-DMA slots: no gain, DESIGN.md §3c. The small-scene scan reading the
+// block's LDS sphere copy instead of scalar loads: DESIGN.md §7.)
+#ifndef RTX_PF_LDS
+#define RTX_PF_LDS 1
+#endif
+constexpr uint32_t kPfSlots = RTX_PF_LDS;  // the tile: kPfSlots KiB, 8 * kPfSlots blocks
+static_assert(kPfSlots >= 1, "the large-scene lane-mode scan has no path without its LDS tile");
+constexpr uint32_t kPfLdsBytes = (kRB / 64) * 64 * 16 * kPfSlots;  // kPfSlots KiB per wave
 // One run of blocks [b, end), all flat (kFlat: the 5-op test, k0/k1 = the
 // per-ray ku/kv of rtx_prefilter.h line_test_flat) or not (the 7-op test,
 // k0/k1 = nou/nov). Returns the block to resume at; `full` when it stopped
-// because some lane's list is full.
-#ifndef RTX_PF_LDS  // large scenes stream through a per-wave LDS tile of RTX_PF_LDS KiB (below; 0: SGPR double buffer)
-#define RTX_PF_LDS 1  // C5 1,880-1,907 -> 1,811-1,847 ms (profiles/R3w_*, R3x_*)
-#endif
-#ifndef RTX_PF_RING  // A/B: the tile stream as a ring of RTX_PF_RING 1-KiB slots filled by LDS-DMA (0: VGPR staging)
-#define RTX_PF_RING 0
-#endif
-constexpr uint32_t kPfSlots = RTX_PF_RING > RTX_PF_LDS ? RTX_PF_RING : RTX_PF_LDS;
-constexpr uint32_t kPfLdsBytes = (kRB / 64) * 64 * 16 * kPfSlots;  // kPfSlots KiB per wave
-// LDS-DMA (global_load_lds_dwordx4): lane l's 16 bytes at gsrc land at LDS byte
-// address lds_base + 16 l (wave-uniform base, in M0). An asm load is outside
-// the compiler's s_waitcnt bookkeeping: the caller counts it with vmcnt. The
-// lgkmcnt(0) first: the slot's earlier ds_reads have returned before it is
-// overwritten.
-__device__ __forceinline__ uint32_t lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
-__device__ __forceinline__ void glds16(const void *gsrc, uint32_t lds_base) {
-    unsigned keep;
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds_base)
-                 : "memory");
-}
-#ifndef RTX_SCAN_LDS  // A/B build: the small-scene scan reads its blocks from the block's LDS copy
-#define RTX_SCAN_LDS 0  // (broadcast ds_read_b128, 8 per block) instead of scalar loads
-#endif
+// because some lane's list is full. lds_pr: the kTile scan's LDS tiles.
 template <bool kPF, bool kFlat, bool kTile = false>
 __device__ __forceinline__ uint32_t scan_range(cfloat_p pre, uint32_t b, uint32_t end, const LineTest &T,
                                                float k0, float k1, uint32_t *my, uint32_t &cnt, bool &full,
@@ -433,80 +409,33 @@ __device__ __forceinline__ uint32_t scan_range(cfloat_p pre, uint32_t b, uint32_
     // kTile (k_render's large-scene lane mode, which passes its tile): the
     // tile stream is the only scan instantiated there, so the SGPR ping-pong
     // below (64 SGPRs) does not crowd that kernel's registers
-    if (kTile && kPF && RTX_PF_RING && lds_pr != nullptr) {
-        // A/B build: the scene streams through a ring of
-        // kNR 1-KiB slots (8 blocks each) per wave, filled by LDS-DMA with no
-        // VGPR staging: kNR - 1 tiles in flight while one is scanned. Before
-        // tile j is scanned, tile j + kNR - 1 is issued into the slot tile
-        // j - 1 used, and vmcnt(kNR - 1) retires tile j (vector-memory
-        // operations complete in issue order). Tiles past `end` re-read the
-        // last block (a constant count of loads in flight); a scan that stops
-        // for a full list leaves its loads in flight (the next scan's counted
-        // waits cover them: they are older), one that reaches `end` drains.
-        // Every lane of the wave runs this (the DMA writes one 16-byte piece
-        // per lane).
-        constexpr uint32_t kNR = RTX_PF_RING ? RTX_PF_RING : 2u;  // (the branch is dead when 0)
-        static_assert(kNR >= 2 && kNR <= 8, "ring of 2..8 slots");
-        float4 *ring = const_cast<float4 *>(reinterpret_cast<const float4 *>(lds_pr)) +
-                       64u * kNR * ((threadIdx.x & 255u) >> 6);
-        const uint32_t rbase = (uint32_t)__builtin_amdgcn_readfirstlane(lds_addr(ring));
-        const float4 *gp = (const float4 *)(const float *)pre;
-        const uint32_t lane = threadIdx.x & 63u;
-        auto issue = [&](uint32_t tb, uint32_t slot) {
-            glds16(gp + 8u * min(tb + (lane >> 3), end - 1u) + (lane & 7u), rbase + 1024u * slot);
-        };
-        uint32_t tb = b - b % 8u;
-#pragma unroll
-        for (uint32_t k = 0; k + 1 < kNR; ++k) issue(tb + 8u * k, k);
-        for (uint32_t j = 0;; ++j) {
-            issue(tb + 8u * (kNR - 1u), (j + kNR - 1u) % kNR);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kNR - 1u) : "memory");
-            const float4 *q0 = ring + 64u * (j % kNR);
-            const uint32_t e = min(tb + 8u, end);
-            for (; b < e; ++b) {
-                const float4 *q = q0 + 8u * (b - tb);
-                float4 v[8];
-#pragma unroll
-                for (int t = 0; t < 8; ++t) v[t] = q[t];
-                auto blk = [&](int i) {
-                    const float4 w = v[i >> 2];
-                    const int c = i & 3;
-                    return c == 0 ? w.x : c == 1 ? w.y : c == 2 ? w.z : w.w;
-                };
-                if (step(blk, b)) return b + 1;
-            }
-            if (tb + 8u >= end) break;
-            tb += 8u;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else if (kTile && kPF && RTX_PF_LDS && lds_pr != nullptr) {
-        // A/B build: the scene streams through a per-wave
-        // LDS tile of 8 * RTX_PF_LDS blocks (RTX_PF_LDS KiB: coalesced 16-byte
-        // loads, one per lane per KiB, the next tile's loads in flight while
-        // this one is scanned), and each block is read from it with 8
-        // broadcast ds_read_b128 into VGPRs. Every lane of the wave runs this
-        // (hit_world_pre_ld's `live`).
-        constexpr uint32_t kT = 8u * RTX_PF_LDS;  // blocks per tile
+    if (kTile && kPF && lds_pr != nullptr) {
+        // The scene streams through a per-wave LDS tile of 8 * kPfSlots
+        // blocks (kPfSlots KiB: coalesced 16-byte loads, one per lane per KiB,
+        // the next tile's loads in flight while this one is scanned), and each
+        // block is read from it with 8 broadcast ds_read_b128 into VGPRs.
+        // Every lane of the wave runs this (hit_world_pre_ld's `live`).
+        constexpr uint32_t kT = 8u * kPfSlots;  // blocks per tile
         float4 *tl = const_cast<float4 *>(reinterpret_cast<const float4 *>(lds_pr)) +
-                     64u * RTX_PF_LDS * ((threadIdx.x & 255u) >> 6);
+                     64u * kPfSlots * ((threadIdx.x & 255u) >> 6);
         const float4 *gp = (const float4 *)(const float *)pre;
         const uint32_t lane = threadIdx.x & 63u;
         auto fetch = [&](uint32_t tb, uint32_t k) {
             return gp[8u * min(tb + 8u * k + (lane >> 3), end - 1u) + (lane & 7u)];
         };
         uint32_t tb = b - b % kT;
-        float4 cur[RTX_PF_LDS ? RTX_PF_LDS : 1];
+        float4 cur[kPfSlots];
 #pragma unroll
-        for (uint32_t k = 0; k < RTX_PF_LDS; ++k) cur[k] = fetch(tb, k);
+        for (uint32_t k = 0; k < kPfSlots; ++k) cur[k] = fetch(tb, k);
         for (;;) {
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
-            for (uint32_t k = 0; k < RTX_PF_LDS; ++k) tl[64u * k + lane] = cur[k];
+            for (uint32_t k = 0; k < kPfSlots; ++k) tl[64u * k + lane] = cur[k];
             __builtin_amdgcn_wave_barrier();
             const bool more = tb + kT < end;
             if (more) {
 #pragma unroll
-                for (uint32_t k = 0; k < RTX_PF_LDS; ++k) cur[k] = fetch(tb + kT, k);
+                for (uint32_t k = 0; k < kPfSlots; ++k) cur[k] = fetch(tb + kT, k);
             }
             const uint32_t e = min(tb + kT, end);
             for (; b < e; ++b) {
@@ -544,45 +473,29 @@ __device__ __forceinline__ uint32_t scan_range(cfloat_p pre, uint32_t b, uint32_
             // the wrapped leg of a segment. Publishing from both halves (every
             // scan) measured no faster than no pack at all, this 4-7 % faster
             // (DESIGN.md §7 R4k-q).
-            if (kPF && RTX_PACK && pack && (b & (kPackEvery - 1u)) == 0u && (threadIdx.x & 63u) == 0u) *pack = b;
+            if (kPF && pack && (b & (kPackEvery - 1u)) == 0u && (threadIdx.x & 63u) == 0u) *pack = b;
             sload_blk(pre + 32 * min(b + 1, end - 1), a_lo, a_hi, ux, uy, uz, vy, vz, ku, kv);
             f = step([&](int i) { return i < 16 ? b_lo[i] : b_hi[i - 16]; }, b);
             sload_wait(a_lo, a_hi);
             if (f) return b + 1;
             if (++b >= end) break;
         }
+    } else if (bmask != ~0ull) {
+        // the layer grid's blocks (hit_world_pre_ld: bit j = block bm_lo + j,
+        // wave-uniform; end <= bm_lo + 64): the set ones, in order
+        while (b < end) {
+            const uint64_t r = bmask & (~0ull << (b - bm_lo));
+            if (r == 0ull) break;
+            b = bm_lo + (uint32_t)__builtin_ctzll(r);
+            if (b >= end) break;
+            const cfloat_p blk = pre + 32 * b;
+            if (step([&](int i) { return blk[i]; }, b)) return b + 1;
+            ++b;
+        }
     } else {
-        if (RTX_SCAN_LDS && lds_pr) {
-            for (; b < end; ++b) {  // pair p of block b: [cx0 cx1 cy0 cy1 cz0 cz1 R0 R1] (SphLds)
-                const float4 *q = reinterpret_cast<const float4 *>(lds_pr + 32u * b);
-                float4 v[8];
-#pragma unroll
-                for (int t = 0; t < 8; ++t) v[t] = q[t];
-                auto blk = [&](int i) {  // AoSoA-8 float i of the block
-                    const int c = i >> 3, sp = i & 7, pp = sp >> 1, w = sp & 1;
-                    const float4 A = v[2 * pp], B = v[2 * pp + 1];
-                    const float a = w ? A.y : A.x, bb = w ? A.w : A.z, cc = w ? B.y : B.x, dd = w ? B.w : B.z;
-                    return c == 0 ? a : c == 1 ? bb : c == 2 ? cc : dd;
-                };
-                if (step(blk, b)) return b + 1;
-            }
-        } else if (bmask != ~0ull) {
-            // the layer grid's blocks (hit_world_pre_ld: bit j = block bm_lo + j,
-            // wave-uniform; end <= bm_lo + 64): the set ones, in order
-            while (b < end) {
-                const uint64_t r = bmask & (~0ull << (b - bm_lo));
-                if (r == 0ull) break;
-                b = bm_lo + (uint32_t)__builtin_ctzll(r);
-                if (b >= end) break;
-                const cfloat_p blk = pre + 32 * b;
-                if (step([&](int i) { return blk[i]; }, b)) return b + 1;
-                ++b;
-            }
-        } else {
-            for (; b < end; ++b) {
-                const cfloat_p blk = pre + 32 * b;
-                if (step([&](int i) { return blk[i]; }, b)) return b + 1;
-            }
+        for (; b < end; ++b) {
+            const cfloat_p blk = pre + 32 * b;
+            if (step([&](int i) { return blk[i]; }, b)) return b + 1;
         }
     }
     full = false;
@@ -680,9 +593,6 @@ struct GiIdentity {
 // 1,024) where the kernel keeps one, else from KScene::cperm. A position past
 // the layout (a lane without a candidate decodes whatever its list column
 // held) is clamped before the lookup. `on` false: the identity.
-#if RTX_LAYOUT && RTX_SCAN_LDS
-static_assert(false, "RTX_SCAN_LDS scans the LDS sphere copy, which is in scene order: build it with -DRTX_LAYOUT=0");
-#endif
 __device__ __forceinline__ bool layout_on(const KScene &S) {
     return RTX_LAYOUT && S.cpre != nullptr && S.n_pad <= kScanPfMin;
 }
@@ -792,8 +702,7 @@ __device__ __forceinline__ uint32_t scan_culled(const KScene &S, uint32_t b, con
     const float thr_b = T.thr * kCullThrScale;
     const f2v hdx = {H.dx, H.dx}, hdy = {H.dy, H.dy}, hdz = {H.dz, H.dz}, hnod = {H.nod, H.nod};
     const f2v ha = {H.a, H.a}, htha = {H.tha, H.tha};
-    const float kws1 = half_test_kw(Hs, kCullSy * S.flat_cy), kwf1 = half_test_kw(H, S.flat_cy);
-    const f2v kwf = {kwf1, kwf1};
+    const float kws1 = half_test_kw(Hs, kCullSy * S.flat_cy);
     const f2v kws = {kws1, kws1}, has = {Hs.a, Hs.a}, hthas = {Hs.tha, Hs.tha};
     // Q of the 4 pairs of an AoSoA-8 block of spheres or bounds (blk(i): its i-th float)
     auto quad = [&](auto flat, auto blk, f2v *q) {
@@ -837,28 +746,9 @@ __device__ __forceinline__ uint32_t scan_culled(const KScene &S, uint32_t b, con
                 inv = (inv << 1) | (__float_as_uint(sq.y) >> 31);
                 inv = (inv << 1) | (__float_as_uint(sq.x) >> 31);
             }
-            // the flagged spheres wholly behind the lane's origin drop out
-            // (the half test per sphere; only for blocks some lane flags)
-            uint32_t hm = 0xffu;
-            if (RTX_CULL_HALF_SPHERES) {
-                hm = 0u;
-#pragma unroll
-                for (int p = 3; p >= 0; --p) {
-                    const f2v cx = {v[2 * p], v[2 * p + 1]}, cz = {v[16 + 2 * p], v[17 + 2 * p]};
-                    const f2v R = {v[24 + 2 * p], v[25 + 2 * p]};
-                    f2v pw;
-                    if constexpr (decltype(flat)::value) {
-                        pw = fma2(cx, hdx, fma2(cz, hdz, kwf));
-                    } else {
-                        const f2v cy = {v[8 + 2 * p], v[9 + 2 * p]};
-                        pw = fma2(cx, hdx, fma2(cy, hdy, fma2(cz, hdz, hnod)));
-                    }
-                    const f2v q2 = fma2(-pw, pw, fma2(R, ha, htha));
-                    hm = (hm << 1) | (half_test_pass(pw.y, q2.y) ? 1u : 0u);
-                    hm = (hm << 1) | (half_test_pass(pw.x, q2.x) ? 1u : 0u);
-                }
-            }
-            const uint32_t mask = ~inv & hm & 0xffu;
+            // (also dropping the flagged spheres wholly behind the lane's
+            // origin, the half test per sphere: slower, RESULTS R9s)
+            const uint32_t mask = ~inv & 0xffu;
             my[cnt * kRB] = (8u * bb) | (mask << 24);
             cnt += mask != 0u ? 1u : 0u;
             return __ballot(cnt == cand_of<true>()) != 0ull;
@@ -906,8 +796,8 @@ __device__ __forceinline__ uint32_t scan_culled(const KScene &S, uint32_t b, con
         uint32_t m = 0;
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            const bool px = !(q[p].x < thr) && (!RTX_CULL_HALF || half_test_pass(pw[p].x, q2[p].x));
-            const bool py = !(q[p].y < thr) && (!RTX_CULL_HALF || half_test_pass(pw[p].y, q2[p].y));
+            const bool px = !(q[p].x < thr) && half_test_pass(pw[p].x, q2[p].x);
+            const bool py = !(q[p].y < thr) && half_test_pass(pw[p].y, q2[p].y);
             m |= (__ballot(px) != 0ull ? 1u : 0u) << (2 * p);
             m |= (__ballot(py) != 0ull ? 1u : 0u) << (2 * p + 1);
         }
@@ -926,8 +816,7 @@ __device__ __forceinline__ uint32_t scan_culled(const KScene &S, uint32_t b, con
     // the super-groups, groups and blocks before b.
     const uint32_t ng = (nblk + 7u) / 8u, nsg = (ng + 7u) / 8u, nhg = (nsg + 7u) / 8u;
     for (uint32_t hg = b >> 9; hg < nhg; ++hg) {
-        uint32_t m3 = first_bits(nsg - 8u * hg);
-        if (RTX_CULL_LEVELS >= 3) m3 &= bound_mask((cfloat_p)S.cbnd3 + 32u * hg, 512u * hg);
+        uint32_t m3 = first_bits(nsg - 8u * hg) & bound_mask((cfloat_p)S.cbnd3 + 32u * hg, 512u * hg);
         if (hg == (b >> 9)) m3 &= 0xffu << ((b >> 6) & 7u);
         while (m3 != 0u) {
             const uint32_t sg = 8u * hg + (uint32_t)__builtin_ctz(m3);
@@ -1115,7 +1004,7 @@ __device__ __forceinline__ uint64_t grid_wave_mask(const KScene &S, f3 o, f3 d, 
 // hit_blocks_seq.
 // `ld(i)` returns (center, radius) of sphere i for the resolve (cen in HBM,
 // or, for scenes up to kCoopLds spheres, the block's LDS copy of them).
-// pack (kPF kernels, RTX_PACK): the workgroup's LDS word holding the block a
+// pack (kPF kernels): the workgroup's LDS word holding the block a
 // wave of it scanned last (published every kPackEvery blocks). A segment's
 // scan starts kPackLag blocks behind it and wraps round — [b0, nblk) then
 // [0, b0): the resolution rule is order-independent, so any start gives the
@@ -1142,21 +1031,21 @@ __device__ __forceinline__ int hit_world_pre_ld(const KScene &S, Ld ld, f3 o, f3
     const GiLayout<Map> gi{map, S.cperm, S.n_cpad - 1u, lay};
     RTX_DIAG_HW_BEGIN();
     LineTest T = line_test_setup(o.x, o.y, o.z, d.x, d.y, d.z, a, S.smag);
-    if (!live) {  // a lane without a ray (RTX_PF_LDS: every lane fills the tile): nothing is flagged
+    if (!live) {  // a lane without a ray (every lane fills the scan's LDS tile): nothing is flagged
         T.ux = T.uy = T.uz = T.vy = T.vz = T.nou = T.nov = 0.0f;
         T.thr = __uint_as_float(0x7f800000u);
     }
     // the layer grid (small scenes, rtx_grid.h): the flat run's blocks some lane of the wave needs
     uint64_t gm = ~0ull;
     if constexpr (!kPF && kGridOk) {
-        if (RTX_GRID && S.grid != nullptr) gm = grid_wave_mask(S, o, d, T, list, list + cand_of<kPF>() * kRB);
+        if (S.grid != nullptr) gm = grid_wave_mask(S, o, d, T, list, list + cand_of<kPF>() * kRB);
     }
     RTX_DIAG_HW(0);
     const float best0 = best;
     int idx = -1;
     bool ok = true;
     uint32_t b0 = nblk ? start % nblk : 0u;
-    if (RTX_PACK && kPF && pack) {
+    if (kPF && pack) {
         const uint32_t at = __builtin_amdgcn_readfirstlane(*pack);  // wave-uniform (SGPR)
         b0 = at < nblk ? (at + nblk - kPackLag) % nblk : 0u;  // nblk > 128 > kPackLag
     }
@@ -1543,7 +1432,7 @@ __device__ __forceinline__ int hit_world_groups_culled(const KScene &S, uint64_t
                 const f2v pv = fma2(cy, vy, fma2(cz, vz, nov));
                 const f2v q = fma2(-pv, pv, fma2(-pu, pu, R));
                 bool px = !(q.x < thr), py = !(q.y < thr);
-                if (RTX_CULL_HALF && Hh) {
+                if (Hh) {
                     const f2v hdx = {Hh->dx, Hh->dx}, hdy = {Hh->dy, Hh->dy}, hdz = {Hh->dz, Hh->dz};
                     const f2v hnod = {Hh->nod, Hh->nod}, ha = {Hh->a, Hh->a}, htha = {Hh->tha, Hh->tha};
                     const f2v pw = fma2(cx, hdx, fma2(cy, hdy, fma2(cz, hdz, hnod)));
@@ -1561,7 +1450,6 @@ __device__ __forceinline__ int hit_world_groups_culled(const KScene &S, uint64_t
             const LineTest &L = flat ? Ts : T;
             const HalfTest &Hh = flat ? Hs : H;
             if (line_test_q(L, q[0], q[8], q[16], q[24]) < (flat ? thr_bs : thr_b)) return false;
-            if (!RTX_CULL_HALF) return true;
             const float pw = half_test_pw(Hh, q[0], q[8], q[16]);
             return half_test_pass(pw, half_test_q2(Hh, pw, q[24]));
         };
@@ -1574,7 +1462,7 @@ __device__ __forceinline__ int hit_world_groups_culled(const KScene &S, uint64_t
         };
         auto first_bits = [](uint32_t n) { return n >= 8u ? 0xffu : (1u << n) - 1u; };
         const uint32_t nsg = (ngrp + 7u) / 8u;
-        if (kBfs && m == 1u && RTX_CULL_BFS) {
+        if (kBfs && m == 1u) {
             // One ray, the whole wave: breadth first. Each level's passing
             // entries are expanded 8 at a time, one child per lane (entry e's
             // bound at (AoSoA-8) floats 32 (e >> 3) + (e & 7) + {0, 8, 16, 24}),
@@ -1585,10 +1473,7 @@ __device__ __forceinline__ int hit_world_groups_culled(const KScene &S, uint64_t
             };
             auto test_sphere = [&](uint32_t pos) {
                 const float *q = S.cpre + 32u * (pos >> 3) + (pos & 7u);
-                if (line_test_q(T, q[0], q[8], q[16], q[24]) < T.thr) return false;
-                if (!RTX_CULL_HALF_SPHERES) return true;
-                const float pw = half_test_pw(H, q[0], q[8], q[16]);
-                return half_test_pass(pw, half_test_q2(H, pw, q[24]));
+                return !(line_test_q(T, q[0], q[8], q[16], q[24]) < T.thr);
             };
             // the child this lane takes: of the (lane >> 3)-th set bit of the
             // uniform mask m (the next 8 set bits are consumed)
@@ -1606,8 +1491,7 @@ __device__ __forceinline__ int hit_world_groups_culled(const KScene &S, uint64_t
 #pragma unroll 1
             for (uint32_t base = 0; base < nsg; base += 64u) {
                 const uint32_t si = base + lane;
-                uint64_t m3 = __ballot(si < nsg && (RTX_CULL_LEVELS < 3 ||
-                                                    test_entry(S.cbnd3, si, 64u * si >= S.cflat_lo)));
+                uint64_t m3 = __ballot(si < nsg && test_entry(S.cbnd3, si, 64u * si >= S.cflat_lo));
 #pragma unroll 1
                 while (m3 != 0ull) {
                     uint32_t ps;
@@ -1643,7 +1527,7 @@ __device__ __forceinline__ int hit_world_groups_culled(const KScene &S, uint64_t
             const uint32_t si = (st << lg) + k;  // super-group si: its bound (512 spheres) in cbnd3
             if (si >= nsg) break;
             const float *sb = S.cbnd3 + 32u * (si >> 3) + (si & 7u);
-            if (RTX_CULL_LEVELS >= 3 && !bound_pass(sb, 64u * si >= S.cflat_lo)) continue;
+            if (!bound_pass(sb, 64u * si >= S.cflat_lo)) continue;
             uint32_t mg = bounds_mask(S.cbnd2 + 32u * si, 64u * si) & first_bits(ngrp - 8u * si);
 #pragma unroll 1
             while (mg != 0u) {
@@ -1654,7 +1538,7 @@ __device__ __forceinline__ int hit_world_groups_culled(const KScene &S, uint64_t
                 while (mb != 0u) {
                     const uint32_t bb = 8u * gi + (uint32_t)__builtin_ctz(mb);
                     mb &= mb - 1u;
-                    uint32_t ms = block_mask(S.cpre + 32u * bb, T, T.thr, RTX_CULL_HALF_SPHERES ? &H : nullptr);
+                    uint32_t ms = block_mask(S.cpre + 32u * bb, T, T.thr);
 #pragma unroll 1
                     while (ms != 0u) {
                         const uint32_t pos = 8u * bb + (uint32_t)__builtin_ctz(ms);
@@ -1693,9 +1577,6 @@ __device__ __forceinline__ int hit_world_groups_culled(const KScene &S, uint64_t
     return active ? result : -1;
 }
 
-#ifndef RTX_PROM_EXACT_RATE  // A/B: a restarted pixel's promotion rate over its samples from 0 (1) or from cost_spp (0)
-#define RTX_PROM_EXACT_RATE 1
-#endif
 // Lane state: the pixel it is tracing and that pixel's current path.
 constexpr uint32_t kSeg0Restart = 0x80000000u;  // Lane::seg0 flag (a lane's segs stay far below 2^31)
 struct Lane {
@@ -1797,9 +1678,6 @@ __device__ __forceinline__ void output_pixel(const KParams &P, uint32_t gid, f3 
     }
 }
 
-#ifndef RTX_EXTRA_BYTES
-#define RTX_EXTRA_BYTES 0
-#endif
 // A pixel's output (output_pixel), or the scheduling pre-pass's record of it.
 // kAdapt (an adaptive refine launch: rtx_adaptive.h): the pixel's count and
 // its old sum are read here, at the finish, so the lane carries no state for
@@ -1837,10 +1715,6 @@ __device__ __forceinline__ void write_pixel(const KParams &P, const Lane &L) {
     // ... and what the pixel cost in this launch, the next one's queue key
     // (the same slot discipline: written only by whoever finishes the pixel)
     if constexpr (kRefine) P.cost_map[L.gid] = launch_segs(P, L);
-    // A/B build (HBM traffic): the pixel's final state also
-    // goes back to its (dead) resume slot: +16 B per pixel of the same
-    // scattered cost-order stores as the image
-    if (RTX_EXTRA_BYTES && P.state) P.state[L.gid] = make_float4(L.acc.x, L.acc.y, L.acc.z, L.seed);
 }
 
 // Diffuse direction before normalisation, target - p (ShaderCompute.hlsl:
@@ -2030,7 +1904,7 @@ __device__ __forceinline__ bool promote(const KParams &P, const Lane &L, uint32_
     // samples traced in this launch (>= 1 here): after the pre-pass's
     // cost_spp, or from sample 0 for a pixel the pre-pass stopped (cost_cap;
     // kSeg0Restart in seg0)
-    const bool restarted = RTX_PROM_EXACT_RATE && (L.seg0 & kSeg0Restart) != 0u;
+    const bool restarted = (L.seg0 & kSeg0Restart) != 0u;
     const uint32_t done = max(restarted ? L.sample : L.sample - min(L.sample, P.cost_spp), 1u);
     const uint32_t segs = L.segs - (L.seg0 & ~kSeg0Restart);
     if ((uint64_t)segs * (P.spp - L.sample) <= (uint64_t)min_segs * done) return false;
@@ -2543,12 +2417,9 @@ static_assert(kPromValveTicks < (1ull << 31), "the valve's 32-bit clock");
 // adds the launch's queue counters, which stay in memory after it). Kept to
 // one atomic: the record's code sits in k_render, whose registers are tight
 // (a larger record moved the C2 render's spill code).
-#ifndef RTX_VALVE_RECORD  // A/B build: 0 = the error bit alone
-#define RTX_VALVE_RECORD 1
-#endif
 __device__ __forceinline__ void valve_fire(const KParams &P, uint32_t bit, uint32_t who, const Valve &V) {
     flag_error(P, bit);
-    if (!RTX_VALVE_RECORD || P.err_diag == nullptr || (threadIdx.x & 63u) != 0u) return;
+    if (P.err_diag == nullptr || (threadIdx.x & 63u) != 0u) return;
     const unsigned long long now = __builtin_amdgcn_s_memrealtime();
     const uint32_t bt = __hip_atomic_load(&P.prom[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t since = min(((uint32_t)now - V.t0) >> kBeatShift, 0xffffu);  // 10.24 us units
@@ -2681,25 +2552,18 @@ __device__ __forceinline__ bool pre_stop(const KParams &P, uint32_t npix, Lane &
 // pixel index (row-major within a T x T tile, tiles row-major), or ~0u for a
 // slot of a partial tile; T = 0: row-major, the identity. The cost sort
 // uses them (RTX_QUEUE_TILE, below): spatially close rays share more of the
-// layer grid's blocks. The exact grid can too (RTX_EXACT_TILE 8: a wave's 64
-// lanes an 8 x 8 patch; an A/B option, flat at C2: S6s).
-__host__ __device__ __forceinline__ uint32_t tile_span(uint32_t width, uint32_t rows, uint32_t T, uint32_t TY = 0u) {
-    if (TY == 0u) TY = T;
-    return T == 0u ? width * rows : ((width + T - 1u) / T) * ((rows + TY - 1u) / TY) * T * TY;
+// layer grid's blocks. (The exact grid is row-major: in 8 x 8 tiles, a wave's
+// 64 lanes one patch, it was flat at C2, S6s.)
+__host__ __device__ __forceinline__ uint32_t tile_span(uint32_t width, uint32_t rows, uint32_t T) {
+    return T == 0u ? width * rows : ((width + T - 1u) / T) * ((rows + T - 1u) / T) * T * T;
 }
-// (T x TY tiles; TY = 0: square)
-__device__ __forceinline__ uint32_t tile_pixel(uint32_t j, uint32_t width, uint32_t rows, uint32_t T, uint32_t TY = 0u) {
+__device__ __forceinline__ uint32_t tile_pixel(uint32_t j, uint32_t width, uint32_t rows, uint32_t T) {
     if (T == 0u) return j < width * rows ? j : ~0u;
-    if (TY == 0u) TY = T;
     const uint32_t tx = (width + T - 1u) / T;
-    const uint32_t t = j / (T * TY), u = j % (T * TY);
-    const uint32_t x = (t % tx) * T + u % T, y = (t / tx) * TY + u / T;
+    const uint32_t t = j / (T * T), u = j % (T * T);
+    const uint32_t x = (t % tx) * T + u % T, y = (t / tx) * T + u / T;
     return (x < width && y < rows) ? y * width + x : ~0u;
 }
-#ifndef RTX_EXACT_TILE
-#define RTX_EXACT_TILE 0
-#endif
-constexpr uint32_t kExactTile = RTX_EXACT_TILE;
 
 // kAdapt (with kPersist and kRefine): an adaptive refine launch's instance —
 // the queue holds the qlen active pixels only (KParams::qlen), write_pixel
@@ -2709,7 +2573,7 @@ template <bool kPersist, bool kCost = false, bool kPF = false, bool kLin = false
           bool kAdapt = false>
 __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
     static_assert(!kAdapt || (kPersist && kRefine && !kCost), "adaptive: the persistent refine render only");
-    constexpr bool kCulled = kPF && RTX_CULL && !kLin;  // the culled scan (large scenes, not the linear mode)
+    constexpr bool kCulled = kPF && !kLin;  // the culled scan (large scenes, not the linear mode)
     // dynamic LDS: [candidate list, list_bytes<kPF>][coop rays, kCoopBytes][coop LDS copy of the spheres]
     extern __shared__ __attribute__((aligned(16))) unsigned char s_mem[];
     uint32_t *list = reinterpret_cast<uint32_t *>(s_mem);
@@ -2726,7 +2590,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
                                          : lds_pos_map(P.scene, s_mem + kLB + kCoopBytes + coop_lds_bytes(P.scene.n));
     // kPF scenes never fit the LDS copy: its place holds the scan's pack word
     uint32_t *pack = kPF ? reinterpret_cast<uint32_t *>(s_mem + kLB + kCoopBytes) : nullptr;
-    const float *pf_tile = kPF && (RTX_PF_LDS || RTX_PF_RING) ? reinterpret_cast<const float *>(s_mem + kLB + kCoopBytes + 16) : nullptr;
+    const float *pf_tile = kPF ? reinterpret_cast<const float *>(s_mem + kLB + kCoopBytes + 16) : nullptr;
     // promotion: the block's first wave to go idle serves the queue, the others leave
     __shared__ uint32_t s_server;
     const bool prom_on = kPersist && !kCost && P.prom != nullptr;
@@ -2751,7 +2615,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
     L.cb = L.ce = 0u;
     bool exhausted = !kPersist;
     if (!kPersist) {
-        const uint32_t gid = tile_pixel(blockIdx.x * kRB + threadIdx.x, P.width, P.rows_local, kExactTile);
+        const uint32_t gid = tile_pixel(blockIdx.x * kRB + threadIdx.x, P.width, P.rows_local, 0u);  // row-major
         if (gid < npix) start_pixel<kRefine>(P, F, gid, L);
     }
     // heavy slots [0, kh) of the queue (k_heavy_split; tier 1 = [0, k1)), normal slots [kh, npix)
@@ -2858,7 +2722,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
                 D.section(1);
                 promoted = shade<kCost, kRefine, kAdapt>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
             }
-        } else if ((RTX_PF_LDS || RTX_PF_RING) && kPF) {  // every lane of the wave fills the scan's LDS tile
+        } else if (kPF) {  // every lane of the wave fills the scan's LDS tile
             float best = __uint_as_float(0x7f800000u);
             auto ldc = [&P](uint32_t i) { return P.scene.cen[i]; };
             const int hit = hit_world_pre_ld<kPF, decltype(ldc), true>(P.scene, ldc, L.o, L.d, L.a, L.inv_a, kTMin,
@@ -2871,8 +2735,8 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
             // from it (the same centre and radius floats as cen) instead of HBM/L2
             const int hit = (!kPF && coop_lds)  // kPF scenes (> kScanPfMin) never fit
                                 ? hit_world_pre_ld<kPF>(P.scene, [sl](uint32_t i) { return sl.sphere(i); }, L.o, L.d,
-                                                        L.a, L.inv_a, kTMin, best, list, nullptr, 0,
-                                                        RTX_SCAN_LDS ? sl.pr : nullptr, true, lmap)
+                                                        L.a, L.inv_a, kTMin, best, list, nullptr, 0, nullptr, true,
+                                                        lmap)
                                 : hit_world_pre<kPF>(P.scene, L.o, L.d, L.a, L.inv_a, kTMin, best, list, pack);
             D.section(1);
             promoted = shade<kCost, kRefine, kAdapt>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
@@ -3156,13 +3020,13 @@ constexpr uint32_t kChunkShare = 16;  // the private runs of large scenes and me
 
 __global__ void __launch_bounds__(kBlock) k_cost_hist(const uint32_t *cost, uint32_t width, uint32_t rows,
                                                       uint32_t cost_spp, uint32_t sat_cap, uint32_t tile,
-                                                      uint32_t tile_y, uint32_t *counts) {
+                                                      uint32_t *counts) {
     __shared__ uint32_t h[kCostBuckets];
     for (uint32_t b = threadIdx.x; b < kCostBuckets; b += kBlock) h[b] = 0;
     __syncthreads();
     const uint32_t base = blockIdx.x * kBlock * kSortPerThread;
     for (uint32_t k = 0; k < kSortPerThread; ++k) {
-        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile, tile_y);
+        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile);
         if (i != ~0u) atomicAdd(&h[cost_key(cost, i, width, rows, cost_spp, sat_cap)], 1u);
     }
     __syncthreads();
@@ -3174,14 +3038,13 @@ __global__ void __launch_bounds__(kBlock) k_cost_hist(const uint32_t *cost, uint
 // carried_key; no saturated entries). A sibling kernel, so that k_cost_hist's
 // code stays what it was.
 __global__ void __launch_bounds__(kBlock) k_carried_hist(const uint32_t *map, uint32_t width, uint32_t rows,
-                                                         uint32_t s_prev, uint32_t tile, uint32_t tile_y,
-                                                         uint32_t *counts) {
+                                                         uint32_t s_prev, uint32_t tile, uint32_t *counts) {
     __shared__ uint32_t h[kCostBuckets];
     for (uint32_t b = threadIdx.x; b < kCostBuckets; b += kBlock) h[b] = 0;
     __syncthreads();
     const uint32_t base = blockIdx.x * kBlock * kSortPerThread;
     for (uint32_t k = 0; k < kSortPerThread; ++k) {
-        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile, tile_y);
+        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile);
         if (i != ~0u) atomicAdd(&h[carried_key(map, i, width, rows, s_prev)], 1u);
     }
     __syncthreads();
@@ -3195,7 +3058,6 @@ __global__ void __launch_bounds__(kBlock) k_carried_hist(const uint32_t *map, ui
 // Per-pixel results do not depend on it.
 __global__ void __launch_bounds__(kBlock) k_cost_scatter(const uint32_t *cost, uint32_t width, uint32_t rows,
                                                          uint32_t cost_spp, uint32_t sat_cap, uint32_t tile,
-                                                         uint32_t tile_y,
                                                          const uint32_t *counts, uint32_t *cursors,
                                                          uint32_t *perm, uint32_t *inv) {
     __shared__ uint32_t h[kCostBuckets], start[kCostBuckets];
@@ -3204,7 +3066,7 @@ __global__ void __launch_bounds__(kBlock) k_cost_scatter(const uint32_t *cost, u
     const uint32_t base = blockIdx.x * kBlock * kSortPerThread;
     uint32_t rank[kSortPerThread], key[kSortPerThread];
     for (uint32_t k = 0; k < kSortPerThread; ++k) {
-        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile, tile_y);
+        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile);
         key[k] = i != ~0u ? cost_key(cost, i, width, rows, cost_spp, sat_cap) : 0u;
         rank[k] = i != ~0u ? atomicAdd(&h[key[k]], 1u) : 0u;
     }
@@ -3221,7 +3083,7 @@ __global__ void __launch_bounds__(kBlock) k_cost_scatter(const uint32_t *cost, u
         if (h[b]) start[b] += atomicAdd(&cursors[b], h[b]);
     __syncthreads();
     for (uint32_t k = 0; k < kSortPerThread; ++k) {
-        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile, tile_y);
+        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile);
         if (i != ~0u) {
             const uint32_t g = start[key[k]] + rank[k];
             perm[g] = i;
@@ -3231,7 +3093,7 @@ __global__ void __launch_bounds__(kBlock) k_cost_scatter(const uint32_t *cost, u
 }
 // k_cost_scatter's sibling for a carried refine launch (k_carried_hist's keys).
 __global__ void __launch_bounds__(kBlock) k_carried_scatter(const uint32_t *map, uint32_t width, uint32_t rows,
-                                                            uint32_t s_prev, uint32_t tile, uint32_t tile_y,
+                                                            uint32_t s_prev, uint32_t tile,
                                                             const uint32_t *counts, uint32_t *cursors,
                                                             uint32_t *perm, uint32_t *inv) {
     __shared__ uint32_t h[kCostBuckets], start[kCostBuckets];
@@ -3240,7 +3102,7 @@ __global__ void __launch_bounds__(kBlock) k_carried_scatter(const uint32_t *map,
     const uint32_t base = blockIdx.x * kBlock * kSortPerThread;
     uint32_t rank[kSortPerThread], key[kSortPerThread];
     for (uint32_t k = 0; k < kSortPerThread; ++k) {
-        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile, tile_y);
+        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile);
         key[k] = i != ~0u ? carried_key(map, i, width, rows, s_prev) : 0u;
         rank[k] = i != ~0u ? atomicAdd(&h[key[k]], 1u) : 0u;
     }
@@ -3257,7 +3119,7 @@ __global__ void __launch_bounds__(kBlock) k_carried_scatter(const uint32_t *map,
         if (h[b]) start[b] += atomicAdd(&cursors[b], h[b]);
     __syncthreads();
     for (uint32_t k = 0; k < kSortPerThread; ++k) {
-        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile, tile_y);
+        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile);
         if (i != ~0u) {
             const uint32_t g = start[key[k]] + rank[k];
             perm[g] = i;
@@ -3321,13 +3183,13 @@ __global__ void __launch_bounds__(kBlock) k_adaptive_edges(const float *__restri
 // is heavy, k_heavy_split).
 __global__ void __launch_bounds__(kBlock) k_adaptive_hist(const uint32_t *map, const uint8_t *flags, uint32_t width,
                                                           uint32_t rows, uint32_t s_prev, uint32_t tile,
-                                                          uint32_t tile_y, uint32_t *counts) {
+                                                          uint32_t *counts) {
     __shared__ uint32_t h[kCostBuckets];
     for (uint32_t b = threadIdx.x; b < kCostBuckets; b += kBlock) h[b] = 0;
     __syncthreads();
     const uint32_t base = blockIdx.x * kBlock * kSortPerThread;
     for (uint32_t k = 0; k < kSortPerThread; ++k) {
-        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile, tile_y);
+        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile);
         if (i != ~0u && flags[i] != 0u)
             atomicAdd(&h[s_prev != 0u ? carried_key(map, i, width, rows, s_prev) : kCostBuckets - 1u], 1u);
     }
@@ -3337,15 +3199,15 @@ __global__ void __launch_bounds__(kBlock) k_adaptive_hist(const uint32_t *map, c
 }
 __global__ void __launch_bounds__(kBlock) k_adaptive_scatter(const uint32_t *map, const uint8_t *flags, uint32_t width,
                                                              uint32_t rows, uint32_t s_prev, uint32_t tile,
-                                                             uint32_t tile_y, const uint32_t *counts,
-                                                             uint32_t *cursors, uint32_t *perm, uint32_t *inv) {
+                                                             const uint32_t *counts, uint32_t *cursors,
+                                                             uint32_t *perm, uint32_t *inv) {
     __shared__ uint32_t h[kCostBuckets], start[kCostBuckets];
     for (uint32_t b = threadIdx.x; b < kCostBuckets; b += kBlock) h[b] = 0;
     __syncthreads();
     const uint32_t base = blockIdx.x * kBlock * kSortPerThread;
     uint32_t rank[kSortPerThread], key[kSortPerThread];
     for (uint32_t k = 0; k < kSortPerThread; ++k) {
-        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile, tile_y);
+        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile);
         const bool on = i != ~0u && flags[i] != 0u;
         key[k] = !on ? ~0u : s_prev != 0u ? carried_key(map, i, width, rows, s_prev) : kCostBuckets - 1u;
         rank[k] = on ? atomicAdd(&h[key[k]], 1u) : 0u;
@@ -3363,7 +3225,7 @@ __global__ void __launch_bounds__(kBlock) k_adaptive_scatter(const uint32_t *map
         if (h[b]) start[b] += atomicAdd(&cursors[b], h[b]);
     __syncthreads();
     for (uint32_t k = 0; k < kSortPerThread; ++k) {
-        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile, tile_y);
+        const uint32_t i = tile_pixel(base + k * kBlock + threadIdx.x, width, rows, tile);
         if (i == ~0u) continue;
         const uint32_t g = key[k] != ~0u ? start[key[k]] + rank[k] : ~0u;
         if (g != ~0u) perm[g] = i;
@@ -3459,7 +3321,7 @@ __global__ void k_heavy_split(const uint32_t *counts, uint32_t npix, uint32_t la
 // po * spp + s) go to the wave's lanes as they free up, so lanes stay busy
 // across path lengths (1..depth segments) without waiting for each other. A
 // finished sample stores its colour (col * sky, or +0 for a black path) into
-// the wave's scratch at [slot][s * npx + po] (float4); when all items of a
+// the wave's scratch at [slot][po * spp + s] (float4); when all items of a
 // batch are done, lane po folds its pixel's colours IN SAMPLE ORDER —
 // acc = ((0 + c_0) + c_1) + ... — which is bit for bit the reference's
 // accumulation (:304-312; adding +0 for a black sample leaves acc unchanged:
@@ -3475,9 +3337,8 @@ __global__ void k_heavy_split(const uint32_t *counts, uint32_t npix, uint32_t la
 // and a wave has at most kCoopMax samples left, it traces them with the
 // group coop of the chain kernel (several lanes per ray), at a raised wave
 // priority: the frame's last, longest paths end sooner.
-#ifndef RTX_PS_ITEM_MAJOR  // per-sample scratch layout: 1 = item-major (37.6 vs 38.5 ms, 8.8 vs 13.5 GB per C2 frame: R3u), 0 = sample-major
-#define RTX_PS_ITEM_MAJOR 1
-#endif
+// (the scratch is item-major, the order the lanes take the items in: against
+// sample-major 37.6 vs 38.5 ms, 8.8 vs 13.5 GB per C2 frame, R3u)
 constexpr int kPsSlots = 4;
 constexpr uint32_t kPsStateBytes = (kRB / 64) * kPsSlots * 4 * sizeof(uint32_t);  // per block
 struct PsLane {
@@ -3485,12 +3346,12 @@ struct PsLane {
     float a, inv_a, seed;
     uint32_t bounce, segs;
     uint32_t slot;  // batch slot of the sample
-    uint32_t sidx;  // s * npx + po: the sample's scratch index in its slot
+    uint32_t sidx;  // po * spp + s (its item): the sample's scratch index in its slot
     bool active;
 };
 
-__device__ __forceinline__ void ps_start(const KParams &P, const Frame &F, uint32_t px0, uint32_t npx,
-                                         uint32_t slot, uint32_t item, PsLane &L) {
+__device__ __forceinline__ void ps_start(const KParams &P, const Frame &F, uint32_t px0, uint32_t slot,
+                                         uint32_t item, PsLane &L) {
     const uint32_t po = item / P.spp;
     const uint32_t s = item - po * P.spp;
     uint32_t x, y;
@@ -3505,7 +3366,7 @@ __device__ __forceinline__ void ps_start(const KParams &P, const Frame &F, uint3
     L.col = mk3(1.0f, 1.0f, 1.0f);
     L.bounce = 0;
     L.slot = slot;
-    L.sidx = RTX_PS_ITEM_MAJOR ? item : s * npx + po;
+    L.sidx = item;
     L.active = true;
 }
 
@@ -3520,28 +3381,24 @@ __device__ __forceinline__ void ps_fold(const KParams &P, uint32_t px0, uint32_t
     if (po >= npx) return;
     f3 acc = mk3(0.0f, 0.0f, 0.0f);
     uint32_t s = 0;
-    // sample s of pixel po: [s * npx + po] (sample-major), or [po * spp + s]
-    // (item-major: the order the lanes take the items in)
-    const uint32_t ss = RTX_PS_ITEM_MAJOR ? 1u : npx;
-    if (RTX_PS_ITEM_MAJOR) c += po * P.spp;
-    else c += po;
+    c += po * P.spp;  // sample s of pixel po: [po * spp + s]
     for (; s + 8 <= P.spp; s += 8) {  // eight samples' loads in flight, adds in order
         float4 v[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = c[(s + k) * ss];
+        for (int k = 0; k < 8; ++k) v[k] = c[s + k];
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc = acc + mk3(v[k].x, v[k].y, v[k].z);
     }
     for (; s < P.spp; ++s) {
-        const float4 v = c[s * ss];
+        const float4 v = c[s];
         acc = acc + mk3(v.x, v.y, v.z);
     }
     output_pixel(P, px0 + po, acc);
 }
 
 template <bool kPF, bool kLin = false>
-__global__ void RTX_PS_BOUNDS_T(kPF) k_render_ps(const KParams P) {
-    constexpr bool kCulled = kPF && RTX_CULL && !kLin;  // the culled scan (large scenes, not the linear mode)
+__global__ void RTX_RENDER_BOUNDS k_render_ps(const KParams P) {
+    constexpr bool kCulled = kPF && !kLin;  // the culled scan (large scenes, not the linear mode)
     // dynamic LDS: [candidate list, list_bytes<kPF>][coop rays, kCoopBytes][batch slots, kPsStateBytes]
     //              [LDS copy of the spheres (n <= kCoopLds)]
     extern __shared__ __attribute__((aligned(16))) unsigned char s_mem[];
@@ -3604,7 +3461,7 @@ __global__ void RTX_PS_BOUNDS_T(kPF) k_render_ps(const KParams P) {
             const uint32_t take = min((uint32_t)__popcll(idle), c_total - c_issued);
             const uint32_t rank =
                 __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-            if (!L.active && rank < take) ps_start(P, F, c_px0, c_npx, cur, c_issued + rank, L);
+            if (!L.active && rank < take) ps_start(P, F, c_px0, cur, c_issued + rank, L);
             c_issued += take;
         }
         if (__ballot(L.active) == 0ull) break;  // queue exhausted and every batch folded
@@ -3929,8 +3786,7 @@ __global__ void RTX_RENDER_BOUNDS k_debug_scan_rate(const KParams P, uint32_t re
     for (uint32_t r = 0; r < reps; ++r) {
         float best = __uint_as_float(0x7f800000u);
         const int hit = hit_world_pre_ld<false>(P.scene, [sl](uint32_t i) { return sl.sphere(i); }, o, d, a, inv_a,
-                                                kTMin, best, list, nullptr, 0, RTX_SCAN_LDS ? sl.pr : nullptr, true,
-                                                lmap);
+                                                kTMin, best, list, nullptr, 0, nullptr, true, lmap);
         acc += (uint32_t)hit ^ __float_as_uint(best);
     }
 #pragma unroll
@@ -4016,8 +3872,8 @@ static hipError_t allow_lds(const void *kern, size_t lds) {
 // k_render with the SGPR double-buffered scan for scenes whose `pre` array
 // does not stay in the scalar cache (kScanPfMin).
 static bool use_pf(const KScene &s) { return s.n_pad > kScanPfMin; }
-// The linear-scan mode (rtx_set_scan_mode RTX_SCAN_LINEAR, or an RTX_CULL=0
-// build): a large scene uploaded without the culled layout; its kernels scan
+// The linear-scan mode (rtx_set_scan_mode RTX_SCAN_LINEAR): a large scene
+// uploaded without the culled layout; its kernels scan
 // every block of every segment (the reference's Hittable_list order of work,
 // with the prefilter), through the per-wave LDS tile in the chain render.
 static bool use_lin(const KScene &s) { return use_pf(s) && s.cpre == nullptr; }
@@ -4075,7 +3931,7 @@ hipError_t launch_cost(const KParams &p, hipStream_t stream) {
     const size_t lds = render_lds(p.scene);
     hipError_t e = allow_lds(render_fn<false, true>(p.scene), lds);
     if (e != hipSuccess) return e;
-    launch_k<false, true>(p.scene, ceil_div(tile_span(p.width, p.rows_local, kExactTile), kRB), lds, stream, p);
+    launch_k<false, true>(p.scene, ceil_div(p.width * p.rows_local, kRB), lds, stream, p);
     return hipGetLastError();
 }
 
@@ -4147,7 +4003,7 @@ hipError_t launch_render(const KParams &p_in, const KSchedule &sched, hipStream_
     const uint64_t lanes = (uint64_t)p.rows_local * p.width;
     if (lanes == 0) return hipSuccess;
     const uint32_t need = ceil_div(lanes, kRB);
-    const uint32_t need_x = ceil_div(tile_span(p.width, p.rows_local, kExactTile), kRB);  // the exact grid's blocks
+    const uint32_t need_x = ceil_div(p.width * p.rows_local, kRB);  // the exact grid's blocks
     if (p.spp == 0 || p.depth == 0) {
         hipLaunchKernelGGL(k_render_trivial, dim3(ceil_div(lanes, kBlock)), dim3(kBlock), 0, stream, p);
         return hipGetLastError();
@@ -4225,26 +4081,18 @@ hipError_t launch_render(const KParams &p_in, const KSchedule &sched, hipStream_
         launch_kr<false, true>(p.scene, need_x, lds, stream, c);
     }
     // 2. counting sort by cost, descending
-    // (in pixel tiles except for a small share: R = 8 12.7 vs 13.0 ms, S6r, S6v)
-#ifndef RTX_QUEUE_TILE_ALL  // A/B: 1 = pixel tiles for every share size
-#define RTX_QUEUE_TILE_ALL 0
-#endif
-#ifndef RTX_QUEUE_TILE_SPLIT  // A/B: a row-split part's tiles, this wide and one row tile (tile_rows) tall
-#define RTX_QUEUE_TILE_SPLIT 0
-#endif
-    // a part's rows are runs of tile_rows image rows: its tiles are one run tall
-    uint32_t qtile = RTX_QUEUE_TILE_ALL || (double)lanes >= tune.rho * (double)min(need, resident_blocks(render_fn<true, false>(p.scene), lds)) * kRB
-                         ? kQueueTile
-                         : 0u;
-    uint32_t qtile_y = 0u;
-    if (RTX_QUEUE_TILE_SPLIT != 0 && p.nparts > 1u && p.tile_rows != 0u) qtile = RTX_QUEUE_TILE_SPLIT, qtile_y = p.tile_rows;
-    const uint32_t sblocks = ceil_div(tile_span(p.width, p.rows_local, qtile, qtile_y), kBlock * kSortPerThread);
+    // (in pixel tiles except for a small share: R = 8 12.7 vs 13.0 ms, S6r, S6v;
+    // a row-split part's tiles one row tile tall: flat, S7a)
+    const uint32_t qtile = (double)lanes >= tune.rho * (double)min(need, resident_blocks(render_fn<true, false>(p.scene), lds)) * kRB
+                               ? kQueueTile
+                               : 0u;
+    const uint32_t sblocks = ceil_div(tile_span(p.width, p.rows_local, qtile), kBlock * kSortPerThread);
     if (carried)
         hipLaunchKernelGGL(k_carried_hist, dim3(sblocks), dim3(kBlock), 0, stream, sched.cost_map, p.width,
-                           p.rows_local, sched.carry_spp, qtile, qtile_y, sched.buckets);
+                           p.rows_local, sched.carry_spp, qtile, sched.buckets);
     else
         hipLaunchKernelGGL(k_cost_hist, dim3(sblocks), dim3(kBlock), 0, stream, sched.cost, p.width,
-                           p.rows_local, c.spp, split_cap, qtile, qtile_y, sched.buckets);
+                           p.rows_local, c.spp, split_cap, qtile, sched.buckets);
     // 3. heavy-pixel split (from the histogram), the ordered queue, then
     // the persistent render over it
     uint32_t blocks = min(need, resident_blocks(render_fn<true, false>(p.scene), lds));
@@ -4258,11 +4106,11 @@ hipError_t launch_render(const KParams &p_in, const KSchedule &sched, hipStream_
                        heavy, tune);
     if (carried)
         hipLaunchKernelGGL(k_carried_scatter, dim3(sblocks), dim3(kBlock), 0, stream, sched.cost_map, p.width,
-                           p.rows_local, sched.carry_spp, qtile, qtile_y, sched.buckets, sched.buckets + kCostBuckets,
+                           p.rows_local, sched.carry_spp, qtile, sched.buckets, sched.buckets + kCostBuckets,
                            sched.perm, sched.stage ? sched.inv : nullptr);
     else
         hipLaunchKernelGGL(k_cost_scatter, dim3(sblocks), dim3(kBlock), 0, stream, sched.cost, p.width,
-                           p.rows_local, c.spp, split_cap, qtile, qtile_y, sched.buckets, sched.buckets + kCostBuckets, sched.perm,
+                           p.rows_local, c.spp, split_cap, qtile, sched.buckets, sched.buckets + kCostBuckets, sched.perm,
                            sched.stage ? sched.inv : nullptr);
     KParams q = p;
     q.cost_spp = carried ? 0u : c.spp;
@@ -4418,10 +4266,10 @@ hipError_t launch_render_adaptive(const KParams &p_in, const KSchedule &sched, c
     if (e != hipSuccess) return e;
     const uint32_t need = ceil_div(lanes, kRB);
     const uint32_t rb = resident_blocks(fn, lds);
-    const uint32_t qtile = RTX_QUEUE_TILE_ALL || (double)lanes >= tune.rho * (double)min(need, rb) * kRB ? kQueueTile : 0u;
+    const uint32_t qtile = (double)lanes >= tune.rho * (double)min(need, rb) * kRB ? kQueueTile : 0u;
     const uint32_t sblocks = ceil_div(tile_span(p.width, p.rows_local, qtile), kBlock * kSortPerThread);
     hipLaunchKernelGGL(k_adaptive_hist, dim3(sblocks), dim3(kBlock), 0, stream, sched.cost_map, a.flags, p.width,
-                       p.rows_local, sched.carry_spp, qtile, 0u, sched.buckets);
+                       p.rows_local, sched.carry_spp, qtile, sched.buckets);
     uint32_t blocks = min(need, rb);
     const double ppl0 = (double)lanes / ((double)blocks * kRB);
     {
@@ -4432,7 +4280,7 @@ hipError_t launch_render_adaptive(const KParams &p_in, const KSchedule &sched, c
     hipLaunchKernelGGL(k_heavy_split, dim3(1), dim3(64), 0, stream, sched.buckets, (uint32_t)lanes, blocks * kRB, p.spp,
                        heavy, tune);
     hipLaunchKernelGGL(k_adaptive_scatter, dim3(sblocks), dim3(kBlock), 0, stream, sched.cost_map, a.flags, p.width,
-                       p.rows_local, sched.carry_spp, qtile, 0u, sched.buckets, sched.buckets + kCostBuckets, sched.perm,
+                       p.rows_local, sched.carry_spp, qtile, sched.buckets, sched.buckets + kCostBuckets, sched.perm,
                        sched.inv);
     KParams q = p;
     q.qlen = (uint32_t)lanes;

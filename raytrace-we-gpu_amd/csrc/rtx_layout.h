@@ -149,10 +149,10 @@ inline void layout_order(const float *sph, std::vector<uint32_t> &ids, LayoutOrd
         layout_tiles(sph, ids, tx, tz);
 }
 
-// The layout of a scene of `n` spheres; valid = false when it has none.
-// `with_grid`: also build the layer grid over the position blocks.
+// The layout of a scene of `n` spheres, with the layer grid over its position
+// blocks; valid = false when it has none.
 inline SceneLayout build_scene_layout(const float *sph, uint32_t n, LayoutOrder order = kLayoutDefault,
-                                      bool with_grid = true, uint32_t tx = 4, uint32_t tz = 2) {
+                                      uint32_t tx = 4, uint32_t tz = 2) {
     SceneLayout L;
     std::vector<uint32_t> layer = layout_find_layer(sph, n);
     if (layer.empty()) return L;
@@ -181,8 +181,7 @@ inline SceneLayout build_scene_layout(const float *sph, uint32_t n, LayoutOrder 
         // the RTIOW worlds' three large ones — would resolve it once per copy)
         blk[24 + p % 8] = pad[p] ? -INFINITY : prefilter_R(s[0], s[1], s[2], s[3] * s[3]);
     }
-    if (with_grid)
-        L.has_grid = build_layer_grid_pos(sph, L.perm.data(), 8 * L.flat_lo, 8 * L.flat_hi, L.grid, L.cell);
+    L.has_grid = build_layer_grid_pos(sph, L.perm.data(), 8 * L.flat_lo, 8 * L.flat_hi, L.grid, L.cell);
     L.valid = true;
     return L;
 }

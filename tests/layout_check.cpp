@@ -250,7 +250,7 @@ static void check_scene(const Scene &s, uint32_t want_layer, float want_y, long 
         uint32_t tx, tz;
     } orders[] = {{rtx::kLayoutMedian, 0, 0}, {rtx::kLayoutTiles, 4, 2}, {rtx::kLayoutTiles, 3, 3}, {rtx::kLayoutScene, 0, 0}};
     for (const auto &od : orders) {
-        const rtx::SceneLayout L = rtx::build_scene_layout(s.data(), n, od.order, true, od.tx, od.tz);
+        const rtx::SceneLayout L = rtx::build_scene_layout(s.data(), n, od.order, od.tx, od.tz);
         check_structure(s, L, want_layer, want_y, what);
         check_grid(s, L, nrays, what);
     }

@@ -86,7 +86,7 @@ int main(int argc, char **argv) {
     fclose(f);
 
     rtx::SceneLayout lay;  // (small scenes only: n_pad <= kScanPfMin of rtx_internal.h, 1,024)
-    if (n != 0 && (n + 7) / 8 * 8 <= 1024) lay = rtx::build_scene_layout(sph.data(), n, rtx::kLayoutDefault, true);
+    if (n != 0 && (n + 7) / 8 * 8 <= 1024) lay = rtx::build_scene_layout(sph.data(), n, rtx::kLayoutDefault);
     const bool valid = lay.valid;
     const uint32_t positions = valid ? (uint32_t)lay.perm.size() : 0;
     const uint32_t n_layer = lay.n_layer;

@@ -128,7 +128,7 @@ inline Count count_blocks(const rtx::LayerGrid &G, const std::vector<unsigned lo
 // without a layout or a grid: nblk = 0).
 inline Count count_order(const float *sph, uint32_t n, rtx::LayoutOrder order, uint32_t tx, uint32_t tz,
                          const std::vector<Ray> &rays) {
-    const rtx::SceneLayout L = rtx::build_scene_layout(sph, n, order, true, tx, tz);
+    const rtx::SceneLayout L = rtx::build_scene_layout(sph, n, order, tx, tz);
     if (!L.valid || !L.has_grid) return Count();
     return count_blocks(L.grid, L.cell, L.flat_hi - L.flat_lo, rays);
 }
