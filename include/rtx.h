@@ -40,6 +40,11 @@ extern "C" {
 
 #define RTX_VERSION 145 /* 1.4.5 */
 /* ABI notes.
+ *  1.4.5 (later builds, no version bump): rtx_features, rtx_features_rows,
+ *         rtx_pick (rtx_hit), rtx_mask_from_ids and rtx_refine_masked (the
+ *         first hit of every pixel's centre ray as feature buffers, picking,
+ *         and refinement of the pixels that show chosen objects); purely
+ *         additive again: probe for the symbol (dlsym "rtx_features").
  *  1.4.5 (later builds, no version bump): rtx_debug_scene_info (what
  *         rtx_upload_world built; dlsym "rtx_debug_scene_info").
  *  1.4.5 (later builds, no version bump): rtx_refine_adaptive_rows,
@@ -630,6 +635,84 @@ RTX_API int rtx_refine_edges(rtx_ctx *ctx, void *d_edges);
  * state's rows * width * 4, in the part's row order (as rtx_refine_export). */
 RTX_API int rtx_refine_counts_rows(rtx_ctx *ctx, uint32_t *host_counts, size_t bytes);
 RTX_API int rtx_refine_error_rows(rtx_ctx *ctx, float *host_err, size_t bytes);
+/* ---- first-hit feature buffers, picking, object-masked refinement ----------
+ * (later builds, no version bump: probe with dlsym "rtx_features").
+ * What a pixel shows: the first hit of the ray through the pixel's centre.
+ * For pixel (x, y) of the current frame, y counted from the bottom row (fp32,
+ * in this order, no fma):
+ *   u = ((float)x + 0.5f) / (img_w - 1.0f),  v = ((float)y + 0.5f) / (img_h - 1.0f)
+ *   origin o = frame.origin,  d = ((lower_left + u*horizontal) + v*vertical) - origin
+ * — get_ray's operations (ShaderCompute.hlsl:118-127) without jitter and
+ * without a lens offset even when the frame has a lens radius; rng_mode,
+ * frame_index and flags do not enter. The hit is the render's hit_world with
+ * t_min = 0.001 and t_max = +inf, its record rtx_debug_hit_world's: t, p, the
+ * normal flipped to face the ray, front_face, the scene index (the largest
+ * index among equal roots, as the reference's scan leaves it). Two planes of
+ * float4, rows * width each, row 0 = bottom:
+ *   geom  xyz = the record's normal, w = depth;          a miss: (0, 0, 0, +inf)
+ *   surf  xyz = the sphere's mat_values rgb, w = (float)index;  a miss: (0, 0, 0, -1)
+ * depth = t * sqrt((d.x*d.x + d.y*d.y) + d.z*d.z): the distance in world
+ * units (plain fp32 multiplies and adds, a correctly rounded square root).
+ * The kernel takes the scan path the render takes for the scene (the layout
+ * and layer grid, the culled scan above 1,024 spheres, the linear scan under
+ * RTX_SCAN_LINEAR); it reads the world and the frame and writes the planes,
+ * nothing else: no stats, no framebuffer, no chain state.
+ * rtx_features_rows: the rows of `part` of `nparts` in rtx_render_rows' part
+ * order; rtx_features is rtx_features_rows(ctx, 1, 0, 1, ...). Device
+ * pointers; either plane may be NULL (skipped). Asynchronous on the context
+ * stream. RTX_ERR_INVALID, before any HIP call: a null ctx, both planes NULL,
+ * tile_rows == 0, nparts == 0, part >= nparts. RTX_ERR_STATE: no world or no
+ * frame. A part without rows returns RTX_OK and launches nothing.
+ * With a group, call it on rtx_group_ctx(g, 0): it only reads the world and
+ * the frame the group installed there (there is no group entry point). */
+RTX_API int rtx_features(rtx_ctx *ctx, void *d_geom, void *d_surf);
+RTX_API int rtx_features_rows(rtx_ctx *ctx, uint32_t tile_rows, uint32_t part, uint32_t nparts,
+                              void *d_geom, void *d_surf);
+/* What is under pixel (x, y): the planes' entry of that pixel, with the
+ * record's p and t, the material code as the kernels hold it (RTX_MAT_*; 3: a
+ * code that is none of them and scatters nothing) and mat_values.w.
+ * Synchronous. A miss: hit = 0, index = -1, depth = +inf, the rest 0.
+ * RTX_ERR_INVALID: a null argument, x >= width or y >= height; RTX_ERR_STATE:
+ * no world or no frame. */
+typedef struct rtx_hit {
+    uint32_t hit; int32_t index; uint32_t front_face; uint32_t material;
+    float t, depth, p[3], normal[3], albedo[3], mat_param;
+    uint32_t reserved[2];
+} rtx_hit;
+RTX_API int rtx_pick(rtx_ctx *ctx, uint32_t x, uint32_t y, rtx_hit *out);
+/* The pixels that show chosen objects. d_surf: a whole-frame surf plane of the
+ * current frame's size (device); ids: host array of scene indices,
+ * 1 <= n <= 256; grow: 0..8; d_mask: width*height bytes in framebuffer order
+ * (device). mask[p] = 1 iff some pixel within Chebyshev distance `grow` of p,
+ * inside the image, hit a sphere whose index is in ids; else 0. A miss is
+ * never listed (an entry 0xffffffff names no sphere). *set (may be NULL)
+ * receives the number of set pixels; the call is synchronous when set is
+ * given, else asynchronous on the context stream. RTX_ERR_INVALID, before any
+ * HIP call: a null ctx, d_surf, ids or d_mask, n == 0, n > 256, grow > 8;
+ * RTX_ERR_STATE: no frame. */
+RTX_API int rtx_mask_from_ids(rtx_ctx *ctx, const void *d_surf, const uint32_t *ids, uint32_t n,
+                              uint32_t grow, void *d_mask, uint32_t *set);
+/* rtx_refine_adaptive with the "noisy" test replaced by the caller's mask
+ * (width*height bytes in framebuffer order, device; rtx_mask_from_ids writes
+ * one): pixel p is traced iff mask[p] != 0 and (max_samples == 0 or
+ * count_p + samples <= max_samples). Everything else is rtx_refine_adaptive's
+ * contract: the count / err maps are filled from a uniform state (count N,
+ * err +inf); each traced pixel's sum, seed, count, E, cost-map entry and
+ * framebuffer value are updated, every other pixel is untouched; one scheduled
+ * launch keyed by the cost map (rtx_refine_last_keys: CARRIED); no active
+ * pixel launches nothing; rtx_refined_samples advances only when something was
+ * traced; rtx_stats.samples counts active * samples. Whole frame only: it
+ * continues an existing whole-frame chain state for the current world and
+ * frame (from rtx_refine, rtx_refine_adaptive or rtx_refine_import) and never
+ * starts one. RTX_ERR_INVALID, before any HIP call: a null ctx or mask, and
+ * rtx_refine_adaptive's argument rules (samples == 0, max_samples nonzero and
+ * below samples, rtx_refined_samples + samples above 2^32 - 1,
+ * samples * depth >= 2^32, depth == 0, a per-sample RNG frame). RTX_ERR_STATE,
+ * before any HIP call: no world, no frame, no chain state for them, or a part
+ * state. Afterwards the counts are non-uniform: rtx_refine without reset
+ * refuses as after adaptive steps; rtx_refine_adaptive continues from the maps. */
+RTX_API int rtx_refine_masked(rtx_ctx *ctx, uint32_t samples, const void *d_mask,
+                              uint32_t max_samples, uint32_t *active);
 /* Device pointer of the chain state (width*height float4; a part state: its
  * rows * width), NULL if none. */
 RTX_API void *rtx_refine_state(rtx_ctx *ctx);

@@ -69,6 +69,7 @@ struct AppConfig {
     float aperture = 2.0f;
     bool simple_camera = false;            // Camera.h instead of ComputeViewVals
     float lens_aperture = 0.0f;            // > 0: thin lens (extension, §8f-3); 0 = reference pinhole
+    float focus_dist = 0.0f;               // > 0: the focus plane's distance; 0 = |cam_pos - cam_look_at| (reference)
     uint32_t rng_mode = RTX_RNG_CHAIN;
     bool lambert_guard = false;            // RTX_FRAME_LAMBERT_GUARD (extension, §8f-4); false = reference
     // Drive the library through the reference's own cbuffer bytes: LoadContent
@@ -142,6 +143,33 @@ public:
     // previous step's measured per-pixel cost; rtx_refine_set_keys). The
     // images are the same. With a group: every member.
     bool SetRefineKeys(int mode);
+    // What every pixel shows (rtx_features): the first hit of its centre ray as
+    // two planes of width * height float4, row 0 = bottom: geom = (normal,
+    // depth), surf = (albedo, sphere index); a miss is (0, 0, 0, +inf) and
+    // (0, 0, 0, -1). With a group: member 0, which holds the same world and frame.
+    bool Features(std::vector<float> &geom, std::vector<float> &surf);
+    // What is under pixel (x, y), y from the bottom row (rtx_pick). True also
+    // for a miss (out->hit == 0); false when the call itself failed.
+    bool Pick(uint32_t x, uint32_t y, rtx_hit *out);
+    // Click to focus: picks the pixel, takes the hit's plane depth
+    // dot(p - cam_pos, normalize(cam_look_at - cam_pos)) as the focus distance,
+    // rebuilds the frame through rtx_camera_look_at with it and sets the thin
+    // lens (rtx_camera_set_aperture); later Update calls keep both
+    // (AppConfig::focus_dist, lens_aperture). False on a miss (last_error()
+    // says so; nothing changes) and for the simple camera and the cbuffer path.
+    // A frame of other bytes ends a chain state: refine again afterwards.
+    bool FocusAt(uint32_t x, uint32_t y, float aperture);
+    float focus_dist() const { return m_cfg.focus_dist; }
+    // "Refine that": `samples` more samples of the pixels within Chebyshev
+    // distance `grow` (0..8) of one that shows a sphere of `ids` (1..256 scene
+    // indices), whose count stays within max_samples (0: no cap) — the feature
+    // planes, rtx_mask_from_ids and rtx_refine_masked. Needs a chain state
+    // (Refine, RefineAdaptive or LoadState first). *active (may be NULL): the
+    // pixels traced; *mask_pixels (may be NULL): the pixels the mask covers.
+    // Under a group it returns false and says why (whole frame on one context
+    // only); the app stays usable.
+    bool RefineMasked(uint32_t samples, const std::vector<uint32_t> &ids, uint32_t grow, uint32_t max_samples,
+                      uint32_t *active, uint32_t *mask_pixels = nullptr);
     // The chain state as a file (write_chain_state below), tagged with this
     // app's world and frame; LoadState refuses a file of another size, world
     // or frame (last_error() says which) and otherwise imports it

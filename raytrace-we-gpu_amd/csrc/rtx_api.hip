@@ -129,6 +129,11 @@ struct rtx_ctx {
     uint32_t *d_adapt = nullptr;
     size_t adapt_pixels = 0;
     bool adapt_valid = false, adapt_mixed = false;
+    // feature buffers (rtx_pick, rtx_mask_from_ids): scratch of feat_bytes
+    // bytes — 64 bytes of words (rtx_pick's record; the mask's set count),
+    // then the mask's listed bytes — grown on demand
+    unsigned char *d_feat = nullptr;
+    size_t feat_bytes = 0;
     // measurement
     unsigned long long *d_counters = nullptr;
     unsigned long long *d_wave_times = nullptr;  // diagnostic (rtx_debug_wave_times)
@@ -347,6 +352,7 @@ void rtx_destroy(rtx_ctx *c) {
     (void)hipFree(c->d_accum);
     (void)hipFree(c->d_chain);
     (void)hipFree(c->d_adapt);
+    (void)hipFree(c->d_feat);
     (void)hipFree(c->d_counters);
     (void)hipFree(c->d_wave_times);
     (void)hipFree(c->d_sched);
@@ -1438,12 +1444,17 @@ static uint32_t uniform_active(size_t px, uint32_t have, uint32_t samples, uint3
 }
 // The flags of a call over valid maps and their number (synchronous: the
 // 4-byte count comes back to the host, which sizes the launch by it). The
-// whole frame takes k_adaptive_mask, a part k_adaptive_mask_rows with d_halo.
+// whole frame takes k_adaptive_mask, a part k_adaptive_mask_rows with d_halo;
+// d_mask (rtx_refine_masked, whole frame): k_masked_flags, the caller's mask
+// in the place of the error test.
 static int adaptive_mask(rtx_ctx *c, const AdaptShape &s, uint32_t samples, float threshold, uint32_t max_samples,
-                         const void *d_halo, rtx::KAdaptive *a) {
+                         const void *d_halo, rtx::KAdaptive *a, const void *d_mask = nullptr) {
     *a = adapt_maps(c);
     hipError_t e;
-    if (s.nparts == 1)
+    if (d_mask)
+        e = rtx::launch_masked_flags(*a, static_cast<const uint8_t *>(d_mask), c->frame.width, c->frame.height, samples,
+                                     max_samples, c->stream);
+    else if (s.nparts == 1)
         e = rtx::launch_adaptive_mask(*a, c->frame.width, c->frame.height, samples, threshold, max_samples, c->stream);
     else
         e = rtx::launch_adaptive_mask_rows(*a, static_cast<const float *>(d_halo), c->frame.width, shape_rows(c, s),
@@ -1455,9 +1466,10 @@ static int adaptive_mask(rtx_ctx *c, const AdaptShape &s, uint32_t samples, floa
     return RTX_OK;
 }
 
-// rtx_refine_adaptive and rtx_refine_adaptive_rows (checked already).
+// rtx_refine_adaptive, rtx_refine_adaptive_rows and rtx_refine_masked (checked
+// already; d_mask: the masked call, which continues a whole-frame state).
 static int adaptive_impl(rtx_ctx *c, const AdaptShape &s, uint32_t samples, float threshold, uint32_t max_samples,
-                         int reset, const void *d_halo, void *d_out, uint32_t *active) {
+                         int reset, const void *d_halo, void *d_out, uint32_t *active, const void *d_mask = nullptr) {
     const uint32_t rows = shape_rows(c, s);
     if (rows == 0) {  // a part without rows: nothing to launch, the state stays
         if (active) *active = 0;
@@ -1490,7 +1502,7 @@ static int adaptive_impl(rtx_ctx *c, const AdaptShape &s, uint32_t samples, floa
     }
     rtx::KAdaptive ka;
     // (a uniform state reads no halo: a caller's buffer may hold anything then)
-    rc = adaptive_mask(c, s, samples, threshold, max_samples, uniform ? nullptr : d_halo, &ka);
+    rc = adaptive_mask(c, s, samples, threshold, max_samples, uniform ? nullptr : d_halo, &ka, d_mask);
     if (rc) return rc;
     if (active) *active = ka.active;
     if (ka.active == 0) {  // (never a fresh start: its errors are +inf and its counts 0)
@@ -1582,6 +1594,19 @@ int rtx_refine_pending_rows(rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint3
     if (rc) return rc;
     if (!active) return fail(RTX_ERR_INVALID, "rtx_refine_pending_rows: null active");
     return pending_impl(c, s, samples, threshold, max_samples, d_halo, active);
+}
+
+int rtx_refine_masked(rtx_ctx *c, uint32_t samples, const void *d_mask, uint32_t max_samples, uint32_t *active) {
+    const char *fn = "rtx_refine_masked";
+    if (!d_mask && c) return fail(RTX_ERR_INVALID, "rtx_refine_masked: null mask");
+    AdaptShape s = kWholeFrame;
+    // (the threshold plays no part: the mask stands in for the error test)
+    const int rc = adaptive_check(c, fn, &s, samples, 0.0f, max_samples, 0, nullptr, false, nullptr);
+    if (rc) return rc;
+    if (!chain_continues(c, s, 0))
+        return fail(RTX_ERR_STATE, "rtx_refine_masked: no whole-frame chain state for this world and frame (start one with "
+                                   "rtx_refine, rtx_refine_adaptive or rtx_refine_import)");
+    return adaptive_impl(c, s, samples, 0.0f, max_samples, 0, nullptr, nullptr, active, d_mask);
 }
 
 int rtx_refine_edges(rtx_ctx *c, void *d_edges) {
@@ -1781,6 +1806,120 @@ int rtx_copy_to_device(rtx_ctx *c, void *d_dst, const void *host, size_t bytes) 
     if (rc) return rc;
     RTX_HIP(hipMemcpyAsync(d_dst, host, bytes, hipMemcpyHostToDevice, c->stream));
     RTX_HIP(hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+
+// ---- first-hit feature buffers, picking, the id mask (rtx_features.h) --------
+static rtx::KFeatures features_of(const rtx_ctx *c, uint32_t rows, uint32_t tile_rows, uint32_t part, uint32_t nparts) {
+    const rtx_frame &f = c->frame;
+    rtx::KFeatures k{};
+    for (int i = 0; i < 3; ++i) {
+        k.org[i] = f.origin[i];
+        k.hor[i] = f.horizontal[i];
+        k.ver[i] = f.vertical[i];
+        k.llc[i] = f.lower_left[i];
+    }
+    k.img_w = f.img_w;
+    k.img_h = f.img_h;
+    k.width = f.width;
+    k.rows_local = rows;
+    k.tile_rows = tile_rows;
+    k.part = part;
+    k.nparts = nparts;
+    return k;
+}
+// The context's feature scratch: 64 bytes of words, then `more` bytes.
+static int ensure_feat(rtx_ctx *c, size_t more) {
+    const size_t need = 64 + more;
+    if (c->d_feat && c->feat_bytes >= need) return RTX_OK;
+    RTX_HIP(hipStreamSynchronize(c->stream));
+    (void)hipFree(c->d_feat);
+    c->d_feat = nullptr;
+    c->feat_bytes = 0;
+    RTX_HIP(hipMalloc(&c->d_feat, need));
+    c->feat_bytes = need;
+    return RTX_OK;
+}
+
+int rtx_features_rows(rtx_ctx *c, uint32_t tile_rows, uint32_t part, uint32_t nparts, void *d_geom, void *d_surf) {
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_features_rows: null ctx");
+    if (!d_geom && !d_surf) return fail(RTX_ERR_INVALID, "rtx_features_rows: both planes are NULL");
+    if (tile_rows == 0 || nparts == 0 || part >= nparts)
+        return fail(RTX_ERR_INVALID, "rtx_features_rows: bad partition (tile_rows, part, nparts)");
+    if (!c->have_world) return fail(RTX_ERR_STATE, "rtx_features_rows: no world uploaded");
+    if (!c->have_frame) return fail(RTX_ERR_STATE, "rtx_features_rows: no frame set");
+    const uint32_t rows = rtx_part_rows(c->frame.height, tile_rows, part, nparts);
+    if (rows == 0 || c->frame.width == 0) return RTX_OK;  // a part without rows: nothing to launch
+    int rc = set_device(c);
+    if (rc) return rc;
+    const hipError_t e = rtx::launch_features(scene_of(c), features_of(c, rows, tile_rows, part, nparts),
+                                              static_cast<float4 *>(d_geom), static_cast<float4 *>(d_surf), nullptr,
+                                              c->stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_features");
+    return RTX_OK;
+}
+
+int rtx_features(rtx_ctx *c, void *d_geom, void *d_surf) {
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_features: null ctx");
+    if (!d_geom && !d_surf) return fail(RTX_ERR_INVALID, "rtx_features: both planes are NULL");
+    return rtx_features_rows(c, 1, 0, 1, d_geom, d_surf);
+}
+
+int rtx_pick(rtx_ctx *c, uint32_t x, uint32_t y, rtx_hit *out) {
+    if (!c || !out) return fail(RTX_ERR_INVALID, "rtx_pick: null argument");
+    if (!c->have_world) return fail(RTX_ERR_STATE, "rtx_pick: no world uploaded");
+    if (!c->have_frame) return fail(RTX_ERR_STATE, "rtx_pick: no frame set");
+    if (x >= c->frame.width || y >= c->frame.height) return fail(RTX_ERR_INVALID, "rtx_pick: the pixel is outside the frame");
+    int rc = set_device(c);
+    if (rc) return rc;
+    rc = ensure_feat(c, 0);
+    if (rc) return rc;
+    // the planes' kernel on the one pixel: a 1 x 1 part whose only row is y
+    rtx::KFeatures k = features_of(c, 1, 1, y, c->frame.height);
+    k.width = 1;
+    k.x0 = x;
+    float4 *d = reinterpret_cast<float4 *>(c->d_feat);  // geom, surf, extra[2]
+    hipError_t e = rtx::launch_features(scene_of(c), k, d, d + 1, d + 2, c->stream);
+    float4 h[4];
+    if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return hip_fail(e, "rtx_pick");
+    std::memset(out, 0, sizeof *out);
+    out->index = (int32_t)h[1].w;
+    out->hit = out->index >= 0 ? 1u : 0u;
+    out->depth = h[0].w;
+    if (out->hit) {
+        out->front_face = h[3].x != 0.0f ? 1u : 0u;
+        out->material = (uint32_t)h[3].y;
+        out->t = h[2].w;
+        out->p[0] = h[2].x, out->p[1] = h[2].y, out->p[2] = h[2].z;
+        out->normal[0] = h[0].x, out->normal[1] = h[0].y, out->normal[2] = h[0].z;
+        out->albedo[0] = h[1].x, out->albedo[1] = h[1].y, out->albedo[2] = h[1].z;
+        out->mat_param = h[3].z;
+    }
+    return RTX_OK;
+}
+
+int rtx_mask_from_ids(rtx_ctx *c, const void *d_surf, const uint32_t *ids, uint32_t n, uint32_t grow, void *d_mask,
+                      uint32_t *set) {
+    if (!c || !d_surf || !ids || !d_mask) return fail(RTX_ERR_INVALID, "rtx_mask_from_ids: null argument");
+    if (n == 0 || n > rtx::kFeatureIdsMax) return fail(RTX_ERR_INVALID, "rtx_mask_from_ids: n outside 1 .. 256");
+    if (grow > rtx::kFeatureGrowMax) return fail(RTX_ERR_INVALID, "rtx_mask_from_ids: grow above 8");
+    if (!c->have_frame) return fail(RTX_ERR_STATE, "rtx_mask_from_ids: no frame set");
+    const size_t px = (size_t)c->frame.width * c->frame.height;
+    int rc = set_device(c);
+    if (rc) return rc;
+    rc = ensure_feat(c, px);
+    if (rc) return rc;
+    uint32_t *d_set = reinterpret_cast<uint32_t *>(c->d_feat);
+    const hipError_t e = rtx::launch_feature_mask(static_cast<const float4 *>(d_surf), c->frame.width, c->frame.height,
+                                                  ids, n, grow, c->d_feat + 64, static_cast<uint8_t *>(d_mask), d_set,
+                                                  c->stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_feature_mask");
+    if (set) {
+        RTX_HIP(hipMemcpyAsync(set, d_set, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        RTX_HIP(hipStreamSynchronize(c->stream));
+    }
     return RTX_OK;
 }
 

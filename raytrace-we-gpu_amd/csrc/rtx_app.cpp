@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <string>
 
 namespace rtx {
 
@@ -166,7 +167,7 @@ void RtxCSApp::Update() {
         rc = rtx_camera_simple(m_cfg.width, m_cfg.height, &m_frame);
     else
         rc = rtx_camera_look_at(m_cfg.cam_pos, m_cfg.cam_look_at, m_cfg.up, m_cfg.vfov, m_cfg.aspect,
-                                m_cfg.aperture, 0.0f, m_cfg.width, m_cfg.height, &m_frame);
+                                m_cfg.aperture, m_cfg.focus_dist, m_cfg.width, m_cfg.height, &m_frame);
     m_frame.rng_mode = m_cfg.rng_mode;
     m_frame.flags = m_cfg.lambert_guard ? RTX_FRAME_LAMBERT_GUARD : 0u;
     if (rc == RTX_OK && m_cfg.lens_aperture > 0.0f) rc = rtx_camera_set_aperture(&m_frame, m_cfg.lens_aperture);
@@ -241,6 +242,85 @@ bool RtxCSApp::SetRefineKeys(int mode) {
         }
     }
     return true;
+}
+
+bool RtxCSApp::Features(std::vector<float> &geom, std::vector<float> &surf) {
+    if (!m_ok) return false;
+    const size_t bytes = 4 * (size_t)m_frame.width * m_frame.height * sizeof(float);
+    void *d[2] = {nullptr, nullptr};
+    bool ok = rtx_alloc(m_ctx, bytes, &d[0]) == RTX_OK && rtx_alloc(m_ctx, bytes, &d[1]) == RTX_OK &&
+              rtx_features(m_ctx, d[0], d[1]) == RTX_OK;
+    if (ok) {
+        geom.resize(bytes / sizeof(float));
+        surf.resize(bytes / sizeof(float));
+        ok = rtx_copy_to_host(m_ctx, geom.data(), d[0], bytes) == RTX_OK &&
+             rtx_copy_to_host(m_ctx, surf.data(), d[1], bytes) == RTX_OK;
+    }
+    if (!ok) m_error = rtx_last_error();
+    for (void *p : d)
+        if (p) rtx_free(m_ctx, p);
+    return ok;
+}
+
+bool RtxCSApp::Pick(uint32_t x, uint32_t y, rtx_hit *out) {
+    if (!m_ok) return false;
+    if (rtx_pick(m_ctx, x, y, out) != RTX_OK) {
+        m_error = rtx_last_error();
+        return false;
+    }
+    return true;
+}
+
+bool RtxCSApp::FocusAt(uint32_t x, uint32_t y, float aperture) {
+    if (!m_ok) return false;
+    if (m_cfg.simple_camera || m_cfg.cbuffers) {
+        m_error = "FocusAt: needs the look-at camera (not the simple camera or the cbuffer path)";
+        return false;
+    }
+    rtx_hit h{};
+    if (!Pick(x, y, &h)) return false;
+    if (!h.hit) {
+        m_error = "FocusAt: nothing under pixel (" + std::to_string(x) + ", " + std::to_string(y) + ")";
+        return false;
+    }
+    // the hit's distance along the view axis: the focus plane is normal to it
+    float w[3], len2 = 0.0f, along = 0.0f;
+    for (int k = 0; k < 3; ++k) {
+        w[k] = m_cfg.cam_look_at[k] - m_cfg.cam_pos[k];
+        len2 += w[k] * w[k];
+    }
+    const float len = std::sqrt(len2);
+    for (int k = 0; k < 3; ++k) along += (h.p[k] - m_cfg.cam_pos[k]) * (w[k] / len);
+    if (!(along > 0.0f) || !(aperture >= 0.0f)) {
+        m_error = "FocusAt: no focus plane in front of the camera, or a negative aperture";
+        return false;
+    }
+    m_cfg.focus_dist = along;
+    m_cfg.lens_aperture = aperture;
+    Update();
+    return m_ok;
+}
+
+bool RtxCSApp::RefineMasked(uint32_t samples, const std::vector<uint32_t> &ids, uint32_t grow, uint32_t max_samples,
+                            uint32_t *active, uint32_t *mask_pixels) {
+    if (!m_ok) return false;
+    if (m_group) {
+        m_error = "RefineMasked: masked refinement runs on one context over the whole frame, not on a group";
+        return false;
+    }
+    const size_t px = (size_t)m_frame.width * m_frame.height;
+    void *d_surf = nullptr, *d_mask = nullptr;
+    uint32_t set = 0;
+    const bool ok = rtx_alloc(m_ctx, px * 4 * sizeof(float), &d_surf) == RTX_OK && rtx_alloc(m_ctx, px, &d_mask) == RTX_OK &&
+                    rtx_features(m_ctx, nullptr, d_surf) == RTX_OK &&
+                    rtx_mask_from_ids(m_ctx, d_surf, ids.data(), (uint32_t)ids.size(), grow, d_mask, &set) == RTX_OK &&
+                    rtx_refine_masked(m_ctx, samples, d_mask, max_samples, active) == RTX_OK &&
+                    rtx_sync(m_ctx) == RTX_OK;  // the mask is read by the launch: freed after it
+    if (!ok) m_error = rtx_last_error();
+    if (mask_pixels) *mask_pixels = set;
+    if (d_surf) rtx_free(m_ctx, d_surf);
+    if (d_mask) rtx_free(m_ctx, d_mask);
+    return ok;
 }
 
 uint32_t RtxCSApp::RefinedSamples() const {

@@ -13,6 +13,21 @@
 //           [--refine S1,S2,...] [--save-state FILE] [--load-state FILE]
 //           [--refine-keys prepass|carried]
 //           [--refine-adaptive S,THRESHOLD[,MAX] --steps K] [--dump-counts FILE]
+//           [--aov PREFIX] [--pick X,Y] [--focus-at X,Y] [--refine-ids S,ID[,ID...] --grow G --steps K]
+// --aov PREFIX writes the first-hit feature buffers of the frame
+// (rtx_features) as PREFIX_normal.pfm, PREFIX_depth.pfm, PREFIX_albedo.pfm and
+// PREFIX_id.pfm (scalars in all three channels; row 0 is the bottom, as --pfm;
+// a miss has depth +inf and id -1). --pick X,Y (Y from the bottom row) adds a
+// "pick" object — what rtx_pick reports for the pixel — to the JSON line.
+// --focus-at X,Y, with --aperture A, puts the thin lens's focus plane on what
+// that pixel shows before anything is rendered (RtxCSApp::FocusAt) and exits
+// nonzero when the pixel shows nothing; the JSON line carries "focus_dist".
+// --refine-ids S,ID[,ID...] with --grow G (0..8, default 0) and --steps K runs K
+// masked steps of S samples (rtx_refine_masked) over the pixels that show the
+// spheres ID... (grown by G pixels), after the --refine steps or the
+// --load-state of the same run: it needs one of them, on one context. The
+// first output line is then {"refine_masked": ...} with each step's active
+// count; --dump-counts works after it.
 // --refine S1,S2,... refines the image along the reference's own RNG chain,
 // one rtx_refine per entry (--spp and --frames are not used): after the last
 // step the image is the plain render's at spp = S1 + S2 + ... (plus a loaded
@@ -83,7 +98,9 @@ static void usage() {
                  "               [--split rows|frames]\n"
                  "               [--refine S1,S2,...] [--save-state FILE] [--load-state FILE]\n"
                  "               [--refine-keys prepass|carried]\n"
-                 "               [--refine-adaptive S,THRESHOLD[,MAX] --steps K] [--dump-counts FILE]\n");
+                 "               [--refine-adaptive S,THRESHOLD[,MAX] --steps K] [--dump-counts FILE]\n"
+                 "               [--aov PREFIX] [--pick X,Y] [--focus-at X,Y]\n"
+                 "               [--refine-ids S,ID[,ID...] --grow G --steps K]\n");
 }
 
 int main(int argc, char **argv) {
@@ -110,6 +127,10 @@ int main(int argc, char **argv) {
     float ad_threshold = 0.0f;
     int ad_steps = 1;              // --steps
     std::string dump_counts;       // --dump-counts
+    std::string aov;               // --aov PREFIX
+    int pick_xy[2] = {-1, -1}, focus_xy[2] = {-1, -1};  // --pick / --focus-at X,Y (-1: not given)
+    uint32_t mask_samples = 0, mask_grow = 0;  // --refine-ids S,ID[,ID...] (S 0: not given), --grow
+    std::vector<uint32_t> mask_ids;
     std::vector<int> devices;  // non-empty: a group
     int gather = RTX_GATHER_AUTO;
     bool group_opts = false;   // --gather / --tile-rows given
@@ -165,6 +186,36 @@ int main(int argc, char **argv) {
             ad_max = (uint32_t)m;
         }
         else if (a == "--steps") ad_steps = std::atoi(next());
+        else if (a == "--aov") aov = next();
+        else if (a == "--pick" || a == "--focus-at") {
+            int *xy = a == "--pick" ? pick_xy : focus_xy;
+            char tail = 0;
+            if (std::sscanf(next(), "%d,%d%c", &xy[0], &xy[1], &tail) != 2 || xy[0] < 0 || xy[1] < 0) {
+                usage();
+                return 2;
+            }
+        }
+        else if (a == "--grow") mask_grow = (uint32_t)std::atoi(next());
+        else if (a == "--refine-ids") {
+            std::vector<uint32_t> v;
+            const std::string list = next();
+            for (size_t pos = 0; pos <= list.size();) {
+                const size_t comma = std::min(list.find(',', pos), list.size());
+                const std::string item = list.substr(pos, comma - pos);
+                if (item.empty() || item.size() > 9 || item.find_first_not_of("0123456789") != std::string::npos) {
+                    usage();
+                    return 2;
+                }
+                v.push_back((uint32_t)std::strtoul(item.c_str(), nullptr, 10));
+                pos = comma + 1;
+            }
+            if (v.size() < 2 || v[0] == 0u) {
+                usage();
+                return 2;
+            }
+            mask_samples = v[0];
+            mask_ids.assign(v.begin() + 1, v.end());
+        }
         else if (a == "--dump-counts") dump_counts = next();
         else if (a == "--refine-keys") {
             const std::string m = next();
@@ -274,11 +325,25 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "rtx_cli: --refine-adaptive takes --steps K >= 1, without --refine and --load-state\n");
         return 2;
     }
-    if (!dump_counts.empty() && !adaptive) {
-        std::fprintf(stderr, "rtx_cli: --dump-counts needs --refine-adaptive\n");
+    const bool masked = mask_samples != 0u;
+    if (masked && refine.empty() && load_state.empty()) {
+        std::fprintf(stderr, "rtx_cli: --refine-ids continues a chain state: it needs --refine or --load-state in the "
+                             "same run\n");
         return 2;
     }
-    const bool refining = !refine.empty() || adaptive;
+    if (masked && (adaptive || ad_steps < 1 || !devices.empty())) {
+        std::fprintf(stderr, "rtx_cli: --refine-ids takes --steps K >= 1, without --refine-adaptive, on one context\n");
+        return 2;
+    }
+    if (!dump_counts.empty() && !adaptive && !masked) {
+        std::fprintf(stderr, "rtx_cli: --dump-counts needs --refine-adaptive or --refine-ids\n");
+        return 2;
+    }
+    if (focus_xy[0] >= 0 && !(cfg.lens_aperture > 0.0f)) {
+        std::fprintf(stderr, "rtx_cli: --focus-at needs --aperture A > 0\n");
+        return 2;
+    }
+    const bool refining = !refine.empty() || adaptive || masked;
     if ((!save_state.empty() || !load_state.empty()) && !refining) {
         std::fprintf(stderr, "rtx_cli: --save-state and --load-state need --refine\n");
         return 2;
@@ -306,6 +371,58 @@ int main(int argc, char **argv) {
         return 1;
     }
     app.Update();
+    std::string extra;  // further fields of the JSON line: "focus_dist", "pick"
+    if (focus_xy[0] >= 0) {
+        if (!app.FocusAt((uint32_t)focus_xy[0], (uint32_t)focus_xy[1], cfg.lens_aperture)) {
+            std::fprintf(stderr, "rtx_cli: --focus-at failed: %s\n", app.last_error().c_str());
+            return 1;
+        }
+        char buf[64];
+        std::snprintf(buf, sizeof buf, ", \"focus_dist\": %.9g", (double)app.focus_dist());
+        extra += buf;
+    }
+    if (pick_xy[0] >= 0) {
+        rtx_hit h{};
+        if (!app.Pick((uint32_t)pick_xy[0], (uint32_t)pick_xy[1], &h)) {
+            std::fprintf(stderr, "rtx_cli: --pick failed: %s\n", app.last_error().c_str());
+            return 1;
+        }
+        char buf[640];
+        // (a miss's depth is +inf, which JSON cannot hold: null)
+        char depth[32];
+        if (h.hit) std::snprintf(depth, sizeof depth, "%.9g", (double)h.depth);
+        else std::snprintf(depth, sizeof depth, "null");
+        std::snprintf(buf, sizeof buf,
+                      ", \"pick\": {\"x\": %d, \"y\": %d, \"hit\": %u, \"index\": %d, \"front_face\": %u, "
+                      "\"material\": %u, \"t\": %.9g, \"depth\": %s, \"p\": [%.9g, %.9g, %.9g], "
+                      "\"normal\": [%.9g, %.9g, %.9g], \"albedo\": [%.9g, %.9g, %.9g], \"mat_param\": %.9g}",
+                      pick_xy[0], pick_xy[1], h.hit, h.index, h.front_face, h.material, (double)h.t, depth,
+                      (double)h.p[0], (double)h.p[1], (double)h.p[2], (double)h.normal[0], (double)h.normal[1],
+                      (double)h.normal[2], (double)h.albedo[0], (double)h.albedo[1], (double)h.albedo[2],
+                      (double)h.mat_param);
+        extra += buf;
+    }
+    if (!aov.empty()) {
+        std::vector<float> geom, surf;
+        if (!app.Features(geom, surf)) {
+            std::fprintf(stderr, "rtx_cli: --aov failed: %s\n", app.last_error().c_str());
+            return 1;
+        }
+        const size_t px = (size_t)cfg.width * cfg.height;
+        std::vector<float> depth(4 * px), id(4 * px);
+        for (size_t i = 0; i < px; ++i)
+            for (int c = 0; c < 4; ++c) {
+                depth[4 * i + c] = geom[4 * i + 3];
+                id[4 * i + c] = surf[4 * i + 3];
+            }
+        if (!rtx::write_pfm(aov + "_normal.pfm", geom.data(), cfg.width, cfg.height) ||
+            !rtx::write_pfm(aov + "_depth.pfm", depth.data(), cfg.width, cfg.height) ||
+            !rtx::write_pfm(aov + "_albedo.pfm", surf.data(), cfg.width, cfg.height) ||
+            !rtx::write_pfm(aov + "_id.pfm", id.data(), cfg.width, cfg.height)) {
+            std::fprintf(stderr, "rtx_cli: --aov: cannot write %s_*.pfm\n", aov.c_str());
+            return 1;
+        }
+    }
     uint32_t loaded_samples = 0;
     if (refining) {
         if (refine_keys >= 0 && !app.SetRefineKeys(refine_keys)) {
@@ -352,6 +469,18 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "rtx_cli: adaptive step %d: %u active\n", k + 1, n);
         if (n == 0u) break;  // nothing is noisy any more (or every pixel is at its cap)
         ad_active.push_back(n);
+    }
+    std::vector<uint32_t> mask_active;  // --refine-ids: pixels traced per step
+    uint32_t mask_pixels = 0;
+    for (int k = 0; masked && k < ad_steps; ++k) {
+        app.Update();
+        uint32_t n = 0;
+        if (!app.RefineMasked(mask_samples, mask_ids, mask_grow, 0, &n, &mask_pixels)) {
+            std::fprintf(stderr, "rtx_cli: --refine-ids failed: %s\n", app.last_error().c_str());
+            return 1;
+        }
+        std::fprintf(stderr, "rtx_cli: masked step %d: %u active of %u masked\n", k + 1, n, mask_pixels);
+        mask_active.push_back(n);
     }
     for (int k = 0; k < frames && !split_frames && !refining; ++k) {
         app.Update();
@@ -431,7 +560,8 @@ int main(int argc, char **argv) {
                     frames, wall, st.kernel_ms, (double)st.samples / wall / 1e6, (unsigned long long)st.segments,
                     (unsigned long long)st.sphere_tests, members, devs.c_str(),
                     rtx_group_gather_mode(grp) == RTX_GATHER_RCCL ? "rccl" : "copy", rccl.c_str(), split.c_str(),
-                    per.c_str(), gather_ms, split_frames ? "fold_ms" : "deinterleave_ms", deint_ms, ref.c_str());
+                    per.c_str(), gather_ms, split_frames ? "fold_ms" : "deinterleave_ms", deint_ms,
+                    (ref + extra).c_str());
         if (!save_state.empty() && !app.SaveState(save_state)) {
             std::fprintf(stderr, "rtx_cli: --save-state failed: %s\n", app.last_error().c_str());
             return 1;
@@ -444,8 +574,9 @@ int main(int argc, char **argv) {
         std::string steps;
         for (size_t k = 0; k < refine.size(); ++k) steps += (k ? ", " : "") + std::to_string(refine[k]);
         for (size_t k = 0; k < ad_active.size(); ++k) steps += (k ? ", " : "") + std::to_string(ad_samples);
+        for (size_t k = 0; k < mask_active.size(); ++k) steps += (steps.empty() ? "" : ", ") + std::to_string(mask_samples);
         std::vector<uint32_t> counts;
-        if (adaptive) {
+        if (adaptive || masked) {
             counts.resize((size_t)cfg.width * cfg.height);
             if (rtx_refine_counts(app.context(), counts.data(), counts.size() * sizeof(uint32_t)) != RTX_OK) {
                 std::fprintf(stderr, "rtx_cli: counts failed: %s\n", rtx_last_error());
@@ -453,9 +584,18 @@ int main(int argc, char **argv) {
             }
             std::string act;
             for (size_t k = 0; k < ad_active.size(); ++k) act += (k ? ", " : "") + std::to_string(ad_active[k]);
-            std::printf("{\"refine_adaptive\": {\"samples\": %u, \"threshold\": %.9g, \"max_samples\": %u, "
-                        "\"steps\": %d, \"steps_run\": %zu, \"active\": [%s]}}\n",
-                        ad_samples, (double)ad_threshold, ad_max, ad_steps, ad_active.size(), act.c_str());
+            if (adaptive)
+                std::printf("{\"refine_adaptive\": {\"samples\": %u, \"threshold\": %.9g, \"max_samples\": %u, "
+                            "\"steps\": %d, \"steps_run\": %zu, \"active\": [%s]}}\n",
+                            ad_samples, (double)ad_threshold, ad_max, ad_steps, ad_active.size(), act.c_str());
+            if (masked) {
+                std::string ids;
+                for (size_t k = 0; k < mask_ids.size(); ++k) ids += (k ? ", " : "") + std::to_string(mask_ids[k]);
+                for (size_t k = 0; k < mask_active.size(); ++k) act += (k ? ", " : "") + std::to_string(mask_active[k]);
+                std::printf("{\"refine_masked\": {\"samples\": %u, \"ids\": [%s], \"grow\": %u, \"steps\": %d, "
+                            "\"steps_run\": %zu, \"mask_pixels\": %u, \"active\": [%s]}}\n",
+                            mask_samples, ids.c_str(), mask_grow, ad_steps, mask_active.size(), mask_pixels, act.c_str());
+            }
             if (!dump_counts.empty()) {
                 std::vector<float> img(4 * counts.size());
                 for (size_t i = 0; i < counts.size(); ++i)
@@ -466,11 +606,12 @@ int main(int argc, char **argv) {
         std::printf("{\"width\": %u, \"height\": %u, \"depth\": %u, \"spheres\": %u, \"cbuffers\": %s, "
                     "\"refine\": [%s], \"loaded_samples\": %u, \"refined_samples\": %u, \"wall_s\": %.6f, "
                     "\"kernel_ms\": %.4f, \"msamples_per_s\": %.3f, \"segments\": %llu, \"sphere_tests\": %llu, "
-                    "\"refine_keys\": \"%s\"}\n",
+                    "\"refine_keys\": \"%s\"%s}\n",
                     cfg.width, cfg.height, cfg.depth, app.sphere_count(), cfg.cbuffers ? "true" : "false",
                     steps.c_str(), loaded_samples, rtx_refined_samples(app.context()), wall, st.kernel_ms,
                     (double)st.samples / wall / 1e6, (unsigned long long)st.segments,
-                    (unsigned long long)st.sphere_tests, refine_keys == RTX_REFINE_KEYS_CARRIED ? "carried" : "prepass");
+                    (unsigned long long)st.sphere_tests, refine_keys == RTX_REFINE_KEYS_CARRIED ? "carried" : "prepass",
+                    extra.c_str());
         if (!save_state.empty() && !app.SaveState(save_state)) {
             std::fprintf(stderr, "rtx_cli: --save-state failed: %s\n", app.last_error().c_str());
             return 1;
@@ -479,11 +620,11 @@ int main(int argc, char **argv) {
         rtx_get_stats(app.context(), &st);
         std::printf("{\"width\": %u, \"height\": %u, \"spp\": %u, \"depth\": %u, \"spheres\": %u, "
                     "\"cbuffers\": %s, \"frames\": %d, \"wall_s\": %.6f, \"kernel_ms\": %.4f, \"msamples_per_s\": %.3f, "
-                    "\"segments\": %llu, \"sphere_tests\": %llu}\n",
+                    "\"segments\": %llu, \"sphere_tests\": %llu%s}\n",
                     cfg.width, cfg.height, cfg.spp, cfg.depth, app.sphere_count(), cfg.cbuffers ? "true" : "false",
                     frames, wall,
                     st.kernel_ms, (double)st.samples / wall / 1e6, (unsigned long long)st.segments,
-                    (unsigned long long)st.sphere_tests);
+                    (unsigned long long)st.sphere_tests, extra.c_str());
     }
     if (!pfm.empty() || !ppm.empty()) {
         std::vector<float> img;

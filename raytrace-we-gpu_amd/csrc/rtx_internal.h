@@ -8,6 +8,7 @@
 #include "rtx_grid.h"
 #include "rtx_refine_keys.h"  // kCostBuckets, kCostSpp, kCostSppLarge, kLptMinSpp; the carried key
 #include "rtx_adaptive.h"     // the adaptive rule: a pixel's error estimate, the activity mask
+#include "rtx_features.h"     // the feature buffers' ray and depth, the id mask, the masked rule
 
 struct rtx_ctx;  // include/rtx.h
 
@@ -310,6 +311,30 @@ hipError_t launch_chain_image_counts(const float4 *chain, const uint32_t *count,
 hipError_t launch_debug_hit_world(const KScene &s, const float *rays, uint32_t nrays,
                                   float t_min, float t_max, uint32_t start_block, float *out,
                                   hipStream_t stream);
+// First-hit feature buffers (rtx_features.h; include/rtx.h rtx_features): the
+// frame's view rows and the part the launch covers — local pixel (xl, lr) of
+// rows_local x width is global pixel (x0 + xl, lane_pixel's row of lr).
+struct KFeatures {
+    float org[3], hor[3], ver[3], llc[3];
+    float img_w, img_h;
+    uint32_t width, rows_local;
+    uint32_t tile_rows, part, nparts;
+    uint32_t x0;
+};
+// k_features: geom / surf (rows_local * width float4 in the part's row order;
+// NULL: skipped), extra (NULL, or per pixel two float4: (p.xyz, t),
+// (front_face, material code, mat_values.w, 0): rtx_pick).
+hipError_t launch_features(const KScene &s, const KFeatures &f, float4 *geom, float4 *surf, float4 *extra,
+                           hipStream_t stream);
+// k_feature_listed + k_feature_mask (rtx_mask_from_ids): ids is host memory
+// (1 <= n <= kFeatureIdsMax), listed a width * height byte scratch, *n_set
+// (device, zeroed here first) the number of set pixels.
+hipError_t launch_feature_mask(const float4 *surf, uint32_t width, uint32_t height, const uint32_t *ids, uint32_t n,
+                               uint32_t grow, uint8_t *listed, uint8_t *mask, uint32_t *n_set, hipStream_t stream);
+// k_masked_flags (rtx_refine_masked): launch_adaptive_mask with the caller's
+// mask (width * rows bytes, device) in the place of the error test.
+hipError_t launch_masked_flags(const KAdaptive &a, const uint8_t *mask, uint32_t width, uint32_t rows, uint32_t samples,
+                               uint32_t max_samples, hipStream_t stream);
 // hit_world alone at the render's occupancy (rtx_debug_scan_rate); *waves: the grid's waves.
 // Scenes that fit the coop's LDS copy (the C2 kernels), non-empty frames only:
 bool debug_scan_rate_supported(const KParams &p);

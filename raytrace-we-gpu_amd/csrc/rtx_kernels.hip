@@ -3757,6 +3757,93 @@ __global__ void __launch_bounds__(kRB) k_debug_hit_world_coop(const KScene S, co
     debug_record(S, o, d, best, min(idx, (int)S.n - 1), out + 10 * (size_t)i);
 }
 
+// ---- first-hit feature buffers (rtx_features, rtx_pick; rtx_features.h) -----
+// One lane per pixel, one segment per lane: the pixel-centre ray's first hit
+// through the scan path the render's lane mode takes for the scene — the
+// layout and layer grid (small scenes), the culled scan (scenes above
+// kScanPfMin with the culled layout), the linear scan (rtx_set_scan_mode) —
+// and debug_record's operations on it. A wave's 64 lanes are an 8 x 8 patch of
+// the part's local rows (lane = 8 * row + column): the lane-mode scan costs
+// the union of its lanes' candidate blocks (the grid mask is the OR of the
+// lanes', the culled scan visits a block when any lane's line passes its
+// bound), and a patch's rays stay closer together than 64 pixels of a row.
+// The spheres come from HBM / L2: with one ray per lane a workgroup-wide LDS
+// copy (up to 10 KiB staged by every workgroup) would cost more than the few
+// candidates each lane resolves. A lane outside the image or the part leaves
+// before the scan; the wave's helpers count the lanes that arrive (__ballot).
+// Reads the scene and the frame constants, writes the planes, nothing else.
+__global__ void __launch_bounds__(kRB) k_features(const KScene S, const KFeatures F, float4 *__restrict__ geom,
+                                                  float4 *__restrict__ surf, float4 *__restrict__ extra) {
+    __shared__ uint32_t list[list_bytes<true>() > kListBytes ? list_bytes<true>() / sizeof(uint32_t)
+                                                             : kListBytes / sizeof(uint32_t)];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t patch = blockIdx.x * (kRB / 64u) + threadIdx.x / 64u;
+    const uint32_t px_tiles = (F.width + 7u) / 8u;
+    const uint32_t ty = patch / px_tiles, tx = patch - ty * px_tiles;
+    const uint32_t xl = tx * 8u + (lane & 7u), lr = ty * 8u + (lane >> 3);
+    if (xl >= F.width || lr >= F.rows_local) return;
+    const uint32_t j = lr / F.tile_rows;
+    const uint32_t x = F.x0 + xl, y = (j * F.nparts + F.part) * F.tile_rows + (lr - j * F.tile_rows);
+    float dv[3];
+    feature_ray(F.org, F.hor, F.ver, F.llc, F.img_w, F.img_h, x, y, dv);
+    const f3 o = mk3(F.org[0], F.org[1], F.org[2]);
+    const f3 d = mk3(dv[0], dv[1], dv[2]);
+    const float a = dir_len2(d);
+    const float inv_a = 1.0f / a;
+    float best = __uint_as_float(0x7f800000u);
+    const int idx = min((S.cpre && S.n_pad > kScanPfMin) ? hit_world_culled(S, o, d, a, inv_a, kTMin, best, list)
+                        : S.n_pad > kScanPfMin           ? hit_world_pre<true>(S, o, d, a, inv_a, kTMin, best, list)
+                                                         : hit_world_pre<false>(S, o, d, a, inv_a, kTMin, best, list),
+                        (int)S.n - 1);
+    float r[10];
+    debug_record(S, o, d, best, idx, r);
+    const size_t i = (size_t)lr * F.width + xl;
+    const bool hit = idx >= 0;
+    const float4 mv = hit ? S.mval[idx] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (geom)
+        geom[i] = hit ? make_float4(r[5], r[6], r[7], feature_depth(best, dv, [](float v) { return sqrt_rn(v); }))
+                      : make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0x7f800000u));
+    if (surf) surf[i] = hit ? make_float4(mv.x, mv.y, mv.z, (float)idx) : make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    if (extra) {  // rtx_pick: p and t; front_face, the material code and its parameter
+        extra[2 * i] = make_float4(r[2], r[3], r[4], r[1]);
+        extra[2 * i + 1] = make_float4(r[8], hit ? (float)S.mtype[idx] : 0.0f, mv.w, 0.0f);
+    }
+}
+
+// rtx_mask_from_ids, two passes (rtx_features.h): which pixels are listed, then
+// the Chebyshev growth and the number of set pixels (one atomic per wave that
+// has any). The id list travels as a kernel argument.
+struct KIdList {
+    uint32_t id[kFeatureIdsMax];
+};
+__global__ void __launch_bounds__(kBlock) k_feature_listed(const float4 *__restrict__ surf, uint32_t npix,
+                                                           const KIdList ids, uint32_t n, uint8_t *__restrict__ listed) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < npix) listed[i] = feature_id_listed(surf[i].w, ids.id, n) ? 1u : 0u;
+}
+__global__ void __launch_bounds__(kBlock) k_feature_mask(const uint8_t *__restrict__ listed, uint32_t width,
+                                                         uint32_t height, uint32_t grow, uint8_t *__restrict__ mask,
+                                                         uint32_t *__restrict__ n_set) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const bool in = i < width * height;
+    const bool on = in && feature_mask_grown(listed, i, width, height, grow);
+    if (in) mask[i] = on ? 1u : 0u;
+    const uint64_t b = __ballot(on);
+    if (b != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(n_set, (uint32_t)__popcll(b));
+}
+// rtx_refine_masked's flags: k_adaptive_mask with the caller's mask in the
+// place of the error test (rtx_features.h masked_active).
+__global__ void __launch_bounds__(kBlock) k_masked_flags(const uint8_t *__restrict__ mask,
+                                                         const uint32_t *__restrict__ count, uint32_t npix,
+                                                         uint32_t samples, uint32_t max_samples,
+                                                         uint8_t *__restrict__ flags, uint32_t *__restrict__ n_active) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const bool on = i < npix && masked_active(mask[i], count[i], samples, max_samples);
+    if (i < npix) flags[i] = on ? 1u : 0u;
+    const uint64_t b = __ballot(on);
+    if (b != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(n_active, (uint32_t)__popcll(b));
+}
+
 // Issue-rate probe of hit_world's own instruction mix (rtx_debug_scan_rate,
 // VERDICT r4 item 3): a full-occupancy grid of the render's shape (same
 // workgroup size, register budget and LDS: list, coop slots, the scene's LDS
@@ -4402,6 +4489,39 @@ hipError_t launch_debug_hit_world(const KScene &s, const float *rays, uint32_t n
     }
     hipLaunchKernelGGL(k_debug_hit_world, dim3(ceil_div(nrays, kRB)), dim3(kRB), 0, stream, s,
                        rays, nrays, t_min, t_max, start_block, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_features(const KScene &s, const KFeatures &f, float4 *geom, float4 *surf, float4 *extra,
+                           hipStream_t stream) {
+    if (f.width == 0 || f.rows_local == 0) return hipSuccess;
+    const uint64_t patches = (uint64_t)ceil_div(f.width, 8u) * ceil_div(f.rows_local, 8u);
+    hipLaunchKernelGGL(k_features, dim3(ceil_div(patches, kRB / 64u)), dim3(kRB), 0, stream, s, f, geom, surf, extra);
+    return hipGetLastError();
+}
+
+hipError_t launch_feature_mask(const float4 *surf, uint32_t width, uint32_t height, const uint32_t *ids, uint32_t n,
+                               uint32_t grow, uint8_t *listed, uint8_t *mask, uint32_t *n_set, hipStream_t stream) {
+    const uint64_t npix = (uint64_t)width * height;
+    if (n == 0 || n > kFeatureIdsMax || grow > kFeatureGrowMax) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(n_set, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess || npix == 0) return e;
+    KIdList l{};
+    for (uint32_t k = 0; k < n; ++k) l.id[k] = ids[k];
+    hipLaunchKernelGGL(k_feature_listed, dim3(ceil_div(npix, kBlock)), dim3(kBlock), 0, stream, surf, (uint32_t)npix, l,
+                       n, listed);
+    hipLaunchKernelGGL(k_feature_mask, dim3(ceil_div(npix, kBlock)), dim3(kBlock), 0, stream, listed, width, height,
+                       grow, mask, n_set);
+    return hipGetLastError();
+}
+
+hipError_t launch_masked_flags(const KAdaptive &a, const uint8_t *mask, uint32_t width, uint32_t rows, uint32_t samples,
+                               uint32_t max_samples, hipStream_t stream) {
+    const uint64_t npix = (uint64_t)width * rows;
+    hipError_t e = hipMemsetAsync(a.n_active, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess || npix == 0) return e;
+    hipLaunchKernelGGL(k_masked_flags, dim3(ceil_div(npix, kBlock)), dim3(kBlock), 0, stream, mask, a.count,
+                       (uint32_t)npix, samples, max_samples, a.flags, a.n_active);
     return hipGetLastError();
 }
 

@@ -109,6 +109,13 @@ class rtx_scene_info(C.Structure):
                 ("reserved", C.c_uint32 * 4)]
 
 
+class rtx_hit(C.Structure):
+    """What a pixel shows (include/rtx.h rtx_hit)."""
+    _fields_ = [("hit", C.c_uint32), ("index", C.c_int32), ("front_face", C.c_uint32), ("material", C.c_uint32),
+                ("t", C.c_float), ("depth", C.c_float), ("p", C.c_float * 3), ("normal", C.c_float * 3),
+                ("albedo", C.c_float * 3), ("mat_param", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 _lib = None
 
 
@@ -164,6 +171,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_refine_edges": (C.c_int, [ctx, vp]),
         "rtx_refine_counts_rows": (C.c_int, [ctx, C.POINTER(u32), C.c_size_t]),
         "rtx_refine_error_rows": (C.c_int, [ctx, f, C.c_size_t]),
+        "rtx_features": (C.c_int, [ctx, vp, vp]),
+        "rtx_features_rows": (C.c_int, [ctx, u32, u32, u32, vp, vp]),
+        "rtx_pick": (C.c_int, [ctx, u32, u32, C.POINTER(rtx_hit)]),
+        "rtx_mask_from_ids": (C.c_int, [ctx, vp, C.POINTER(u32), u32, u32, vp, C.POINTER(u32)]),
+        "rtx_refine_masked": (C.c_int, [ctx, u32, vp, u32, C.POINTER(u32)]),
         "rtx_camera_set_aperture": (C.c_int, [C.POINTER(rtx_frame), C.c_float]),
         "rtx_part_rows": (u32, [u32, u32, u32, u32]),
         "rtx_deinterleave_rows": (C.c_int, [ctx, vp, u32, u32, u32, u32, vp]),
@@ -229,6 +241,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     optional |= {"rtx_render_sum", "rtx_fold_frames"}            # ... with rtx_group_accumulate
     optional |= {n for n in sig if n.startswith("rtx_refine")}   # ... probe "rtx_refine"
     optional |= {"rtx_adaptive_error"}                           # ... with rtx_refine_adaptive
+    optional |= {"rtx_features", "rtx_features_rows", "rtx_pick", "rtx_mask_from_ids"}  # ... probe "rtx_features"
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -654,6 +667,63 @@ class Context:
         out = np.empty((self._state_rows(), self.frame.width), np.float32)
         _check(self._lib.rtx_refine_error_rows(self._h, _fptr(out), out.nbytes), "rtx_refine_error_rows", self._lib)
         return out
+
+    def features_rows(self, tile_rows: int, part: int, nparts: int, d_geom: int = 0, d_surf: int = 0):
+        """The first-hit feature planes of the rows of `part` of `nparts` into
+        device buffers of rows x W float4 (0: that plane is skipped),
+        asynchronously (rtx_features_rows)."""
+        _check(self._lib.rtx_features_rows(self._h, tile_rows, part, nparts, C.c_void_p(d_geom or 0),
+                                           C.c_void_p(d_surf or 0)), "rtx_features_rows", self._lib)
+
+    def features(self):
+        """(geom, surf), two (H, W, 4) float32 arrays, row 0 = bottom: the first
+        hit of every pixel's centre ray. geom = (normal, depth), (0, 0, 0, +inf)
+        on a miss; surf = (albedo, sphere index), (0, 0, 0, -1) on a miss
+        (rtx_features)."""
+        f = self.frame
+        g, s = self.alloc((f.height, f.width, 4)), self.alloc((f.height, f.width, 4))
+        try:
+            _check(self._lib.rtx_features(self._h, C.c_void_p(g.ptr), C.c_void_p(s.ptr)), "rtx_features", self._lib)
+            return g.numpy(), s.numpy()
+        finally:
+            g.free()
+            s.free()
+
+    def pick(self, x: int, y: int) -> dict:
+        """What is under pixel (x, y), y from the bottom row: the planes' entry
+        of that pixel plus p, t, the material code and its parameter
+        (rtx_pick)."""
+        h = rtx_hit()
+        _check(self._lib.rtx_pick(self._h, x, y, C.byref(h)), "rtx_pick", self._lib)
+        return dict(hit=bool(h.hit), index=int(h.index), front_face=bool(h.front_face), material=int(h.material),
+                    t=np.float32(h.t), depth=np.float32(h.depth), p=np.array(h.p[:], np.float32),
+                    normal=np.array(h.normal[:], np.float32), albedo=np.array(h.albedo[:], np.float32),
+                    mat_param=np.float32(h.mat_param))
+
+    def mask_from_ids(self, d_surf, ids, grow: int = 0):
+        """The pixels within Chebyshev distance `grow` of one that shows a
+        sphere of `ids`, from a whole-frame surf plane on the device (a
+        DeviceArray or a pointer). Returns (mask, set): an (H, W) uint8
+        DeviceArray and the number of set pixels (rtx_mask_from_ids)."""
+        f = self.frame
+        a = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        mask = self.alloc((f.height, f.width), np.uint8)
+        n = C.c_uint32(0)
+        _check(self._lib.rtx_mask_from_ids(self._h, C.c_void_p(getattr(d_surf, "ptr", d_surf) or 0),
+                                           a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size, grow, C.c_void_p(mask.ptr),
+                                           C.byref(n)), "rtx_mask_from_ids", self._lib)
+        return mask, int(n.value)
+
+    def refine_masked(self, samples: int, d_mask, max_samples: int = 0) -> int:
+        """Trace `samples` more samples of every pixel whose mask byte is set
+        (a DeviceArray or a device pointer of H x W bytes) and whose count stays
+        within max_samples (0: no cap); every other pixel keeps its state.
+        Needs a whole-frame chain state. Returns the number of pixels traced
+        (rtx_refine_masked)."""
+        n = C.c_uint32(0)
+        _check(self._lib.rtx_refine_masked(self._h, samples, C.c_void_p(getattr(d_mask, "ptr", d_mask) or 0),
+                                           max_samples, C.byref(n)), "rtx_refine_masked", self._lib)
+        return int(n.value)
 
     def deinterleave(self, d_gathered: int, width: int, height: int, tile_rows: int, nparts: int,
                      d_image: int):
