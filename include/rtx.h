@@ -332,7 +332,17 @@ RTX_API int rtx_set_schedule(rtx_ctx *ctx, const rtx_schedule *schedule);
 RTX_API int rtx_get_schedule(rtx_ctx *ctx, rtx_schedule *out);
 
 /* ---- scene / frame upload ----------------------------------------------
- * ~ CreateBuffer(WorldDef, IMMUTABLE) (DxCSApp.cpp:393-413). */
+ * ~ CreateBuffer(WorldDef, IMMUTABLE) (DxCSApp.cpp:393-413).
+ * What rtx_upload_world accepts: every sphere component (centre and radius)
+ * finite with |value| <= 1e15, nothing more. A radius may be 0, -0 or
+ * negative: the reference reads it as r * r in the discriminant and as 1 / r
+ * in the normal, and so does the library (a negative radius turns the normal
+ * and front_face round, a zero one makes them infinite or NaN). mat_types and
+ * mat_values are not looked at: a code other than 0, 1, 2 does not scatter,
+ * and a NaN, infinite, zero or negative albedo, fuzz or refraction index
+ * enters the path arithmetic as it stands. rtx_set_frame does not check that
+ * the camera vectors are finite either. Every such input renders what the
+ * reference's arithmetic gives, bit for bit (tests/test_gpu_hostile_inputs.py). */
 RTX_API int rtx_upload_world(rtx_ctx *ctx, const rtx_world *world);
 /* How hit_world finds its candidates (the answer is the reference's in both):
  * RTX_SCAN_AUTO (the default): the flat layer's blocks through the layer grid
@@ -993,7 +1003,17 @@ RTX_API int rtx_frame_from_perframe(const void *perframe_bytes, size_t nbytes,
  * (used by the parity tests; same device code as the render kernel).
  * rays: nrays * 6 floats (origin.xyz, dir.xyz) host memory. out: nrays * 10
  * floats: hit(0/1), t, p.xyz, normal.xyz, front_face(0/1), sphere index.
- * Uses the uploaded world. Synchronous. ~ hit_world, ShaderCompute.hlsl:188-205. */
+ * Uses the uploaded world. Synchronous. ~ hit_world, ShaderCompute.hlsl:188-205.
+ * The rays may hold any bit patterns: NaN, infinities, zero directions, tiny
+ * and huge lengths. The reference accepts a root with
+ * !(root < t_min || t_max < root), so a NaN root is accepted and after it
+ * every later sphere whose discriminant is not negative: a ray with a NaN
+ * component "hits" sphere count - 1 with t = NaN, and what a ray with
+ * |d|^2 = inf or 1 / |d|^2 = inf hits depends on the scene's order. The record
+ * is the in-order scan's for such rays too, in every scan form below. The
+ * render meets them in ordinary use (the unguarded Lambert direction
+ * normalize(0), RTX_FN_LAMBERT_DIR): a NaN ray then goes on from sphere
+ * count - 1 by that sphere's material. */
 RTX_API int rtx_debug_hit_world(rtx_ctx *ctx, const float *rays, uint32_t nrays,
                                 float t_min, float t_max, float *out);
 /* Requirements of both: t_min finite and > 0 (the render's 0.001; the

@@ -669,9 +669,11 @@ int rtx_upload_world(rtx_ctx *c, const rtx_world *w) {
     if (w->reserved != 0) return fail(RTX_ERR_INVALID, "rtx_upload_world: reserved must be 0");
     if (w->count > 0 && (!w->spheres || !w->mat_types || !w->mat_values))
         return fail(RTX_ERR_INVALID, "rtx_upload_world: null array with count > 0");
-    // Exactness bound of the kernel's all-miss test (rtx_kernels.hip,
-    // RTX_ANYMAX): finite scene values of magnitude <= 1e15 keep every
-    // ray-sphere discriminant of a finite ray free of fp32 overflow.
+    // Finite scene values of magnitude <= 1e15 keep every ray-sphere
+    // discriminant of a ray inside the prefilter's safe range free of fp32
+    // overflow (rtx_prefilter.h line_test_setup: S^2 and a S^2 <= 1e36). The
+    // radius may have either sign or be zero, and the materials are not
+    // checked (include/rtx.h).
     for (uint32_t i = 0; i < w->count; ++i)
         for (int k = 0; k < 4; ++k) {
             const float v = w->spheres[4 * i + k];

@@ -274,14 +274,21 @@ __device__ __forceinline__ int hit_blocks_seq(Ptr soa, uint32_t nblk, uint32_t b
             const float cc = fmaf(ocz, ocz, fmaf(ocy, ocy, fmaf(ocx, ocx, blk[24 + k])));
             disc[k] = fmaf(hb[k], hb[k], -(a * cc));
         }
-        // max() drops a NaN operand: a batch mixing NaN and negative discs
-        // needs an fp32 overflow in hb^2 or a*cc, which rtx_upload_world's
-        // bound (|scene values| <= 1e15) rules out; an all-NaN batch (NaN
-        // ray) yields NaN and is taken, like the reference.
-        float m = disc[0];
+        // Skip the batch only if every disc is negative, the reference's own
+        // test of each sphere. fmaxf alone drops a NaN operand, and a batch can
+        // mix a NaN disc with negative ones (a = |d|^2 = inf and cc exactly 0
+        // give inf * 0 beside -inf: tests/hostile_cases.py divergence_case), so
+        // the sum goes with it: it is NaN whenever a disc is. m < 0 and s == s
+        // together say that no disc is NaN and the largest is negative; a sum
+        // that is NaN without a NaN operand needs a +inf one, which m >= 0
+        // takes anyway, so the test is exact, not a superset.
+        // (The per-sphere compares, or-ed as lane masks, hold 16 SGPRs and an
+        // integer max of the bit patterns regroups the loads: both make the
+        // render kernels spill, C2 30.3 -> 40.7 ms for the former, RESULTS.md.)
+        float m = disc[0], s = disc[0];
 #pragma unroll
-        for (int k = 1; k < 8; ++k) m = fmaxf(m, disc[k]);
-        if (__ballot(!(m < 0.0f)) != 0ull) {
+        for (int k = 1; k < 8; ++k) m = fmaxf(m, disc[k]), s += disc[k];
+        if (__ballot(!(m < 0.0f) | (s != s)) != 0ull) {
             const int g = (int)(8 * (blk0 + b));
 #pragma unroll
             for (int k = 0; k < 8; ++k)

@@ -11,6 +11,13 @@
 // oracle/rtx_oracle.c hit_world32) must have its block's bit in the walk's
 // mask, whenever the kernel applies the grid (the prefilter's line test in
 // its safe range). The grid is built and walked by the header's own code.
+// Hostile mode (argv[3] = k > 0): a quarter of every layer's spheres are made
+// degenerate (radius 0, -0, negated, 1e-30, concentric, on the 1/8 lattice)
+// and every k-th ray is turned into the next hostile class of
+// tests/hostile_rays.h (NaN, infinite, zero, tiny and huge components). The
+// claim is checked for them like for any ray; a ray the line test finds
+// outside its safe range, which the kernel never walks, is still sent through
+// grid_walk and grid_stretch so that their give-up exits run.
 // Prints one JSON line; exit status 1 if any accepted sphere is missed.
 // Build: g++ -O2 -std=c++17 -ffp-contract=off -mfma grid_check.cpp
 #include <cmath>
@@ -20,6 +27,7 @@
 
 #include "../raytrace-we-gpu_amd/csrc/rtx_grid.h"
 #include "../raytrace-we-gpu_amd/csrc/rtx_prefilter.h"
+#include "hostile_rays.h"
 
 static unsigned long long g_s = 0x2545f4914f6cdd1dull;
 static double uni() {
@@ -64,7 +72,7 @@ struct Layer {
     std::vector<unsigned long long> cell;
 };
 
-static bool make_layer(Layer &L, bool rtiow) {
+static bool make_layer(Layer &L, bool rtiow, bool degenerate) {
     L.s.clear();
     if (rtiow) {
         for (int a = -11; a < 11; ++a)
@@ -81,19 +89,25 @@ static bool make_layer(Layer &L, bool rtiow) {
         for (int i = 0; i < n; ++i)
             L.s.insert(L.s.end(), {(float)(ext * sym()), y0, (float)(ext * sym()), (float)(rmax * (0.05 + 0.95 * uni()))});
     }
+    if (degenerate)
+        for (uint32_t j = 1; j < (uint32_t)(L.s.size() / 4); ++j)
+            if (uni() < 0.25) hostile::degenerate_sphere(L.s.data(), j, (int)(uni() * 6.0), true);
     return rtx::build_layer_grid(L.s.data(), 0u, (uint32_t)(L.s.size() / 4), L.G, L.cell);
 }
 
 int main(int argc, char **argv) {
     const long nlayers = argc > 1 ? atol(argv[1]) : 300;
     const long nrays = argc > 2 ? atol(argv[2]) : 4000;
+    const long hostile_every = argc > 3 ? atol(argv[3]) : 0;
+    long hostile_rays = 0, hostile_walked = 0, hostile_gave_up = 0;
+    int hostile_cls = 0;
     long rays = 0, applied = 0, all = 0, accepted = 0, missed = 0, layers = 0, nogrid = 0;
     long far_checked = 0, far_missed = 0;
     double far_bits = 0.0;
     double bits = 0.0;
     for (long li = 0; li < nlayers; ++li) {
         Layer L;
-        if (!make_layer(L, li % 3 == 0)) {
+        if (!make_layer(L, li % 3 == 0, hostile_every > 0)) {
             ++nogrid;
             continue;
         }
@@ -143,10 +157,23 @@ int main(int argc, char **argv) {
             float of[3], df[3];
             for (int i = 0; i < 3; ++i) of[i] = (float)o[i], df[i] = (float)(dir[i] * dlen);
             ++rays;
+            const bool hz = hostile_every > 0 && k % hostile_every == 0;
+            if (hz) {
+                hostile::hostile_ray(hostile_cls++, c, of, df);
+                ++hostile_rays;
+            }
             const float a = fmaf(df[2], df[2], fmaf(df[1], df[1], df[0] * df[0]));
             // the kernel applies the grid only where the line test is safe
             const rtx::LineTest T = rtx::line_test_setup(of[0], of[1], of[2], df[0], df[1], df[2], a, 200.0f);
-            if (T.thr == -INFINITY) continue;
+            if (T.thr == -INFINITY) {
+                if (hz) {  // never walked by the kernel: the walks must still end, inside the grid
+                    ++hostile_walked;
+                    const uint64_t md = rtx::grid_mask(L.G, cellf, of[0], of[1], of[2], df[0], df[1], df[2]);
+                    const uint64_t mi = rtx::grid_mask_items(L.G, cellf, of[0], of[1], of[2], df[0], df[1], df[2]);
+                    hostile_gave_up += (md == ~0ull) + (mi == ~0ull);
+                }
+                continue;
+            }
             ++applied;
             const uint64_t m = rtx::grid_mask(L.G, cellf, of[0], of[1], of[2], df[0], df[1], df[2]);
             if (m == ~0ull) {
@@ -198,8 +225,9 @@ int main(int argc, char **argv) {
     const long masked = applied - all;
     printf("{\"layers\": %ld, \"layers_without_grid\": %ld, \"rays\": %ld, \"grid_applied\": %ld, "
            "\"every_block\": %ld, \"accepted_spheres\": %ld, \"missed\": %ld, \"mean_blocks_marked\": %.3f, "
-           "\"far_checked\": %ld, \"far_missed\": %ld}\n",
+           "\"far_checked\": %ld, \"far_missed\": %ld, \"hostile_rays\": %ld, \"hostile_walked\": %ld, "
+           "\"hostile_gave_up\": %ld, \"failures\": %ld}\n",
            layers, nogrid, rays, applied, all, accepted, missed, masked ? bits / (double)masked : 0.0, far_checked,
-           far_missed);
+           far_missed, hostile_rays, hostile_walked, hostile_gave_up, missed + far_missed);
     return missed == 0 && far_missed == 0 ? 0 : 1;
 }

@@ -18,8 +18,15 @@
 //    lane holding every item over several rounds, totals of 63, 64, 65 and
 //    128, inactive lanes in between, a give-up lane among normal ones (~0),
 //    and random waves.
-// Prints one JSON line; exit status 1 on a miss, on too few rays, or on a
-// wave whose emulation differs.
+// 4. Hostile mode (argv[4] = k > 0): a quarter of every layer's spheres are
+//    made degenerate and every k-th ray becomes the next hostile class of
+//    tests/hostile_rays.h (NaN, infinite, zero, tiny and huge components). A
+//    ray inside the line test's safe range is checked like any other; one
+//    outside it, which the kernel never walks, still goes through grid_walk,
+//    grid_stretch and grid_item_cells: every cell index must lie inside the
+//    grid (hostile_cells_outside), and a wave with such a lane gives up.
+// Prints one JSON line; exit status 1 on a miss, on too few rays, on a wave
+// whose emulation differs, or on a cell index outside the grid.
 // Build: g++ -O2 -std=c++17 -ffp-contract=off -mfma grid_coop_check.cpp
 #include <bitset>
 #include <cmath>
@@ -29,6 +36,7 @@
 
 #include "../raytrace-we-gpu_amd/csrc/rtx_grid.h"
 #include "../raytrace-we-gpu_amd/csrc/rtx_prefilter.h"
+#include "hostile_rays.h"
 
 static unsigned long long g_s = 0x9e3779b97f4a7c15ull;
 static double uni() {
@@ -55,7 +63,7 @@ struct Ray {
     float o[3], d[3];
 };
 
-static bool make_layer(Layer &L, bool rtiow) {
+static bool make_layer(Layer &L, bool rtiow, bool degenerate) {
     L.s.clear();
     if (rtiow) {  // the layer of random_world(11): unit cells, jitter 0.9, r 0.2
         for (int a = -11; a < 11; ++a)
@@ -72,6 +80,9 @@ static bool make_layer(Layer &L, bool rtiow) {
         for (int i = 0; i < n; ++i)
             L.s.insert(L.s.end(), {(float)(ext * sym()), y0, (float)(ext * sym()), (float)(rmax * (0.05 + 0.95 * uni()))});
     }
+    if (degenerate)
+        for (uint32_t j = 1; j < (uint32_t)(L.s.size() / 4); ++j)
+            if (uni() < 0.25) hostile::degenerate_sphere(L.s.data(), j, (int)(uni() * 6.0), true);
     return rtx::build_layer_grid(L.s.data(), 0u, (uint32_t)(L.s.size() / 4), L.G, L.cell);
 }
 
@@ -217,24 +228,56 @@ int main(int argc, char **argv) {
     const long nlayers = argc > 1 ? atol(argv[1]) : 400;
     const long nrays = argc > 2 ? atol(argv[2]) : 4000;
     const long min_checked = argc > 3 ? atol(argv[3]) : 1000000;
+    const long hostile_every = argc > 4 ? atol(argv[4]) : 0;
+    long hostile_rays = 0, hostile_walked = 0, hostile_gave_up = 0, hostile_outside = 0;
+    int hostile_cls = 0;
     long rays = 0, checked = 0, dda_all = 0, item_all = 0, missed_rays = 0, missed_cells = 0, layers = 0;
     double dda_bits = 0.0, item_bits = 0.0, dda_cells = 0.0, item_cells_n = 0.0, items_n = 0.0;
     long waves = 0, wave_bad = 0, wave_rounds = 0;
     for (long li = 0; li < nlayers; ++li) {
         Layer L;
-        if (!make_layer(L, li % 3 == 0)) continue;
+        if (!make_layer(L, li % 3 == 0, hostile_every > 0)) continue;
         ++layers;
         auto cellf = [&L](uint32_t k) { return (uint64_t)L.cell[k]; };
         // rays by item count, for the waves below
-        std::vector<Ray> by_n[4], none, quit, longest;
+        std::vector<Ray> by_n[4], none, quit, longest, hostile_quit;
         uint32_t longest_n = 0;
         for (long k = 0; k < nrays; ++k) {
             Ray r;
             if (!make_ray(L, r)) continue;
             ++rays;
+            const bool hz = hostile_every > 0 && k % hostile_every == 0;
+            if (hz) {
+                hostile::hostile_ray(hostile_cls++, &L.s[4 * (size_t)(uni() * (double)(L.s.size() / 4))], r.o, r.d);
+                ++hostile_rays;
+            }
             const float a = fmaf(r.d[2], r.d[2], fmaf(r.d[1], r.d[1], r.d[0] * r.d[0]));
             const rtx::LineTest T = rtx::line_test_setup(r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.d[2], a, 200.0f);
-            if (T.thr == -INFINITY) continue;
+            if (T.thr == -INFINITY) {
+                if (hz) {  // never walked by the kernel: both walks must still end, inside the grid
+                    ++hostile_walked;
+                    const uint32_t ncell = L.G.nx * L.G.nz;
+                    const bool w_ok = rtx::grid_walk(L.G, rtx::kGridMaxSteps, r.o[0], r.o[1], r.o[2], r.d[0], r.d[1],
+                                                     r.d[2], INFINITY, [&](uint32_t c) {
+                                                         hostile_outside += c >= ncell;
+                                                         return true;
+                                                     });
+                    rtx::GridStretch S;
+                    const bool s_ok = rtx::grid_stretch(L.G, r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.d[2], S);
+                    if (s_ok) {
+                        if (S.n > rtx::kGridMaxSteps) ++hostile_outside;
+                        for (uint32_t i = 0; i < S.n && i < rtx::kGridMaxSteps; ++i) {
+                            uint32_t k0, stride, cnt;
+                            rtx::grid_item_cells(L.G, S.lo, S.hi, S.A, S.s, S.zmajor, S.c0 + i, k0, stride, cnt);
+                            for (uint32_t q = 0; q < cnt; ++q) hostile_outside += k0 + q * stride >= ncell;
+                        }
+                    } else if (hostile_quit.size() < 4) {
+                        hostile_quit.push_back(r);
+                    }
+                    hostile_gave_up += !w_ok + !s_ok;
+                }
+                continue;
+            }
             CellSet dda, itm;
             const bool dda_ok = rtx::grid_walk(L.G, rtx::kGridMaxSteps, r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.d[2],
                                                INFINITY, [&](uint32_t c) { return dda.set(c), true; });
@@ -333,6 +376,10 @@ int main(int argc, char **argv) {
                 w[5] = quit[0];
                 run_wave(w, ~0ull, 0ull, -1, true);
             }
+            for (size_t q = 0; q < hostile_quit.size(); ++q) {  // a hostile lane among normal ones
+                w[9 + q] = hostile_quit[q];
+                run_wave(w, ~0ull, 0ull, -1, true);
+            }
             // random waves
             for (int rep = 0; rep < 40; ++rep) {
                 for (int l = 0; l < 64; ++l) {
@@ -348,14 +395,16 @@ int main(int argc, char **argv) {
             }
         }
     }
-    const bool ok = missed_rays == 0 && checked >= min_checked && wave_bad == 0 && waves > 0;
+    const bool ok = missed_rays == 0 && checked >= min_checked && wave_bad == 0 && waves > 0 && hostile_outside == 0;
     printf("{\"layers\": %ld, \"rays\": %ld, \"checked\": %ld, \"min_checked\": %ld, \"dda_every_block\": %ld, "
            "\"items_every_block\": %ld, \"missed_rays\": %ld, \"missed_cells\": %ld, \"cells_dda\": %.3f, "
            "\"cells_items\": %.3f, \"items_per_ray\": %.3f, \"block_mask_bloat\": %.5f, \"waves\": %ld, "
-           "\"wave_rounds\": %ld, \"waves_wrong\": %ld, \"eps\": %g}\n",
+           "\"wave_rounds\": %ld, \"waves_wrong\": %ld, \"eps\": %g, \"hostile_rays\": %ld, \"hostile_walked\": %ld, "
+           "\"hostile_gave_up\": %ld, \"hostile_cells_outside\": %ld, \"failures\": %ld}\n",
            layers, rays, checked, min_checked, dda_all, item_all, missed_rays, missed_cells,
            checked ? dda_cells / (double)checked : 0.0, checked ? item_cells_n / (double)checked : 0.0,
            checked ? items_n / (double)checked : 0.0, dda_bits > 0.0 ? item_bits / dda_bits : 0.0, waves, wave_rounds,
-           wave_bad, (double)rtx::kGridCoopEps);
+           wave_bad, (double)rtx::kGridCoopEps, hostile_rays, hostile_walked, hostile_gave_up, hostile_outside,
+           missed_rays + wave_bad + hostile_outside);
     return ok ? 0 : 1;
 }

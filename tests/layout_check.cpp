@@ -19,6 +19,13 @@
 //   - on RTIOW ext 11, with the seeded ray family of tools/layout_blocks.h, the
 //     mean union of marked blocks per emulated wave is strictly below scene
 //     order's (the ratio is printed, not a pass mark).
+// Hostile mode (argv[3] = k > 0): the same checks again on degenerate versions
+// of the RTIOW worlds and of one interleaved scene per layer size (a quarter
+// of the spheres with radius 0, -0, negated, 1e-30, concentric with their
+// predecessor or on the 1/8 lattice; heights kept, so the layer is the same
+// set), and every k-th ray of every scene becomes the next hostile class of
+// tests/hostile_rays.h. A ray outside the line test's safe range, which the
+// kernel never walks, still goes through both walks (hostile_walked).
 // Prints one JSON line; exit status 1 on any failure.
 // Build: g++ -O2 -std=c++17 -ffp-contract=off -mfma layout_check.cpp ../raytrace-we-gpu_amd/csrc/rtx_host.cpp
 #include <cmath>
@@ -33,6 +40,7 @@
 #include "../raytrace-we-gpu_amd/csrc/rtx_layout.h"
 #include "../raytrace-we-gpu_amd/csrc/rtx_prefilter.h"
 #include "../tools/layout_blocks.h"
+#include "hostile_rays.h"
 
 static unsigned long long g_s = 0x2545f4914f6cdd1dull;
 static double uni() {
@@ -113,6 +121,14 @@ static Scene interleaved(uint32_t layer, uint32_t off, float y0, double ext) {
 }
 
 static long g_layouts = 0, g_rays = 0, g_accepted = 0, g_missed = 0;
+static long g_hostile_every = 0, g_hostile_rays = 0, g_hostile_walked = 0, g_hostile_gave_up = 0;
+static int g_hostile_cls = 0;
+
+static Scene degenerate(Scene s) {
+    for (uint32_t j = 1; j < (uint32_t)(s.size() / 4); ++j)
+        if (uni() < 0.25) hostile::degenerate_sphere(s.data(), j, (int)(uni() * 6.0), true);
+    return s;
+}
 
 // The structure of a layout of scene s; want_layer: the expected layer size
 // (0: no layout expected), want_y: its height.
@@ -223,9 +239,21 @@ static void check_grid(const Scene &s, const rtx::SceneLayout &L, long nrays, co
         const double dlen = std::pow(10.0, -2.0 + 4.0 * uni());
         float of[3], df[3];
         for (int i = 0; i < 3; ++i) of[i] = (float)o[i], df[i] = (float)(dir[i] * dlen);
+        const bool hz = g_hostile_every > 0 && k % g_hostile_every == 0;
+        if (hz) {
+            hostile::hostile_ray(g_hostile_cls++, c, of, df);
+            ++g_hostile_rays;
+        }
         const float a = fmaf(df[2], df[2], fmaf(df[1], df[1], df[0] * df[0]));
         const rtx::LineTest T = rtx::line_test_setup(of[0], of[1], of[2], df[0], df[1], df[2], a, 200.0f);
-        if (T.thr == -INFINITY) continue;  // the kernel applies the grid only where the line test is safe
+        if (T.thr == -INFINITY) {  // the kernel applies the grid only where the line test is safe
+            if (hz) {  // the walks must still end, inside the grid
+                ++g_hostile_walked;
+                g_hostile_gave_up += rtx::grid_mask(L.grid, cellf, of[0], of[1], of[2], df[0], df[1], df[2]) == ~0ull;
+                g_hostile_gave_up += rtx::grid_mask_items(L.grid, cellf, of[0], of[1], of[2], df[0], df[1], df[2]) == ~0ull;
+            }
+            continue;
+        }
         ++g_rays;
         const uint64_t md = rtx::grid_mask(L.grid, cellf, of[0], of[1], of[2], df[0], df[1], df[2]);
         const uint64_t mi = rtx::grid_mask_items(L.grid, cellf, of[0], of[1], of[2], df[0], df[1], df[2]);
@@ -259,6 +287,7 @@ static void check_scene(const Scene &s, uint32_t want_layer, float want_y, long 
 int main(int argc, char **argv) {
     const long nrays = argc > 1 ? atol(argv[1]) : 3000;
     const uint32_t waves = argc > 2 ? (uint32_t)atol(argv[2]) : 2000;
+    g_hostile_every = argc > 3 ? atol(argv[3]) : 0;
     // RTIOW: the layer is every small sphere (y = 0.2), the 4 fixed ones are off it
     const Scene w11 = rtiow(11), w5 = rtiow(5);
     check_scene(w11, (uint32_t)(w11.size() / 4) - 4, 0.2f, 4 * nrays, "rtiow11");
@@ -275,7 +304,15 @@ int main(int argc, char **argv) {
             char what[64];
             snprintf(what, sizeof what, "layer%u+%u", ls, off);
             check_scene(s, has ? ls : 0u, y0, nrays, what);
+            if (g_hostile_every > 0 && rep == 1) {
+                snprintf(what, sizeof what, "layer%u+%u degenerate", ls, off);
+                check_scene(degenerate(s), has ? ls : 0u, y0, nrays, what);
+            }
         }
+    if (g_hostile_every > 0) {
+        check_scene(degenerate(w11), (uint32_t)(w11.size() / 4) - 4, 0.2f, 4 * nrays, "rtiow11 degenerate");
+        check_scene(degenerate(w5), (uint32_t)(w5.size() / 4) - 4, 0.2f, 4 * nrays, "rtiow5 degenerate");
+    }
     {  // two layers of equal size: the one whose first sphere comes first
         Scene s;
         for (int i = 0; i < 48; ++i) s.insert(s.end(), {(float)(8.0 * sym()), i % 2 ? 1.5f : -0.25f, (float)(8.0 * sym()), 0.3f});
@@ -304,8 +341,10 @@ int main(int argc, char **argv) {
     CHECK(g_missed == 0, "%ld accepted spheres missing from the grid", g_missed);
     printf("{\"layouts\": %ld, \"rays\": %ld, \"accepted_spheres\": %ld, \"missed\": %ld, \"failures\": %ld, "
            "\"scene_blocks_per_wave\": %.3f, \"layout_blocks_per_wave\": %.3f, \"ratio\": %.3f, "
-           "\"scene_blocks_per_ray\": %.3f, \"layout_blocks_per_ray\": %.3f}\n",
+           "\"scene_blocks_per_ray\": %.3f, \"layout_blocks_per_ray\": %.3f, \"hostile_rays\": %ld, "
+           "\"hostile_walked\": %ld, \"hostile_gave_up\": %ld}\n",
            g_layouts, g_rays, g_accepted, g_missed, g_fail, cs.per_wave, cm.per_wave,
-           cs.per_wave > 0.0 ? cm.per_wave / cs.per_wave : 0.0, cs.per_ray, cm.per_ray);
+           cs.per_wave > 0.0 ? cm.per_wave / cs.per_wave : 0.0, cs.per_ray, cm.per_ray, g_hostile_rays,
+           g_hostile_walked, g_hostile_gave_up);
     return g_fail == 0 ? 0 : 1;
 }

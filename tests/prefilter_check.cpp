@@ -8,6 +8,12 @@
 // hit_world32), the prefilter must flag the sphere — in both op orders the
 // scan uses (line_test_q, and line_test_q_flat for flat blocks), with the
 // line basis's hardware rsq/sqrt modelled as exact or one ulp off either way.
+// Hostile mode (argv[2] = k > 0): every k-th single-sphere case has its ray
+// turned into the next hostile class of tests/hostile_rays.h (NaN, infinite,
+// zero, tiny and huge components, the origin at the centre or exactly on the
+// surface), and the case after it a degenerate radius (0, -0, negated, 1e-30;
+// rtx_upload_world bounds the scene by |c| + |r|). The claim is the same:
+// a discriminant that is not negative, NaN included, must be flagged.
 // Prints one JSON line; exit status 1 if any reference candidate is missed.
 // Build: g++ -O2 -std=c++17 -ffp-contract=off -mfma prefilter_check.cpp
 #include <cmath>
@@ -15,6 +21,7 @@
 #include <cstdlib>
 
 #include "../raytrace-we-gpu_amd/csrc/rtx_prefilter.h"
+#include "hostile_rays.h"
 
 static unsigned long long g_s = 0x9e3779b97f4a7c15ull;
 static double uni() {
@@ -204,6 +211,9 @@ static void block_cases(long n, long &ref_pos, long &missed, double &max_used, l
 
 int main(int argc, char **argv) {
     const long n = argc > 1 ? std::atol(argv[1]) : 2000000;
+    const long hostile_every = argc > 2 ? std::atol(argv[2]) : 0;
+    long hostile_rays = 0, hostile_radii = 0, hostile_ref = 0, hostile_nan = 0;
+    int hostile_cls = 0;
     long ref_pos = 0, flagged = 0, missed = 0, unsafe = 0, false_pos = 0;
     long s_acc = 0, s_half_missed = 0, s_half_culled = 0;
     double max_used = -1e300, s_half_used = -1e300;
@@ -269,10 +279,21 @@ int main(int argc, char **argv) {
                 d[i] = (float)(dlen * dv[i]);
             }
         }
-        const float rf = (float)r;
+        float rf = (float)r;
+        const bool hz = hostile_every > 0 && k % hostile_every == 0;
+        if (hostile_every > 0 && (k % hostile_every == 1 || (hz && hostile_cls / hostile::kClasses % 2 == 1))) {
+            float one[4] = {c[0], c[1], c[2], rf};
+            hostile::degenerate_sphere(one, 0u, (int)(hostile_radii++ % 4), true);
+            rf = one[3];
+        }
+        if (hz) {
+            const float c4[4] = {c[0], c[1], c[2], rf};
+            hostile::hostile_ray(hostile_cls++, c4, o, d);
+            ++hostile_rays;
+        }
         const float r2 = rf * rf;
         const float a = fmaf(d[2], d[2], fmaf(d[1], d[1], d[0] * d[0]));
-        const double sm = std::sqrt((double)c[0] * c[0] + (double)c[1] * c[1] + (double)c[2] * c[2]) + rf;
+        const double sm = std::sqrt((double)c[0] * c[0] + (double)c[1] * c[1] + (double)c[2] * c[2]) + std::fabs(rf);
         float smag = (float)sm;
         if ((double)smag < sm) smag = std::nextafter(smag, INFINITY);
         // the basis's 1-ulp hardware rsq/sqrt: exact, or one ulp either way
@@ -288,6 +309,8 @@ int main(int argc, char **argv) {
         ref_pos += ref;
         flagged += flag;
         false_pos += flag && !ref;
+        hostile_ref += hz && ref;
+        hostile_nan += hz && disc != disc;
         if (T.thr == -INFINITY) ++unsafe;
         if (ref && !flag) {
             if (++missed <= 5)
@@ -327,8 +350,11 @@ int main(int argc, char **argv) {
                 "\"block_reference_candidates\": %ld, \"block_missed\": %ld, \"block_max_used\": %.9g, "
                 "\"block_reference_accepted\": %ld, \"half_missed\": %ld, \"half_culled\": %ld, "
                 "\"half_max_used\": %.9g, \"sphere_reference_accepted\": %ld, \"sphere_half_missed\": %ld, "
-                "\"sphere_half_culled\": %ld, \"sphere_half_max_used\": %.9g}\n",
+                "\"sphere_half_culled\": %ld, \"sphere_half_max_used\": %.9g, \"hostile_rays\": %ld, "
+                "\"hostile_radii\": %ld, \"hostile_reference_candidates\": %ld, \"hostile_nan_discs\": %ld, "
+                "\"failures\": %ld}\n",
                 n, ref_pos, flagged, false_pos, unsafe, missed, max_used, n / 2, b_ref, b_missed, b_used, h_acc,
-                h_missed, h_culled, h_used, s_acc, s_half_missed, s_half_culled, s_half_used);
+                h_missed, h_culled, h_used, s_acc, s_half_missed, s_half_culled, s_half_used, hostile_rays,
+                hostile_radii, hostile_ref, hostile_nan, missed + b_missed + h_missed + s_half_missed);
     return missed || b_missed || h_missed || s_half_missed ? 1 : 0;
 }

@@ -85,7 +85,8 @@ def test_layer_grid_never_skips_an_accepted_sphere(tmp_path):
                                                            "rtx_prefilter.h")).read())
     btests = tmp_path / "bad" / "tests"
     btests.mkdir()
-    (btests / "grid_check.cpp").write_text(open(GRID_SRC).read())
+    for name in ("grid_check.cpp", "hostile_rays.h"):
+        (btests / name).write_text(open(os.path.join(ROOT, "tests", name)).read())
     bexe = str(tmp_path / "grid_check_bad")
     subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-o", bexe, str(btests / "grid_check.cpp")],
                    check=True)
