@@ -40,6 +40,10 @@ extern "C" {
 
 #define RTX_VERSION 145 /* 1.4.5 */
 /* ABI notes.
+ *  1.4.5 (later builds, no version bump): rtx_cast_rays (rtx_ray, rtx_ray_hit,
+ *         RTX_CAST_ORDER_*) and rtx_cast_last_order (batched closest-hit ray
+ *         queries on device buffers, each ray with its own t_max); purely
+ *         additive again: probe for the symbol (dlsym "rtx_cast_rays").
  *  1.4.5 (later builds, no version bump): rtx_features, rtx_features_rows,
  *         rtx_pick (rtx_hit), rtx_mask_from_ids and rtx_refine_masked (the
  *         first hit of every pixel's centre ray as feature buffers, picking,
@@ -723,6 +727,50 @@ RTX_API int rtx_mask_from_ids(rtx_ctx *ctx, const void *d_surf, const uint32_t *
  * refuses as after adaptive steps; rtx_refine_adaptive continues from the maps. */
 RTX_API int rtx_refine_masked(rtx_ctx *ctx, uint32_t samples, const void *d_mask,
                               uint32_t max_samples, uint32_t *active);
+/* ---- batched closest-hit ray queries ----------------------------------------
+ * (later builds, no version bump: probe with dlsym "rtx_cast_rays").
+ * What n rays of the caller's choosing hit in the uploaded world: the render's
+ * hit_world for every ray, each over its own range (t_min, t_max_i). d_rays
+ * (n rtx_ray), d_hits (n rtx_ray_hit) and d_occluded (n bytes) are device
+ * pointers; either output may be NULL, not both; the buffers must not overlap.
+ * Asynchronous on the context stream. Reads the world and needs no frame.
+ * Ray i: if !(t_max_i >= t_min) — a NaN, negative or too short t_max — it
+ * misses without being scanned. Otherwise its record is rtx_debug_hit_world's
+ * for that ray with (t_min, t_max_i), in every scan form the context selects
+ * for the scene (the layout and layer grid, the culled scan above 1,024
+ * spheres, the linear scan under RTX_SCAN_LINEAR): the reference's in-order
+ * hit_world, the largest index among equal roots, a NaN ray "hitting" sphere
+ * count - 1 with t = NaN.
+ *   hit:   t, index, the normal flipped to face the ray, front_face (1 / 0),
+ *          reserved 0
+ *   miss:  t = +inf, index = -1, the rest 0
+ *   occluded[i] = (index >= 0)
+ * The hit point is not stored: o + t * d, one multiply then one add per
+ * component, is the record's p. `tag` is the caller's and is ignored.
+ * `order` is a schedule and nothing else; no record depends on it:
+ *   GIVEN     lane i of the kernel casts ray i: a wave scans the union of its
+ *             64 rays' candidate blocks, so rays that are neighbours in space
+ *             should be neighbours in the buffer
+ *   COHERENT  the rays are first sorted by a coarse key of their origin and
+ *             direction (three small passes on the context's own scratch,
+ *             which grows when a call needs more), and lane i casts the i-th
+ *             ray of that order
+ *   AUTO      one of the two, by the batch size and the scene's class
+ * rtx_cast_last_order: what the last call ran, GIVEN or COHERENT (AUTO
+ * resolved); GIVEN before any call.
+ * RTX_ERR_INVALID, before any HIP call and before the context is looked at: a
+ * null ctx; n > 0 with d_rays NULL or both outputs NULL; t_min not finite or
+ * <= 0; an unknown order. RTX_ERR_STATE: no world. n == 0 returns RTX_OK and
+ * launches nothing. The call touches nothing else: no stats, no framebuffer,
+ * no chain state, no cost map. With a group, call it on rtx_group_ctx(g, 0),
+ * as rtx_features. */
+typedef struct rtx_ray     { float o[3]; float t_max; float d[3]; uint32_t tag; } rtx_ray;        /* 32 B */
+typedef struct rtx_ray_hit { float t; int32_t index; float normal[3]; uint32_t front_face;
+                             uint32_t reserved[2]; } rtx_ray_hit;                                  /* 32 B */
+enum { RTX_CAST_ORDER_AUTO = 0, RTX_CAST_ORDER_GIVEN = 1, RTX_CAST_ORDER_COHERENT = 2 };
+RTX_API int rtx_cast_rays(rtx_ctx *ctx, const void *d_rays, uint32_t n, float t_min, uint32_t order,
+                          void *d_hits, void *d_occluded);
+RTX_API int rtx_cast_last_order(rtx_ctx *ctx);   /* GIVEN or COHERENT: what the last call ran; AUTO resolved */
 /* Device pointer of the chain state (width*height float4; a part state: its
  * rows * width), NULL if none. */
 RTX_API void *rtx_refine_state(rtx_ctx *ctx);

@@ -151,6 +151,15 @@ public:
     // What is under pixel (x, y), y from the bottom row (rtx_pick). True also
     // for a miss (out->hit == 0); false when the call itself failed.
     bool Pick(uint32_t x, uint32_t y, rtx_hit *out);
+    // What rays of the caller's choosing hit (rtx_cast_rays): one record per
+    // ray, each over (t_min, its own t_max), through device buffers of the
+    // call's own; synchronous. order: RTX_CAST_ORDER_AUTO, _GIVEN or _COHERENT,
+    // a schedule and never a different record. Needs a world and no frame.
+    // With a group: member 0, which holds the same world.
+    bool Cast(const std::vector<rtx_ray> &rays, std::vector<rtx_ray_hit> *hits, int order = RTX_CAST_ORDER_AUTO,
+              float t_min = 0.001f);
+    // RTX_CAST_ORDER_GIVEN or _COHERENT: what the last Cast ran (rtx_cast_last_order).
+    int CastLastOrder() const;
     // Click to focus: picks the pixel, takes the hit's plane depth
     // dot(p - cam_pos, normalize(cam_look_at - cam_pos)) as the focus distance,
     // rebuilds the frame through rtx_camera_look_at with it and sets the thin

@@ -134,6 +134,14 @@ struct rtx_ctx {
     // then the mask's listed bytes — grown on demand
     unsigned char *d_feat = nullptr;
     size_t feat_bytes = 0;
+    // rtx_cast_rays: the box of the world's body (rtx_cast.h, from
+    // rtx_upload_world), the COHERENT order's scratch — kCastBuckets counts,
+    // then keys and perm of cast_rays words each — grown on demand, and what
+    // the last call ran
+    rtx::CastBox cast_box{};
+    uint32_t *d_cast = nullptr;
+    size_t cast_rays = 0;
+    int cast_last = RTX_CAST_ORDER_GIVEN;
     // measurement
     unsigned long long *d_counters = nullptr;
     unsigned long long *d_wave_times = nullptr;  // diagnostic (rtx_debug_wave_times)
@@ -353,6 +361,7 @@ void rtx_destroy(rtx_ctx *c) {
     (void)hipFree(c->d_chain);
     (void)hipFree(c->d_adapt);
     (void)hipFree(c->d_feat);
+    (void)hipFree(c->d_cast);
     (void)hipFree(c->d_counters);
     (void)hipFree(c->d_wave_times);
     (void)hipFree(c->d_sched);
@@ -845,6 +854,10 @@ int rtx_upload_world(rtx_ctx *c, const rtx_world *w) {
     c->flat_hi = flat_hi;
     c->depth = w->depth;
     c->spp = w->spp;
+    {
+        std::vector<float> radii(n);
+        c->cast_box = rtx::cast_box(w->spheres, n, radii.data());
+    }
     c->have_world = true;
     c->chain_n = 0;  // a chain state belongs to the world it was traced in
     return RTX_OK;
@@ -1923,6 +1936,60 @@ int rtx_mask_from_ids(rtx_ctx *c, const void *d_surf, const uint32_t *ids, uint3
         RTX_HIP(hipStreamSynchronize(c->stream));
     }
     return RTX_OK;
+}
+
+// ---- batched closest-hit ray queries (rtx_cast.h) -----------------------------
+static_assert(sizeof(rtx_ray) == 32 && sizeof(rtx_ray_hit) == 32, "rtx_cast_rays: two float4 per record");
+// The COHERENT order's scratch for n rays. Once it fits there is no host wait.
+static int ensure_cast(rtx_ctx *c, size_t n) {
+    if (c->d_cast && c->cast_rays >= n) return RTX_OK;
+    RTX_HIP(hipStreamSynchronize(c->stream));
+    (void)hipFree(c->d_cast);
+    c->d_cast = nullptr;
+    c->cast_rays = 0;
+    RTX_HIP(hipMalloc(&c->d_cast, (rtx::kCastBuckets + 2 * n) * sizeof(uint32_t)));
+    c->cast_rays = n;
+    return RTX_OK;
+}
+
+int rtx_cast_rays(rtx_ctx *c, const void *d_rays, uint32_t n, float t_min, uint32_t order, void *d_hits,
+                  void *d_occluded) {
+    // the argument rules first: none of them looks at the context
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_cast_rays: null ctx");
+    if (n != 0 && !d_rays) return fail(RTX_ERR_INVALID, "rtx_cast_rays: d_rays is NULL");
+    if (n != 0 && !d_hits && !d_occluded) return fail(RTX_ERR_INVALID, "rtx_cast_rays: both outputs are NULL");
+    // the resolve compares roots by their bit patterns, which order like the values only for roots > 0
+    if (!(t_min > 0.0f && t_min <= 3.4028235e38f))
+        return fail(RTX_ERR_INVALID, "rtx_cast_rays: t_min must be finite and > 0");
+    if (order != RTX_CAST_ORDER_AUTO && order != RTX_CAST_ORDER_GIVEN && order != RTX_CAST_ORDER_COHERENT)
+        return fail(RTX_ERR_INVALID, "rtx_cast_rays: unknown order");
+    if (!c->have_world) return fail(RTX_ERR_STATE, "rtx_cast_rays: no world uploaded");
+    if (n == 0) return RTX_OK;
+    const rtx::KScene s = scene_of(c);
+    const bool sort = order == RTX_CAST_ORDER_COHERENT ||
+                      (order == RTX_CAST_ORDER_AUTO && rtx::cast_auto_coherent(n, rtx::scene_kernels(s).kernels));
+    int rc = set_device(c);
+    if (rc) return rc;
+    const float4 *rays = static_cast<const float4 *>(d_rays);
+    const uint32_t *perm = nullptr;
+    if (sort) {
+        rc = ensure_cast(c, n);
+        if (rc) return rc;
+        const rtx::KCastScratch k{c->d_cast, c->d_cast + rtx::kCastBuckets, c->d_cast + rtx::kCastBuckets + c->cast_rays};
+        const hipError_t e = rtx::launch_cast_order(rays, n, c->cast_box, k, c->stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_cast_order");
+        perm = k.perm;
+    }
+    const hipError_t e = rtx::launch_cast(s, rays, n, t_min, perm, static_cast<float4 *>(d_hits),
+                                          static_cast<uint8_t *>(d_occluded), c->stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_cast");
+    c->cast_last = sort ? RTX_CAST_ORDER_COHERENT : RTX_CAST_ORDER_GIVEN;
+    return RTX_OK;
+}
+
+int rtx_cast_last_order(rtx_ctx *c) {
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_cast_last_order: null ctx");
+    return c->cast_last;
 }
 
 int rtx_debug_pixel_cost(rtx_ctx *c, uint32_t spp, uint32_t *host_cost) {

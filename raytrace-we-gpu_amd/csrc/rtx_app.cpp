@@ -262,6 +262,32 @@ bool RtxCSApp::Features(std::vector<float> &geom, std::vector<float> &surf) {
     return ok;
 }
 
+bool RtxCSApp::Cast(const std::vector<rtx_ray> &rays, std::vector<rtx_ray_hit> *hits, int order, float t_min) {
+    if (!m_ok) return false;
+    if (!hits) {
+        m_error = "Cast: hits is NULL";
+        return false;
+    }
+    hits->resize(rays.size());
+    if (rays.size() > 0xffffffffull) {
+        m_error = "Cast: more than 2^32 - 1 rays";
+        return false;
+    }
+    const uint32_t n = (uint32_t)rays.size();
+    const size_t bytes = (size_t)n * sizeof(rtx_ray);
+    void *d[2] = {nullptr, nullptr};
+    bool ok = n == 0 || (rtx_alloc(m_ctx, bytes, &d[0]) == RTX_OK && rtx_alloc(m_ctx, bytes, &d[1]) == RTX_OK &&
+                         rtx_copy_to_device(m_ctx, d[0], rays.data(), bytes) == RTX_OK);
+    ok = ok && rtx_cast_rays(m_ctx, d[0], n, t_min, (uint32_t)order, d[1], nullptr) == RTX_OK;
+    if (ok && n != 0) ok = rtx_copy_to_host(m_ctx, hits->data(), d[1], bytes) == RTX_OK;
+    if (!ok) m_error = rtx_last_error();
+    for (void *p : d)
+        if (p) rtx_free(m_ctx, p);
+    return ok;
+}
+
+int RtxCSApp::CastLastOrder() const { return m_ctx ? rtx_cast_last_order(m_ctx) : RTX_CAST_ORDER_GIVEN; }
+
 bool RtxCSApp::Pick(uint32_t x, uint32_t y, rtx_hit *out) {
     if (!m_ok) return false;
     if (rtx_pick(m_ctx, x, y, out) != RTX_OK) {

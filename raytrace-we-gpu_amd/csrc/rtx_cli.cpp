@@ -14,6 +14,14 @@
 //           [--refine-keys prepass|carried]
 //           [--refine-adaptive S,THRESHOLD[,MAX] --steps K] [--dump-counts FILE]
 //           [--aov PREFIX] [--pick X,Y] [--focus-at X,Y] [--refine-ids S,ID[,ID...] --grow G --steps K]
+//           [--cast RAYS.bin --hits OUT.bin [--cast-order auto|given|coherent] [--t-min T]]
+// --cast RAYS.bin casts the file's rays into the scene (rtx_cast_rays) instead
+// of rendering: RAYS.bin is raw little-endian rtx_ray records (32 bytes: o,
+// t_max, d, tag), OUT.bin receives one rtx_ray_hit record (32 bytes) per ray
+// in the same order. --cast-order picks the schedule (default auto; the records
+// do not depend on it), --t-min the rays' common t_min (default 0.001). The
+// JSON line is {"cast": {"rays", "hits", "order", "t_min", "ms"}}: how many
+// rays hit something, the order the call ran, and the call's wall time.
 // --aov PREFIX writes the first-hit feature buffers of the frame
 // (rtx_features) as PREFIX_normal.pfm, PREFIX_depth.pfm, PREFIX_albedo.pfm and
 // PREFIX_id.pfm (scalars in all three channels; row 0 is the bottom, as --pfm;
@@ -100,7 +108,8 @@ static void usage() {
                  "               [--refine-keys prepass|carried]\n"
                  "               [--refine-adaptive S,THRESHOLD[,MAX] --steps K] [--dump-counts FILE]\n"
                  "               [--aov PREFIX] [--pick X,Y] [--focus-at X,Y]\n"
-                 "               [--refine-ids S,ID[,ID...] --grow G --steps K]\n");
+                 "               [--refine-ids S,ID[,ID...] --grow G --steps K]\n"
+                 "               [--cast RAYS.bin --hits OUT.bin [--cast-order auto|given|coherent] [--t-min T]]\n");
 }
 
 int main(int argc, char **argv) {
@@ -131,6 +140,9 @@ int main(int argc, char **argv) {
     int pick_xy[2] = {-1, -1}, focus_xy[2] = {-1, -1};  // --pick / --focus-at X,Y (-1: not given)
     uint32_t mask_samples = 0, mask_grow = 0;  // --refine-ids S,ID[,ID...] (S 0: not given), --grow
     std::vector<uint32_t> mask_ids;
+    std::string cast_in, cast_out;             // --cast RAYS.bin, --hits OUT.bin
+    int cast_order = RTX_CAST_ORDER_AUTO;      // --cast-order
+    float cast_t_min = 0.001f;                 // --t-min
     std::vector<int> devices;  // non-empty: a group
     int gather = RTX_GATHER_AUTO;
     bool group_opts = false;   // --gather / --tile-rows given
@@ -217,6 +229,19 @@ int main(int argc, char **argv) {
             mask_ids.assign(v.begin() + 1, v.end());
         }
         else if (a == "--dump-counts") dump_counts = next();
+        else if (a == "--cast") cast_in = next();
+        else if (a == "--hits") cast_out = next();
+        else if (a == "--t-min") cast_t_min = (float)std::atof(next());
+        else if (a == "--cast-order") {
+            const std::string m = next();
+            if (m == "auto") cast_order = RTX_CAST_ORDER_AUTO;
+            else if (m == "given") cast_order = RTX_CAST_ORDER_GIVEN;
+            else if (m == "coherent") cast_order = RTX_CAST_ORDER_COHERENT;
+            else {
+                usage();
+                return 2;
+            }
+        }
         else if (a == "--refine-keys") {
             const std::string m = next();
             if (m == "prepass") refine_keys = RTX_REFINE_KEYS_PREPASS;
@@ -320,6 +345,10 @@ int main(int argc, char **argv) {
                              "(a group accumulates with --split frames)\n");
         return 2;
     }
+    if (cast_in.empty() != cast_out.empty()) {
+        std::fprintf(stderr, "rtx_cli: --cast RAYS.bin and --hits OUT.bin go together\n");
+        return 2;
+    }
     const bool adaptive = ad_samples != 0u;
     if (adaptive && (!refine.empty() || !load_state.empty() || ad_steps < 1)) {
         std::fprintf(stderr, "rtx_cli: --refine-adaptive takes --steps K >= 1, without --refine and --load-state\n");
@@ -371,6 +400,45 @@ int main(int argc, char **argv) {
         return 1;
     }
     app.Update();
+    if (!cast_in.empty()) {  // cast the file's rays instead of rendering
+        std::vector<rtx_ray> rays;
+        std::FILE *f = std::fopen(cast_in.c_str(), "rb");
+        bool ok = f != nullptr;
+        if (ok) {
+            ok = std::fseek(f, 0, SEEK_END) == 0;
+            const long bytes = ok ? std::ftell(f) : -1;
+            ok = ok && bytes >= 0 && bytes % (long)sizeof(rtx_ray) == 0 && std::fseek(f, 0, SEEK_SET) == 0;
+            if (ok) {
+                rays.resize((size_t)bytes / sizeof(rtx_ray));
+                ok = std::fread(rays.data(), sizeof(rtx_ray), rays.size(), f) == rays.size();
+            }
+            std::fclose(f);
+        }
+        if (!ok) {
+            std::fprintf(stderr, "rtx_cli: --cast: cannot read %s as 32-byte ray records\n", cast_in.c_str());
+            return 1;
+        }
+        std::vector<rtx_ray_hit> hits;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (!app.Cast(rays, &hits, cast_order, cast_t_min)) {
+            std::fprintf(stderr, "rtx_cli: --cast failed: %s\n", app.last_error().c_str());
+            return 1;
+        }
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        f = std::fopen(cast_out.c_str(), "wb");
+        ok = f != nullptr && std::fwrite(hits.data(), sizeof(rtx_ray_hit), hits.size(), f) == hits.size();
+        if (f) ok = std::fclose(f) == 0 && ok;
+        if (!ok) {
+            std::fprintf(stderr, "rtx_cli: --hits: cannot write %s\n", cast_out.c_str());
+            return 1;
+        }
+        size_t nhit = 0;
+        for (const rtx_ray_hit &h : hits) nhit += h.index >= 0;
+        std::printf("{\"cast\": {\"rays\": %zu, \"hits\": %zu, \"order\": \"%s\", \"t_min\": %.9g, \"ms\": %.3f}}\n",
+                    rays.size(), nhit, app.CastLastOrder() == RTX_CAST_ORDER_COHERENT ? "coherent" : "given",
+                    (double)cast_t_min, ms);
+        return 0;
+    }
     std::string extra;  // further fields of the JSON line: "focus_dist", "pick"
     if (focus_xy[0] >= 0) {
         if (!app.FocusAt((uint32_t)focus_xy[0], (uint32_t)focus_xy[1], cfg.lens_aperture)) {

@@ -9,6 +9,7 @@
 #include "rtx_refine_keys.h"  // kCostBuckets, kCostSpp, kCostSppLarge, kLptMinSpp; the carried key
 #include "rtx_adaptive.h"     // the adaptive rule: a pixel's error estimate, the activity mask
 #include "rtx_features.h"     // the feature buffers' ray and depth, the id mask, the masked rule
+#include "rtx_cast.h"         // rtx_cast_rays: the body box, the sort key, the AUTO rule
 
 struct rtx_ctx;  // include/rtx.h
 
@@ -326,6 +327,22 @@ struct KFeatures {
 // (front_face, material code, mat_values.w, 0): rtx_pick).
 hipError_t launch_features(const KScene &s, const KFeatures &f, float4 *geom, float4 *surf, float4 *extra,
                            hipStream_t stream);
+// Batched closest-hit ray queries (rtx_cast.h; include/rtx.h rtx_cast_rays): n
+// records of two float4 each way (rtx_ray, rtx_ray_hit), one byte per ray;
+// hits or occluded may be NULL. The call's scratch, the context's: counts
+// (kCastBuckets words), keys and perm (n words each).
+struct KCastScratch {
+    uint32_t *counts;
+    uint32_t *keys;
+    uint32_t *perm;
+};
+// k_cast_keys, k_cast_prefix, k_cast_scatter: scratch.perm becomes the rays'
+// COHERENT order, a permutation of 0 .. n-1 (n > 0).
+hipError_t launch_cast_order(const float4 *rays, uint32_t n, const CastBox &box, const KCastScratch &scratch,
+                             hipStream_t stream);
+// k_cast: lane g casts ray perm[g] (perm NULL: ray g) over (t_min, its own t_max).
+hipError_t launch_cast(const KScene &s, const float4 *rays, uint32_t n, float t_min, const uint32_t *perm,
+                       float4 *hits, uint8_t *occluded, hipStream_t stream);
 // k_feature_listed + k_feature_mask (rtx_mask_from_ids): ids is host memory
 // (1 <= n <= kFeatureIdsMax), listed a width * height byte scratch, *n_set
 // (device, zeroed here first) the number of set pixels.

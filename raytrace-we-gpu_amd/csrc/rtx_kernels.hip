@@ -3817,6 +3817,170 @@ __global__ void __launch_bounds__(kRB) k_features(const KScene S, const KFeature
     }
 }
 
+// ---- batched closest-hit ray queries (rtx_cast_rays; rtx_cast.h) -------------
+// The COHERENT order: a counting sort of the rays by cast_key in three passes —
+// k_cast_keys (key and histogram), k_cast_prefix (bucket starts), k_cast_scatter
+// (perm) — in the shape of k_cost_hist / k_cost_scatter. The 65,536 buckets do
+// not fit a workgroup's LDS histogram, and a batch's rays share few keys (every
+// primary ray of a camera has one origin cell), so a global atomic per ray, or
+// per wave, queues up on a handful of addresses (measured: 0.73 ms for the key
+// passes of 2 M centre rays, 9 ms a pass for the C5 AO batch). Instead a
+// workgroup counts its kCastChunk rays in an LDS table keyed by the keys it
+// meets (open addressing, at most half full), which also ranks each ray among
+// the workgroup's rays of its key, and then adds one number per distinct key
+// to the global array.
+constexpr uint32_t kCastPerThread = 8;
+constexpr uint32_t kCastChunk = kBlock * kCastPerThread;  // rays per workgroup of the two passes
+constexpr uint32_t kCastSlotsLg = 12;
+constexpr uint32_t kCastSlots = 1u << kCastSlotsLg;       // table slots
+static_assert(kCastSlots >= 2 * kCastChunk, "the table is at most half full");
+constexpr uint32_t kCastEmpty = 0xffffffffu;              // no key (keys are < kCastBuckets)
+struct CastTable {
+    uint32_t key[kCastSlots];
+    uint32_t cnt[kCastSlots];  // rays of the key so far; k_cast_scatter: then the key's first slot in perm
+};
+__device__ __forceinline__ void cast_table_clear(CastTable &t) {
+    for (uint32_t s = threadIdx.x; s < kCastSlots; s += kBlock) t.key[s] = kCastEmpty, t.cnt[s] = 0u;
+    __syncthreads();
+}
+// The slot of `key` (claimed on first sight) and this ray's rank among the
+// workgroup's rays of the key. kCastSlots: no slot found, which a table at most
+// half full never reports (the probe is bounded all the same).
+__device__ __forceinline__ uint32_t cast_table_add(CastTable &t, uint32_t key, uint32_t &rank) {
+    uint32_t s = (key * 2654435761u) >> (32u - kCastSlotsLg);
+    for (uint32_t probe = 0; probe < kCastSlots; ++probe) {
+        const uint32_t old = atomicCAS(&t.key[s], kCastEmpty, key);
+        if (old == kCastEmpty || old == key) {
+            rank = atomicAdd(&t.cnt[s], 1u);
+            return s;
+        }
+        s = (s + 1u) & (kCastSlots - 1u);
+    }
+    rank = 0u;
+    return kCastSlots;
+}
+__global__ void __launch_bounds__(kBlock) k_cast_keys(const float4 *__restrict__ rays, uint32_t n, const CastBox box,
+                                                      uint32_t *__restrict__ keys, uint32_t *counts) {
+    __shared__ CastTable t;
+    cast_table_clear(t);
+    const uint32_t base = blockIdx.x * kCastChunk;
+    for (uint32_t k = 0; k < kCastPerThread; ++k) {
+        const uint32_t i = base + k * kBlock + threadIdx.x;
+        if ((uint64_t)base + k * kBlock + threadIdx.x >= n) continue;
+        const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];
+        const float o[3] = {r0.x, r0.y, r0.z}, d[3] = {r1.x, r1.y, r1.z};
+        const uint32_t key = cast_key(box, o, d);  // < kCastBuckets for every input
+        keys[i] = key;
+        uint32_t rank;
+        if (cast_table_add(t, key, rank) == kCastSlots) atomicAdd(&counts[key], 1u);
+    }
+    __syncthreads();
+    for (uint32_t s = threadIdx.x; s < kCastSlots; s += kBlock)
+        if (t.key[s] != kCastEmpty) atomicAdd(&counts[t.key[s]], t.cnt[s]);
+}
+// counts[b] -> the number of rays in buckets below b, in place: one workgroup,
+// a run of kCastBuckets / kBlock buckets per thread.
+__global__ void __launch_bounds__(kBlock) k_cast_prefix(uint32_t *counts) {
+    constexpr uint32_t kRun = kCastBuckets / kBlock;
+    static_assert(kRun * kBlock == kCastBuckets, "k_cast_prefix: whole runs");
+    __shared__ uint32_t part[kBlock];
+    uint32_t *mine = counts + threadIdx.x * kRun;
+    uint32_t sum = 0u;
+    for (uint32_t k = 0; k < kRun; ++k) sum += mine[k];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t pre = 0u;
+        for (uint32_t t = 0; t < kBlock; ++t) {
+            const uint32_t c = part[t];
+            part[t] = pre;
+            pre += c;
+        }
+    }
+    __syncthreads();
+    uint32_t pre = part[threadIdx.x];
+    for (uint32_t k = 0; k < kRun; ++k) {
+        const uint32_t c = mine[k];
+        mine[k] = pre;
+        pre += c;
+    }
+}
+// perm: bucket by bucket; a workgroup's rays of a key stay together, in any
+// order. cursors: k_cast_prefix's starts, advanced here by one reservation per
+// workgroup and key; every slot in [0, n) is written once.
+__global__ void __launch_bounds__(kBlock) k_cast_scatter(const uint32_t *__restrict__ keys, uint32_t n,
+                                                         uint32_t *cursors, uint32_t *__restrict__ perm) {
+    __shared__ CastTable t;
+    cast_table_clear(t);
+    const uint32_t base = blockIdx.x * kCastChunk;
+    uint32_t slot[kCastPerThread], rank[kCastPerThread];
+    for (uint32_t k = 0; k < kCastPerThread; ++k) {
+        const uint32_t i = base + k * kBlock + threadIdx.x;
+        slot[k] = kCastSlots, rank[k] = 0u;
+        if ((uint64_t)base + k * kBlock + threadIdx.x >= n) continue;
+        const uint32_t key = min(keys[i], kCastBuckets - 1u);
+        slot[k] = cast_table_add(t, key, rank[k]);
+        if (slot[k] == kCastSlots) rank[k] = atomicAdd(&cursors[key], 1u);  // (its slot in perm itself)
+    }
+    __syncthreads();
+    for (uint32_t s = threadIdx.x; s < kCastSlots; s += kBlock)
+        if (t.key[s] != kCastEmpty) t.cnt[s] = atomicAdd(&cursors[t.key[s]], t.cnt[s]);
+    __syncthreads();
+    for (uint32_t k = 0; k < kCastPerThread; ++k) {
+        const uint32_t i = base + k * kBlock + threadIdx.x;
+        if ((uint64_t)base + k * kBlock + threadIdx.x >= n) continue;
+        const uint32_t g = (slot[k] == kCastSlots ? 0u : t.cnt[slot[k]]) + rank[k];
+        if (g < n) perm[g] = i;
+    }
+}
+
+// One lane per ray, one segment per lane, as k_features: the scan path the
+// render's lane mode takes for the scene, then debug_record's operations, into
+// a 32-byte record (include/rtx.h rtx_ray_hit) and / or a byte. perm: the
+// COHERENT order (lane g casts ray perm[g] and writes record perm[g]); NULL:
+// lane g casts ray g. A lane past n, and a lane whose ray has an empty range,
+// !(t_max >= t_min), leaves before the scan, as k_features' and
+// k_debug_hit_world's lanes outside the image do: the wave's helpers count the
+// lanes that arrive (__ballot).
+__global__ void __launch_bounds__(kRB) k_cast(const KScene S, const float4 *__restrict__ rays, uint32_t n, float t_min,
+                                              const uint32_t *__restrict__ perm, float4 *__restrict__ hits,
+                                              uint8_t *__restrict__ occluded) {
+    __shared__ uint32_t list[list_bytes<true>() > kListBytes ? list_bytes<true>() / sizeof(uint32_t)
+                                                             : kListBytes / sizeof(uint32_t)];
+    const uint32_t g = blockIdx.x * kRB + threadIdx.x;
+    if ((uint64_t)blockIdx.x * kRB + threadIdx.x >= n) return;
+    const uint32_t i = perm ? min(perm[g], n - 1u) : g;
+    const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];
+    const f3 o = mk3(r0.x, r0.y, r0.z);
+    const f3 d = mk3(r1.x, r1.y, r1.z);
+    const float t_max = r0.w;
+    const float inf = __uint_as_float(0x7f800000u);
+    if (!(t_max >= t_min)) {  // an empty range (a NaN, negative or too short t_max): a miss, unscanned
+        if (hits) {
+            hits[2 * (size_t)i] = make_float4(inf, __int_as_float(-1), 0.0f, 0.0f);
+            hits[2 * (size_t)i + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+        if (occluded) occluded[i] = 0u;
+        return;
+    }
+    const float a = dir_len2(d);
+    const float inv_a = 1.0f / a;
+    float best = t_max;
+    const int idx = min((S.cpre && S.n_pad > kScanPfMin) ? hit_world_culled(S, o, d, a, inv_a, t_min, best, list)
+                        : S.n_pad > kScanPfMin           ? hit_world_pre<true>(S, o, d, a, inv_a, t_min, best, list)
+                                                         : hit_world_pre<false>(S, o, d, a, inv_a, t_min, best, list),
+                        (int)S.n - 1);
+    float r[10];
+    debug_record(S, o, d, best, idx, r);
+    const bool hit = idx >= 0;
+    if (hits) {
+        hits[2 * (size_t)i] = hit ? make_float4(r[1], __int_as_float(idx), r[5], r[6])
+                                  : make_float4(inf, __int_as_float(-1), 0.0f, 0.0f);
+        hits[2 * (size_t)i + 1] = make_float4(r[7], __uint_as_float(r[8] != 0.0f ? 1u : 0u), 0.0f, 0.0f);
+    }
+    if (occluded) occluded[i] = hit ? 1u : 0u;
+}
+
 // rtx_mask_from_ids, two passes (rtx_features.h): which pixels are listed, then
 // the Chebyshev growth and the number of set pixels (one atomic per wave that
 // has any). The id list travels as a kernel argument.
@@ -4504,6 +4668,26 @@ hipError_t launch_features(const KScene &s, const KFeatures &f, float4 *geom, fl
     if (f.width == 0 || f.rows_local == 0) return hipSuccess;
     const uint64_t patches = (uint64_t)ceil_div(f.width, 8u) * ceil_div(f.rows_local, 8u);
     hipLaunchKernelGGL(k_features, dim3(ceil_div(patches, kRB / 64u)), dim3(kRB), 0, stream, s, f, geom, surf, extra);
+    return hipGetLastError();
+}
+
+hipError_t launch_cast_order(const float4 *rays, uint32_t n, const CastBox &box, const KCastScratch &scratch,
+                             hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(scratch.counts, 0, kCastBuckets * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    const uint32_t blocks = ceil_div(n, kCastChunk);
+    hipLaunchKernelGGL(k_cast_keys, dim3(blocks), dim3(kBlock), 0, stream, rays, n, box, scratch.keys, scratch.counts);
+    hipLaunchKernelGGL(k_cast_prefix, dim3(1), dim3(kBlock), 0, stream, scratch.counts);
+    hipLaunchKernelGGL(k_cast_scatter, dim3(blocks), dim3(kBlock), 0, stream, scratch.keys, n, scratch.counts,
+                       scratch.perm);
+    return hipGetLastError();
+}
+
+hipError_t launch_cast(const KScene &s, const float4 *rays, uint32_t n, float t_min, const uint32_t *perm,
+                       float4 *hits, uint8_t *occluded, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_cast, dim3(ceil_div(n, kRB)), dim3(kRB), 0, stream, s, rays, n, t_min, perm, hits, occluded);
     return hipGetLastError();
 }
 

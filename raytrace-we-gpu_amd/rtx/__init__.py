@@ -52,6 +52,11 @@ FN = dict(sqrt=0, div=1, sin=2, cos=3, log2=4, exp2=5, pow=6, basehash=7,
 FRAME_LAMBERT_GUARD = 1  # rtx_frame.flags bit (RTX_FRAME_LAMBERT_GUARD)
 # rtx_refine_set_keys / rtx_refine_last_keys (RTX_REFINE_KEYS_*; "unscheduled": last_keys only)
 REFINE_KEYS = {"prepass": 0, "carried": 1, "unscheduled": 2}
+CAST_ORDERS = {"auto": 0, "given": 1, "coherent": 2}  # rtx_cast_rays (RTX_CAST_ORDER_*)
+# rtx_ray / rtx_ray_hit (include/rtx.h), 32 bytes each; a ray is also a row of 8 float32 (o, t_max, d, tag)
+RAY_DTYPE = np.dtype([("o", "<f4", (3,)), ("t_max", "<f4"), ("d", "<f4", (3,)), ("tag", "<u4")])
+RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("index", "<i4"), ("normal", "<f4", (3,)), ("front_face", "<u4"),
+                          ("reserved", "<u4", (2,))])
 GATHER_MODES = {"auto": 0, "rccl": 1, "copy": 2}  # rtx_group_create (RTX_GATHER_*)
 GROUP_MAX = 64  # RTX_GROUP_MAX
 
@@ -176,6 +181,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_pick": (C.c_int, [ctx, u32, u32, C.POINTER(rtx_hit)]),
         "rtx_mask_from_ids": (C.c_int, [ctx, vp, C.POINTER(u32), u32, u32, vp, C.POINTER(u32)]),
         "rtx_refine_masked": (C.c_int, [ctx, u32, vp, u32, C.POINTER(u32)]),
+        "rtx_cast_rays": (C.c_int, [ctx, vp, u32, C.c_float, u32, vp, vp]),
+        "rtx_cast_last_order": (C.c_int, [ctx]),
         "rtx_camera_set_aperture": (C.c_int, [C.POINTER(rtx_frame), C.c_float]),
         "rtx_part_rows": (u32, [u32, u32, u32, u32]),
         "rtx_deinterleave_rows": (C.c_int, [ctx, vp, u32, u32, u32, u32, vp]),
@@ -242,6 +249,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     optional |= {n for n in sig if n.startswith("rtx_refine")}   # ... probe "rtx_refine"
     optional |= {"rtx_adaptive_error"}                           # ... with rtx_refine_adaptive
     optional |= {"rtx_features", "rtx_features_rows", "rtx_pick", "rtx_mask_from_ids"}  # ... probe "rtx_features"
+    optional |= {"rtx_cast_rays", "rtx_cast_last_order"}         # ... probe "rtx_cast_rays"
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -255,6 +263,19 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 
 def _fptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _dev_ptr(x) -> int:
+    """The device address of a pointer, a DeviceArray (.ptr) or a torch tensor (.data_ptr()); None: 0."""
+    if x is None:
+        return 0
+    if isinstance(x, (int, np.integer)):
+        return int(x)
+    if hasattr(x, "ptr"):
+        return int(x.ptr)
+    if hasattr(x, "data_ptr"):
+        return int(x.data_ptr())
+    raise TypeError(f"not a device buffer: {type(x).__name__}")
 
 
 def _check(rc: int, what: str, lib: Optional[C.CDLL] = None):
@@ -724,6 +745,63 @@ class Context:
         _check(self._lib.rtx_refine_masked(self._h, samples, C.c_void_p(getattr(d_mask, "ptr", d_mask) or 0),
                                            max_samples, C.byref(n)), "rtx_refine_masked", self._lib)
         return int(n.value)
+
+    def cast(self, rays, t_min: float = 0.001, order: str = "auto", hits=True, occluded=False,
+             n: Optional[int] = None):
+        """What `rays` hit in the uploaded world, each over (t_min, its own
+        t_max): rtx_cast_rays. Returns (hits, occluded), None for an output
+        that was not asked for.
+
+        rays: a numpy array — (n, 8) float32 rows (o, t_max, d, tag) or n
+        RAY_DTYPE records — is uploaded, and numpy arrays come back (n
+        RAY_HIT_DTYPE records, n uint8), after a wait. A device pointer, a
+        DeviceArray or a torch tensor is used in place, asynchronously on the
+        context's stream, and DeviceArrays come back (`n`: the number of rays,
+        when the object has no shape). hits / occluded: True (allocate one),
+        False (skip it), or the caller's device buffer, which is filled and
+        returned as it is. order: "auto", "given" or "coherent" — a schedule,
+        never a different record."""
+        if isinstance(rays, np.ndarray):
+            host = np.ascontiguousarray(rays)
+            if host.dtype != RAY_DTYPE:
+                host = np.ascontiguousarray(host, np.float32).reshape(-1, 8)
+            n = host.shape[0]
+            d_rays = self.alloc((max(n, 1),), RAY_DTYPE)
+            try:
+                if n:
+                    _check(self._lib.rtx_copy_to_device(self._h, C.c_void_p(d_rays.ptr), host.ctypes.data, 32 * n),
+                           "rtx_copy_to_device", self._lib)
+                got = self.cast(d_rays, t_min, order, hits, occluded, n)
+                out = []
+                for g, dt, asked in ((got[0], RAY_HIT_DTYPE, hits), (got[1], np.uint8, occluded)):
+                    if g is None:
+                        out.append(None)
+                    elif asked is True:
+                        out.append(g.numpy()[:n])
+                        g.free()
+                    else:
+                        out.append(g)
+                return tuple(out)
+            finally:
+                d_rays.free()
+        if n is None:
+            if not hasattr(rays, "shape"):
+                raise RtxError("Context.cast: n is needed with a bare pointer")
+            n = int(rays.shape[0])
+        d_hits = self.alloc((max(n, 1),), RAY_HIT_DTYPE) if hits is True else (None if hits is False else hits)
+        d_occ = self.alloc((max(n, 1),), np.uint8) if occluded is True else (None if occluded is False else occluded)
+        _check(self._lib.rtx_cast_rays(self._h, C.c_void_p(_dev_ptr(rays)), n, t_min, CAST_ORDERS[order],
+                                       C.c_void_p(_dev_ptr(d_hits)), C.c_void_p(_dev_ptr(d_occ))),
+               "rtx_cast_rays", self._lib)
+        return d_hits, d_occ
+
+    def cast_last_order(self) -> str:
+        """"given" or "coherent": what the last cast ran ("auto" resolved) (rtx_cast_last_order)."""
+        code = self._lib.rtx_cast_last_order(self._h)
+        for name, v in CAST_ORDERS.items():
+            if v == code:
+                return name
+        raise RtxError(f"rtx_cast_last_order returned {code}")
 
     def deinterleave(self, d_gathered: int, width: int, height: int, tile_rows: int, nparts: int,
                      d_image: int):
