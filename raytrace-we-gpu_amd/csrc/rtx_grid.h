@@ -210,52 +210,58 @@ struct GridStretch {
 
 // The items of the ray (o, d): false when the lane gives up (the caller scans
 // every block). n = 0: the ray's t >= 0 part never enters the slab inside the
-// grid's box.
+// grid's box, or the lane gives up.
+// Straight-line: every output is computed for every ray and the outcome
+// (gives up / never enters / n items) is decided once at the end; a ray that
+// has items runs the ops of the early-return form (tests/setup_equiv_check.cpp
+// keeps that form as the specification) in the same order, so its outputs are
+// the same bits. Of a ray without items only the return value and n = 0 mean
+// anything: the other outputs hold whatever the ops made of it. (As nested
+// early returns, each exit zeroed all seven outputs again, in every segment's
+// set-up.)
 RTX_GD bool grid_stretch(const LayerGrid &G, float ox, float oy, float oz, float dx, float dy, float dz,
                          GridStretch &R) {
-    R.lo = R.hi = R.A = R.s = 0.0f;
-    R.c0 = R.n = R.zmajor = 0u;
     const float o2 = fmaf(ox, ox, fmaf(oy, oy, oz * oz));
     const float d2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
-    if (!(o2 <= kGridOMax * kGridOMax) || !(d2 <= 3.0e38f)) return false;  // far or non-finite
+    const bool near = o2 <= kGridOMax * kGridOMax && d2 <= 3.0e38f;  // not far, nothing non-finite
     const float inf = INFINITY;
     float t0 = 0.0f, t1 = inf;
     // grid_walk's clips, op for op (the same t0, t1); returns 1 / d (0 for d = 0)
     auto clip = [&](float o, float d, float lo, float hi) {
-        if (d == 0.0f) {
-            if (!(o >= lo && o <= hi)) t1 = -inf;
-            return 0.0f;
-        }
+        const bool par = d == 0.0f;  // parallel: outside the slab nothing, inside no cut
         const float inv = 1.0f / d;
         const float ta = (lo - o) * inv, tb = (hi - o) * inv;
-        t0 = fmaxf(t0, fminf(ta, tb));
-        t1 = fminf(t1, fmaxf(ta, tb));
-        return inv;
+        const float c0 = fmaxf(t0, fminf(ta, tb)), c1 = fminf(t1, fmaxf(ta, tb));
+        const bool outside = !(o >= lo && o <= hi);
+        t0 = par ? t0 : c0;
+        t1 = par ? (outside ? -inf : t1) : c1;
+        return par ? 0.0f : inv;
     };
     clip(oy, dy, G.ylo, G.yhi);
     const float ivx = clip(ox, dx, G.x0, G.x0 + (float)G.nx * G.h);
     const float ivz = clip(oz, dz, G.z0, G.z0 + (float)G.nz * G.h);
-    if (!(t0 <= t1)) return true;
-    if (!(t1 <= 3.0e38f)) return false;  // no end: d = 0 along x and z, or overflow
+    const bool enters = t0 <= t1;
+    const bool ends = t1 <= 3.0e38f;  // no end: d = 0 along x and z, or overflow
     const bool zm = fabsf(dz) > fabsf(dx);
     const float om = zm ? oz : ox, dm = zm ? dz : dx, on = zm ? ox : oz, dn = zm ? dx : dz;
     const float M0 = zm ? G.z0 : G.x0, N0 = zm ? G.x0 : G.z0;
     const float nM = (float)(zm ? G.nz : G.nx);
     const float s = dn * (zm ? ivz : ivx);  // |dn| <= |dm|: |s| <= 1 + 2u, or 0 (dm = 0), or not a number (1 / dm overflowed)
-    if (!(fabsf(s) <= 2.0f)) return false;
+    const bool slope = fabsf(s) <= 2.0f;
     const float a0 = (fmaf(t0, dm, om) - M0) * G.inv_h, a1 = (fmaf(t1, dm, om) - M0) * G.inv_h;
     const float b0 = (fmaf(t0, dn, on) - N0) * G.inv_h;
     R.lo = fminf(a0, a1), R.hi = fmaxf(a0, a1);
     R.s = s;
     R.A = fmaf(-a0, s, b0);
+    // (the clamps take a NaN to a bound: the conversions below are defined for every ray)
     const float c0 = grid_clampf(floorf(R.lo - kGridCoopEps), 0.0f, nM - 1.0f);
     const float c1 = grid_clampf(floorf(R.hi + kGridCoopEps), 0.0f, nM - 1.0f);
     R.c0 = (uint32_t)c0;
     R.zmajor = zm ? 1u : 0u;
     const uint32_t n = (uint32_t)c1 - (uint32_t)c0 + 1u;
-    if (n > kGridMaxSteps) return false;
-    R.n = n;
-    return true;
+    const bool items = enters && ends && slope && n <= kGridMaxSteps;
+    R.n = near && items ? n : 0u;
+    return near && (!enters || items);
 }
 
 // The cells of the item at column c of a stretch (lo, hi, A, s, zmajor):

@@ -927,8 +927,9 @@ __device__ __forceinline__ uint64_t grid_wave_mask(const KScene &S, f3 o, f3 d, 
     G.nx = gp->nx, G.nz = gp->nz, G.far_m = 0.0f, G.nblk = 0u;
     const cell_gp gc = (cell_gp)(uintptr_t)(gaddr + sizeof(LayerGrid));
     GridStretch R;
-    const bool mine_ok =
-        T.thr != -__uint_as_float(0x7f800000u) && grid_stretch(G, o.x, o.y, o.z, d.x, d.y, d.z, R);
+    // (straight-line, rtx_grid.h: run for every lane, an unsafe one's included, and judged after)
+    const bool cut_ok = grid_stretch(G, o.x, o.y, o.z, d.x, d.y, d.z, R);
+    const bool mine_ok = cut_ok & (T.thr != -__uint_as_float(0x7f800000u));
     if (__ballot(!mine_ok) != 0ull) {  // some lane scans every block: so does the wave
         RTX_DIAG_WALK(0u, 1u);
         return ~0ull;
@@ -1611,10 +1612,13 @@ __device__ __forceinline__ uint32_t launch_segs(const KParams &P, const Lane &L)
     return own + (P.carry_spp != 0u && L.slot != ~0u ? 0u : L.c0);
 }
 
+// kInvA false: the caller takes inv_a = 1 / a itself (shade: once for the
+// scattered and the restarted lanes together).
+template <bool kInvA = true>
 __device__ __forceinline__ void set_dir(Lane &L, f3 d) {
     L.d = d;
     L.a = dir_len2(d);
-    L.inv_a = 1.0f / L.a;
+    if constexpr (kInvA) L.inv_a = 1.0f / L.a;
 }
 
 __device__ __forceinline__ float pixel_seed(const KParams &P, uint32_t x, uint32_t y, uint32_t s) {
@@ -1627,13 +1631,14 @@ __device__ __forceinline__ float pixel_seed(const KParams &P, uint32_t x, uint32
     return (float)h / 4294967296.0f;
 }
 
+template <bool kInvA = true>
 __device__ __forceinline__ void begin_sample(const KParams &P, const Frame &F, uint32_t x, uint32_t y,
                                              Lane &L) {
     if (P.rng_mode == 1u) L.seed = pixel_seed(P, x, y, L.sample);
     f3 o, d;
     start_sample(F, x, y, L.seed, o, d);
     L.o = o;
-    set_dir(L, d);
+    set_dir<kInvA>(L, d);
     L.col = mk3(1.0f, 1.0f, 1.0f);
     L.bounce = 0;
 }
@@ -1791,7 +1796,8 @@ __device__ __forceinline__ HitMat hit_mat(const KScene &S, int hit) {
 
 // path_segment with the hit's record inputs given (hit >= 0; M unused on a
 // miss) and, with kSpec, the scatter's seed-determined part precomputed.
-template <bool kSpec, typename LaneT>
+// kInvA false: a scattered lane's inv_a is left to the caller (set_dir).
+template <bool kSpec, bool kInvA = true, typename LaneT>
 __device__ __forceinline__ int path_segment_m(const KParams &P, LaneT &L, int hit, float t, const HitMat &M,
                                               const ScatterSpec &sp, f3 &sky_col) {
     int mt = 3;
@@ -1870,15 +1876,15 @@ __device__ __forceinline__ int path_segment_m(const KParams &P, LaneT &L, int hi
     L.o = p;
     L.d = dir;
     L.a = dir_len2(dir);
-    L.inv_a = 1.0f / L.a;
+    if constexpr (kInvA) L.inv_a = 1.0f / L.a;
     L.bounce++;
     return L.bounce >= P.depth ? kSegBlack : kSegContinue;  // depth exhausted -> black (:286)
 }
-template <typename LaneT>
+template <bool kInvA = true, typename LaneT>
 __device__ __forceinline__ int path_segment(const KParams &P, LaneT &L, int hit, float t, f3 &sky_col) {
     HitMat M;
     if (hit >= 0) M = hit_mat(P.scene, hit);
-    return path_segment_m<false>(P, L, hit, t, M, ScatterSpec{}, sky_col);
+    return path_segment_m<false, kInvA>(P, L, hit, t, M, ScatterSpec{}, sky_col);
 }
 
 // Cross-XCD hand-off without cache maintenance. On gfx950 an agent-scope
@@ -1940,12 +1946,19 @@ __device__ __forceinline__ bool promote(const KParams &P, const Lane &L, uint32_
 // pixel at a sample boundary if it is projected to need more segments than
 // this (KParams::prom_min once the wave's queue is exhausted). Returns true
 // when the pixel was promoted.
-template <bool kCost = false, bool kRefine = false, bool kAdapt = false>
+template <bool kCost = false, bool kRefine = false, bool kAdapt = false, bool kOneDiv = false>
 __device__ __forceinline__ bool shade(const KParams &P, const Frame &F, Lane &L, int hit, float t,
                                       uint32_t prom_thr = 0u) {
     L.segs++;
     f3 c;
-    const int r = path_segment(P, L, hit, t, c);
+    // A lane leaves here with a new direction either way: scattered
+    // (path_segment) or at its next sample's start (begin_sample). Both end in
+    // inv_a = 1 / a, an IEEE divide of a dozen VALU ops, and a wave mostly has
+    // lanes of both kinds, so it paid the divide twice per segment: it is
+    // taken once, below, after the two rejoin (the same divide of the same a).
+    // kOneDiv: the small-scene render's instances; in the large-scene ones the
+    // later divide costs VGPR spills, they keep it in both branches.
+    const int r = path_segment<!kOneDiv>(P, L, hit, t, c);
     if (r == kSegSky) L.acc = L.acc + c;
     const bool ended = r != kSegContinue;
     if (ended) {
@@ -1958,7 +1971,7 @@ __device__ __forceinline__ bool shade(const KParams &P, const Frame &F, Lane &L,
             L.active = false;  // the promotion queue owns the pixel now
             return true;
         } else {
-            begin_sample(P, F, L.x, L.y, L);
+            begin_sample<!kOneDiv>(P, F, L.x, L.y, L);
         }
     } else if (kCost && P.cost_cap != 0u && L.segs - L.seg0 >= P.cost_cap) {
         // pre-pass: a pixel this long is heavy whatever its remaining
@@ -1971,6 +1984,7 @@ __device__ __forceinline__ bool shade(const KParams &P, const Frame &F, Lane &L,
         L.active = false;
         diag_pixel_end(P, L.gid);
     }
+    if constexpr (kOneDiv) L.inv_a = 1.0f / L.a;  // (a lane that just ended its pixel: unused)
     return false;
 }
 
@@ -2701,7 +2715,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
                 // the tail's pixels may be promoted (tier-1 waves already
                 // trace one ray with every lane; promoting tier-2 pixels
                 // measured 1-6 ms slower at R = 2, 4, 8: profiles/R3r_*)
-                promoted = shade<kCost, kRefine, kAdapt>(P, F, L, min(my_hit, last), my_best,
+                promoted = shade<kCost, kRefine, kAdapt, !kPF>(P, F, L, min(my_hit, last), my_best,
                                         prom_on && exhausted && H.tier == 0u ? P.prom_min : 0u);
             }
             if (prom_on)
@@ -2727,7 +2741,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
                 float best = __uint_as_float(0x7f800000u);
                 const int hit = hit_world_culled(P.scene, L.o, L.d, L.a, L.inv_a, kTMin, best, list);
                 D.section(1);
-                promoted = shade<kCost, kRefine, kAdapt>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
+                promoted = shade<kCost, kRefine, kAdapt, !kPF>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
             }
         } else if (kPF) {  // every lane of the wave fills the scan's LDS tile
             float best = __uint_as_float(0x7f800000u);
@@ -2735,7 +2749,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
             const int hit = hit_world_pre_ld<kPF, decltype(ldc), true>(P.scene, ldc, L.o, L.d, L.a, L.inv_a, kTMin,
                                                                        best, list, nullptr, 0, pf_tile, L.active);
             D.section(1);
-            if (L.active) promoted = shade<kCost, kRefine, kAdapt>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
+            if (L.active) promoted = shade<kCost, kRefine, kAdapt, !kPF>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
         } else if (L.active) {
             float best = __uint_as_float(0x7f800000u);
             // scenes that fit the coop's LDS copy resolve their candidates
@@ -2746,7 +2760,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
                                                         lmap)
                                 : hit_world_pre<kPF>(P.scene, L.o, L.d, L.a, L.inv_a, kTMin, best, list, pack);
             D.section(1);
-            promoted = shade<kCost, kRefine, kAdapt>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
+            promoted = shade<kCost, kRefine, kAdapt, !kPF>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
         }
         D.section(2);
         if (prom_on)  // pixels written this iteration (promoted ones are counted by whoever finishes them)
