@@ -34,7 +34,7 @@ $(LIBDIR)/%.o: $(SRC)/%.hip $(HDRS) | $(LIBDIR)
 $(LIBDIR)/rtx_api.o: $(SRC)/rtx_api.hip $(LIBSRCS) | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -DRTX_SRC_SHA='"$(SRC_SHA)"' -c $< -o $@
 
-$(LIBDIR)/rtx_host.o: $(SRC)/rtx_host.cpp include/rtx.h | $(LIBDIR)
+$(LIBDIR)/rtx_host.o: $(SRC)/rtx_host.cpp $(SRC)/rtx_paths.h include/rtx.h | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the group layer (several devices, one frame): host code only, no kernels
@@ -91,7 +91,7 @@ VDIR := $(LIBDIR)/variants
 
 variants: $(foreach v,$(VARIANTS),$(VDIR)/librtx_$(v).so)
 
-$(VDIR)/librtx_%.so: $(SRC)/rtx_kernels.hip $(SRC)/rtx_api.hip $(SRC)/rtx_host.cpp $(SRC)/rtx_group.hip $(SRC)/rtx_group_plan.h $(HDRS) Makefile
+$(VDIR)/librtx_%.so: $(SRC)/rtx_kernels.hip $(SRC)/rtx_api.hip $(SRC)/rtx_host.cpp $(SRC)/rtx_paths.h $(SRC)/rtx_group.hip $(SRC)/rtx_group_plan.h $(HDRS) Makefile
 	mkdir -p $(VDIR)/$*
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS_$*) -c $(SRC)/rtx_kernels.hip -o $(VDIR)/$*/k.o
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS_$*) -DRTX_SRC_SHA='"$(SRC_SHA)"' -DRTX_VARIANT='"$*"' -c $(SRC)/rtx_api.hip -o $(VDIR)/$*/a.o

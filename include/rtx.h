@@ -40,6 +40,10 @@ extern "C" {
 
 #define RTX_VERSION 145 /* 1.4.5 */
 /* ABI notes.
+ *  1.4.5 (later builds, no version bump): rtx_path_seed (the chain seed of a
+ *         pixel, on the host; groundwork for path queries along rays of the
+ *         caller's choosing); purely additive again: probe for the symbol
+ *         (dlsym "rtx_path_seed").
  *  1.4.5 (later builds, no version bump): rtx_cast_rays (rtx_ray, rtx_ray_hit,
  *         RTX_CAST_ORDER_*) and rtx_cast_last_order (batched closest-hit ray
  *         queries on device buffers, each ray with its own t_max); purely
@@ -771,6 +775,21 @@ enum { RTX_CAST_ORDER_AUTO = 0, RTX_CAST_ORDER_GIVEN = 1, RTX_CAST_ORDER_COHEREN
 RTX_API int rtx_cast_rays(rtx_ctx *ctx, const void *d_rays, uint32_t n, float t_min, uint32_t order,
                           void *d_hits, void *d_occluded);
 RTX_API int rtx_cast_last_order(rtx_ctx *ctx);   /* GIVEN or COHERENT: what the last call ran; AUTO resolved */
+/* ---- the chain seed of a pixel ------------------------------------------------
+ * (later builds, no version bump: probe with dlsym "rtx_path_seed").
+ * Host, no GPU, no context. The seed pixel (x, y)'s RNG chain starts from in
+ * a chain-mode frame with frame_index f: (float)h / 4294967296.0f, where h =
+ * base_hash(x, y) and, for f != 0, then h = base_hash(h, 0x80000000 | f) (the
+ * rule of the render's first sample and of rtx_refine's chain state, whose w
+ * is this seed advanced by the samples taken).
+ * What it is for: in a frame whose horizontal and vertical rows and lens are
+ * zero, every pixel starts every sample on the one ray (origin, fl(lower_left -
+ * origin)), whatever the jitter, and (x, y) enters through this seed alone. So
+ * "what does the ray (o, d) see, with the random numbers of pixel (x, y)" is
+ * pixel (x, y) of rtx_render_sum in the frame with origin = o, lower_left = L
+ * where fl(L - o) == d, zero horizontal and vertical, any img_w, img_h != 1 —
+ * the zero-film twin of a path query. */
+RTX_API float rtx_path_seed(uint32_t x, uint32_t y, uint32_t frame_index);
 /* Device pointer of the chain state (width*height float4; a part state: its
  * rows * width), NULL if none. */
 RTX_API void *rtx_refine_state(rtx_ctx *ctx);

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "../../include/rtx.h"
+#include "rtx_paths.h"  // rtx_path_seed: the seed rule, shared with tests/paths_check.cpp
 
 namespace {
 
@@ -209,6 +210,10 @@ int rtx_camera_set_aperture(rtx_frame *frame, float aperture) {
     frame->lens_u[3] = aperture / 2.0f;  // f4w.w = aperture / 2 (DXRayTrace.cpp:52-57)
     return RTX_OK;
 }
+
+// The chain seed of pixel (x, y) in frame frame_index (rtx_paths.h): what a
+// path query along a ray starts from to be that pixel of the ray's twin frame.
+float rtx_path_seed(uint32_t x, uint32_t y, uint32_t frame_index) { return rtx::path_seed(x, y, frame_index); }
 
 // WorldDef byte layout (DxCSApp.cpp:64-71): float4 sceneValues;
 // float4 spheres[512]; float4 matTypes[128] (4 per float4,

@@ -183,6 +183,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_refine_masked": (C.c_int, [ctx, u32, vp, u32, C.POINTER(u32)]),
         "rtx_cast_rays": (C.c_int, [ctx, vp, u32, C.c_float, u32, vp, vp]),
         "rtx_cast_last_order": (C.c_int, [ctx]),
+        "rtx_path_seed": (C.c_float, [u32, u32, u32]),
         "rtx_camera_set_aperture": (C.c_int, [C.POINTER(rtx_frame), C.c_float]),
         "rtx_part_rows": (u32, [u32, u32, u32, u32]),
         "rtx_deinterleave_rows": (C.c_int, [ctx, vp, u32, u32, u32, u32, vp]),
@@ -250,6 +251,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     optional |= {"rtx_adaptive_error"}                           # ... with rtx_refine_adaptive
     optional |= {"rtx_features", "rtx_features_rows", "rtx_pick", "rtx_mask_from_ids"}  # ... probe "rtx_features"
     optional |= {"rtx_cast_rays", "rtx_cast_last_order"}         # ... probe "rtx_cast_rays"
+    optional |= {"rtx_path_seed"}                                # ... probe "rtx_path_seed"
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -276,6 +278,16 @@ def _dev_ptr(x) -> int:
     if hasattr(x, "data_ptr"):
         return int(x.data_ptr())
     raise TypeError(f"not a device buffer: {type(x).__name__}")
+
+
+def path_seed(x: int, y: int, frame_index: int = 0) -> np.float32:
+    """The chain seed of pixel (x, y) in frame frame_index (rtx_path_seed; host, no GPU): the seed
+    with which a ray (o, d) sees what that pixel sees in the frame with origin o, lower_left o + d and
+    zero horizontal and vertical rows."""
+    lib = load_library()
+    if not hasattr(lib, "rtx_path_seed"):
+        raise RtxError("this librtx has no rtx_path_seed")
+    return np.float32(lib.rtx_path_seed(x, y, frame_index))
 
 
 def _check(rc: int, what: str, lib: Optional[C.CDLL] = None):
