@@ -59,11 +59,12 @@ struct FrameVals {
 // arguments (scalar loads through an opaque kernarg pointer), not held for
 // the whole kernel: held, their 21 SGPRs were spilled to VGPR lanes and
 // every sample start paid ~18 v_readlane restores in VALU issue slots.
-// Every kernel that starts samples takes `const KParams` as its only
-// argument, so the kernarg segment begins with it.
+// Every kernel that starts samples takes `const KParams` as its first
+// argument, so the kernarg segment begins with it (the check build compares:
+// load_frame).
 struct Frame {};
 typedef const __attribute__((address_space(4))) KParams *kparams_cp;
-__device__ __forceinline__ FrameVals frame_vals() {
+__device__ __forceinline__ kparams_cp kernarg_here() {
     // opaque (reloaded at each use, never hoisted into live SGPRs): passed
     // through a VGPR by an empty asm (an SGPR-constrained asm in divergent
     // code does not compile), then made uniform again by readfirstlane
@@ -72,7 +73,35 @@ __device__ __forceinline__ FrameVals frame_vals() {
     asm volatile("" : "+v"(lo), "+v"(hi));
     lo = __builtin_amdgcn_readfirstlane(lo);
     hi = __builtin_amdgcn_readfirstlane(hi);
-    kparams_cp kp = (kparams_cp)(uintptr_t)(((uint64_t)hi << 32) | lo);
+    return (kparams_cp)(uintptr_t)(((uint64_t)hi << 32) | lo);
+}
+// The launch's parameters for one site of a kernel whose only (or first)
+// argument is `const KParams P`: P itself, or (kLate) the same values behind
+// a kernarg pointer formed right here, so that the fields the site reads are
+// scalar loads next to their use and not SGPRs held, spilled to VGPR lanes
+// and restored by v_readlane across the whole lane-mode loop. One call per
+// site, every field of the site through its result. kLate is the small-scene
+// k_render instances' (the large-scene ones are compiled as before).
+template <bool kLate>
+__device__ __forceinline__ decltype(auto) params_at(const KParams &P) {
+    if constexpr (kLate) {
+        return (*kernarg_here());
+    } else {
+        return (P);
+    }
+}
+// Memory a late-read parameter points to is global: a pointer loaded through
+// kernarg_here() is a generic one to the compiler (flat instructions) unless
+// it is told (the by-value P's pointers it knows to be global). The queue
+// atomic is told; the once-per-pixel accesses are left flat.
+template <typename T>
+using global_p = T __attribute__((address_space(1))) *;
+template <typename T>
+__device__ __forceinline__ global_p<T> as_global(T *p) {
+    return (global_p<T>)(uintptr_t)p;
+}
+__device__ __forceinline__ FrameVals frame_vals() {
+    kparams_cp kp = kernarg_here();
     FrameVals F;
     F.org = mk3(kp->org[0], kp->org[1], kp->org[2]);
     F.hor = mk3(kp->hor[0], kp->hor[1], kp->hor[2]);
@@ -1607,7 +1636,8 @@ struct Lane {
 // pixel's before the hand-over (slot ~0u). A queue pixel's c0 in a carried
 // launch is the previous launch's count (dyn_level) and no part of this one;
 // a pixel the render restarted counts from 0 (c0 is 0 there).
-__device__ __forceinline__ uint32_t launch_segs(const KParams &P, const Lane &L) {
+template <typename PT>
+__device__ __forceinline__ uint32_t launch_segs(const PT &P, const Lane &L) {
     const uint32_t own = L.segs - (L.seg0 & ~kSeg0Restart);
     return own + (P.carry_spp != 0u && L.slot != ~0u ? 0u : L.c0);
 }
@@ -1621,7 +1651,8 @@ __device__ __forceinline__ void set_dir(Lane &L, f3 d) {
     if constexpr (kInvA) L.inv_a = 1.0f / L.a;
 }
 
-__device__ __forceinline__ float pixel_seed(const KParams &P, uint32_t x, uint32_t y, uint32_t s) {
+template <typename PT>
+__device__ __forceinline__ float pixel_seed(const PT &P, uint32_t x, uint32_t y, uint32_t s) {
     // Reference: p = float(baseHash(DTid.xy)) / float(0xffffffffU)  (:295)
     uint32_t h = base_hash(x, y);
     if (P.rng_mode == 1u)  // per-sample re-seed (extension)
@@ -1631,8 +1662,8 @@ __device__ __forceinline__ float pixel_seed(const KParams &P, uint32_t x, uint32
     return (float)h / 4294967296.0f;
 }
 
-template <bool kInvA = true>
-__device__ __forceinline__ void begin_sample(const KParams &P, const Frame &F, uint32_t x, uint32_t y,
+template <bool kInvA = true, typename PT>
+__device__ __forceinline__ void begin_sample(const PT &P, const Frame &F, uint32_t x, uint32_t y,
                                              Lane &L) {
     if (P.rng_mode == 1u) L.seed = pixel_seed(P, x, y, L.sample);
     f3 o, d;
@@ -1659,8 +1690,8 @@ __device__ __forceinline__ void begin_sample(const KParams &P, const Frame &F, u
 #ifndef RTX_FINISH_IN_LOOP  // A/B: 1 = a staged pixel is finished here too, and k_unpermute only moves it
 #define RTX_FINISH_IN_LOOP 0
 #endif
-template <bool kRefine = false, bool kAdapt = false>
-__device__ __forceinline__ void output_pixel(const KParams &P, uint32_t gid, f3 sum, uint32_t slot = ~0u,
+template <bool kRefine = false, bool kAdapt = false, typename PT>
+__device__ __forceinline__ void output_pixel(const PT &P, uint32_t gid, f3 sum, uint32_t slot = ~0u,
                                              uint32_t n_new = 0u) {
     float n = (float)(kAdapt ? n_new : kRefine ? P.out_n : P.spp);
     if (P.accum) {  // progressive: running linear sum over frames
@@ -1696,8 +1727,8 @@ __device__ __forceinline__ void output_pixel(const KParams &P, uint32_t gid, f3 
 // them. Its chain slot still holds the previous launch's sum (written only by
 // whoever finishes the pixel, and that is this lane, below); a fresh state's
 // slot holds anything, and n_old == 0 reads none of it.
-template <bool kCost = false, bool kRefine = false, bool kAdapt = false>
-__device__ __forceinline__ void write_pixel(const KParams &P, const Lane &L) {
+template <bool kCost = false, bool kRefine = false, bool kAdapt = false, typename PT>
+__device__ __forceinline__ void write_pixel(const PT &P, const Lane &L) {
     if constexpr (kAdapt) {
         const float4 old = P.chain_out[L.gid];
         const uint32_t n_old = P.count[L.gid];
@@ -1880,6 +1911,9 @@ __device__ __forceinline__ int path_segment_m(const KParams &P, LaneT &L, int hi
     L.bounce++;
     return L.bounce >= P.depth ? kSegBlack : kSegContinue;  // depth exhausted -> black (:286)
 }
+// (The three scene pointers hit_mat reads stay held in SGPRs: read late like
+// the sample-end fields, once per segment, they cost more VALU than their
+// restores did, RESULTS.md S14.)
 template <bool kInvA = true, typename LaneT>
 __device__ __forceinline__ int path_segment(const KParams &P, LaneT &L, int hit, float t, f3 &sky_col) {
     HitMat M;
@@ -1912,8 +1946,8 @@ __device__ __forceinline__ void agent_store_order() {
 // whose L2 does not see these stores otherwise): the fields, a wait for their
 // completion, then the epoch word (agent_store_order). The kRefine instances
 // also publish the segments so far in word 6 (take_promoted reads it into c0).
-template <bool kRefine = false>
-__device__ __forceinline__ bool promote(const KParams &P, const Lane &L, uint32_t min_segs) {
+template <bool kRefine = false, typename PT>
+__device__ __forceinline__ bool promote(const PT &P, const Lane &L, uint32_t min_segs) {
     // samples traced in this launch (>= 1 here): after the pre-pass's
     // cost_spp, or from sample 0 for a pixel the pre-pass stopped (cost_cap;
     // kSeg0Restart in seg0)
@@ -1946,7 +1980,10 @@ __device__ __forceinline__ bool promote(const KParams &P, const Lane &L, uint32_
 // pixel at a sample boundary if it is projected to need more segments than
 // this (KParams::prom_min once the wave's queue is exhausted). Returns true
 // when the pixel was promoted.
-template <bool kCost = false, bool kRefine = false, bool kAdapt = false, bool kOneDiv = false>
+// kLate: the launch's fields are read where they are used (params_at): one
+// site for everything a sample's end reads (spp, the output, promotion and cost fields, the RNG mode); prom_thr
+// is then only the flag, the threshold is KParams::prom_min read there.
+template <bool kCost = false, bool kRefine = false, bool kAdapt = false, bool kOneDiv = false, bool kLate = false>
 __device__ __forceinline__ bool shade(const KParams &P, const Frame &F, Lane &L, int hit, float t,
                                       uint32_t prom_thr = 0u) {
     L.segs++;
@@ -1962,16 +1999,18 @@ __device__ __forceinline__ bool shade(const KParams &P, const Frame &F, Lane &L,
     if (r == kSegSky) L.acc = L.acc + c;
     const bool ended = r != kSegContinue;
     if (ended) {
+        const auto &K = params_at<kLate>(P);
         L.sample++;
-        if (L.sample >= P.spp) {
-            write_pixel<kCost, kRefine, kAdapt>(P, L);
+        if (L.sample >= K.spp) {
+            write_pixel<kCost, kRefine, kAdapt>(K, L);
             L.active = false;
             diag_pixel_end(P, L.gid);
-        } else if (!kCost && prom_thr != 0u && promote<kRefine>(P, L, prom_thr)) {
+        } else if (!kCost && prom_thr != 0u && (!kLate || K.prom_min != 0u) &&
+                   promote<kRefine>(K, L, kLate ? K.prom_min : prom_thr)) {
             L.active = false;  // the promotion queue owns the pixel now
             return true;
         } else {
-            begin_sample<!kOneDiv>(P, F, L.x, L.y, L);
+            begin_sample<!kOneDiv>(K, F, L.x, L.y, L);
         }
     } else if (kCost && P.cost_cap != 0u && L.segs - L.seg0 >= P.cost_cap) {
         // pre-pass: a pixel this long is heavy whatever its remaining
@@ -1988,7 +2027,8 @@ __device__ __forceinline__ bool shade(const KParams &P, const Frame &F, Lane &L,
     return false;
 }
 
-__device__ __forceinline__ void lane_pixel(const KParams &P, uint32_t gid, uint32_t &x, uint32_t &y) {
+template <typename PT>
+__device__ __forceinline__ void lane_pixel(const PT &P, uint32_t gid, uint32_t &x, uint32_t &y) {
     const uint32_t lr = gid / P.width;  // local row
     x = gid - lr * P.width;
     const uint32_t j = lr / P.tile_rows;
@@ -2009,7 +2049,9 @@ __device__ __forceinline__ void count_segments(const KParams &P, uint32_t segs) 
 // build the GPU tests run) compares what it reads there with `P` — the
 // kernel's own argument at every call site — and flags the launch
 // (kErrKernarg: rtx_sync / rtx_get_stats report it) if a kernel ever breaks
-// that layout.
+// that layout. The same for every field a small-scene k_render instance
+// reads late (params_at): a field added to such a site is
+// added to the comparison below.
 #ifndef RTX_CHECK_KERNARG
 #define RTX_CHECK_KERNARG 0
 #endif
@@ -2021,15 +2063,33 @@ __device__ __forceinline__ Frame load_frame(const KParams &P) {
                           __float_as_uint(v.org.x) == __float_as_uint(P.org[0]) &&
                           __float_as_uint(v.llc.z) == __float_as_uint(P.llc[2]) &&
                           __float_as_uint(v.lens_r) == __float_as_uint(P.lens_r);
-        if (!same && P.errors && (threadIdx.x & 63u) == 0u) atomicOr(P.errors, kErrKernarg);
+        // ... and every field a site reads through params_at
+        const kparams_cp kp = kernarg_here();
+        bool late = true;
+        auto eq = [&late](auto a, auto b) { late = late && a == b; };
+        eq(kp->out, P.out), eq(kp->out_slot, P.out_slot), eq(kp->stage_tag, P.stage_tag);
+        eq(kp->queue, P.queue), eq(kp->spp, P.spp), eq(kp->width, P.width), eq(kp->tile_rows, P.tile_rows);
+        eq(kp->part, P.part), eq(kp->nparts, P.nparts), eq(kp->rng_mode, P.rng_mode);
+        eq(kp->frame_index, P.frame_index), eq(kp->accum, P.accum), eq(kp->accum_frames, P.accum_frames);
+        eq(kp->perm, P.perm), eq(kp->cost_out, P.cost_out), eq(kp->cost_spp, P.cost_spp), eq(kp->state, P.state);
+        eq(kp->prio_slots, P.prio_slots), eq(kp->coop_max, P.coop_max), eq(kp->prio_t1, P.prio_t1);
+        eq(kp->prio_t2, P.prio_t2), eq(kp->prio_hot, P.prio_hot), eq(kp->chunk, P.chunk), eq(kp->prom, P.prom);
+        eq(kp->errors, P.errors), eq(kp->err_diag, P.err_diag), eq(kp->prom_q, P.prom_q);
+        eq(kp->prom_cap, P.prom_cap), eq(kp->prom_min, P.prom_min), eq(kp->epoch, P.epoch);
+        eq(kp->heavy, P.heavy), eq(kp->cost_in, P.cost_in);
+        for (int i = 0; i < 3; ++i) eq(__float_as_uint(kp->dyn_bar[i]), __float_as_uint(P.dyn_bar[i]));
+        eq(kp->chain_in, P.chain_in), eq(kp->chain_out, P.chain_out), eq(kp->out_n, P.out_n);
+        eq(kp->cost_map, P.cost_map), eq(kp->carry_spp, P.carry_spp), eq(kp->qlen, P.qlen);
+        eq(kp->count, P.count), eq(kp->err, P.err);
+        if (!(same && late) && P.errors && (threadIdx.x & 63u) == 0u) atomicOr(P.errors, kErrKernarg);
     }
     return Frame{};
 }
 
 // Start pixel `gid` (local index of this launch's rows) on this lane.
 // Launches with spp == 0 or depth == 0 never get here (k_render_trivial).
-template <bool kRefine = false>
-__device__ __forceinline__ void start_pixel(const KParams &P, const Frame &F, uint32_t gid, Lane &L) {
+template <bool kRefine = false, typename PT>
+__device__ __forceinline__ void start_pixel(const PT &P, const Frame &F, uint32_t gid, Lane &L) {
     L.gid = gid;
     lane_pixel(P, gid, L.x, L.y);
     L.seg0 = L.segs;
@@ -2085,8 +2145,8 @@ __device__ __forceinline__ void set_prio(uint32_t p) {
 // A carried refine launch (KParams::carry_spp) has no pre-pass figures: the
 // rate is seeded by the previous launch's count over its carry_spp samples,
 // (carried + segments so far) / (carry_spp + samples so far).
-template <bool kRefine = false>
-__device__ __forceinline__ uint32_t dyn_level(const KParams &P, const Lane &L, float m) {
+template <bool kRefine = false, typename PT>
+__device__ __forceinline__ uint32_t dyn_level(const PT &P, const Lane &L, float m) {
     float rem = 0.0f;
     if (L.active) {
         const bool rs = (L.seg0 & kSeg0Restart) != 0u;
@@ -2108,14 +2168,27 @@ __device__ __forceinline__ uint32_t dyn_level(const KParams &P, const Lane &L, f
                                                       : 0u;
 }
 
+// atomicAdd on the queue head (kLate: through a late-read pointer, global all the same)
+template <bool kLate>
+__device__ __forceinline__ uint32_t queue_take(uint32_t *q, uint32_t n) {
+    if constexpr (kLate) {
+        return __hip_atomic_fetch_add(as_global(q), n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+        return atomicAdd(q, n);
+    }
+}
+
 // Persistent-lane pixel queue: every idle lane of the wave takes the next
 // slot of [lo, hi) (the queue counter counts from lo); ONE atomic per wave
 // per refill (ballot + lane rank). Returns true once the queue is
 // exhausted (wave-uniform).
-template <bool kRefine = false>
-__device__ __forceinline__ bool refill(const KParams &P, const Frame &F, uint32_t lo, uint32_t hi, Lane &L) {
+// kLate: the queue, perm and state fields (and start_pixel's) are read from
+// the kernel arguments here, once a lane is idle (params_at).
+template <bool kRefine = false, bool kLate = false>
+__device__ __forceinline__ bool refill(const KParams &P0, const Frame &F, uint32_t lo, uint32_t hi, Lane &L) {
     const uint64_t idle = __ballot(!L.active);
     if (idle == 0ull) return false;
+    const auto &P = params_at<kLate>(P0);
     const uint32_t cnt = (uint32_t)__popcll(idle);
     if (P.chunk > 1u) {
         // The wave's idle lanes take consecutive slots of a private run
@@ -2131,7 +2204,7 @@ __device__ __forceinline__ bool refill(const KParams &P, const Frame &F, uint32_
         if (cnt > avail) {
             n = cnt - avail;
             if (L.cb < hi - (hi - lo) / 8u) n = max(n, P.chunk);
-            if (lane == 0u) nb = atomicAdd(P.queue, n);
+            if (lane == 0u) nb = queue_take<kLate>(P.queue, n);
             nb = lo + (uint32_t)__shfl((int)nb, 0, 64);
         }
         if (!L.active) {
@@ -2139,7 +2212,7 @@ __device__ __forceinline__ bool refill(const KParams &P, const Frame &F, uint32_
             if (g < hi) {
                 start_pixel<kRefine>(P, F, P.perm ? P.perm[g] : g, L);
                 L.slot = g;
-                diag_pixel_start(P, L.gid, 0);
+                diag_pixel_start(P0, L.gid, 0);
             }
         }
         if (cnt > avail) {
@@ -2153,14 +2226,14 @@ __device__ __forceinline__ bool refill(const KParams &P, const Frame &F, uint32_
     const int leader = __ffsll((long long)idle) - 1;
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t base = 0;
-    if ((int)lane == leader) base = atomicAdd(P.queue, cnt);
+    if ((int)lane == leader) base = queue_take<kLate>(P.queue, cnt);
     base = lo + __shfl(base, leader, 64);
     if (!L.active) {
         const uint32_t g = base + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
         if (g < hi) {
             start_pixel<kRefine>(P, F, P.perm ? P.perm[g] : g, L);
             L.slot = g;
-            diag_pixel_start(P, L.gid, 0);
+            diag_pixel_start(P0, L.gid, 0);
         }
     }
     return base + cnt >= hi;
@@ -2181,8 +2254,8 @@ struct HeavyState {
     bool t1_done, t2_done;
     uint32_t tier;       // 1, 2, or 0 (normal wave)
 };
-template <bool kRefine = false>
-__device__ __forceinline__ bool take_from(const KParams &P, const Frame &F, uint32_t *ctr, uint32_t lo, uint32_t hi,
+template <bool kRefine = false, typename PT>
+__device__ __forceinline__ bool take_from(const KParams &P0, const PT &P, const Frame &F, uint32_t *ctr, uint32_t lo, uint32_t hi,
                                           uint32_t room, uint64_t act, Lane &L, bool &done) {
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t h = 0;
@@ -2197,22 +2270,23 @@ __device__ __forceinline__ bool take_from(const KParams &P, const Frame &F, uint
     if (!L.active && rk < take) {
         start_pixel<kRefine>(P, F, P.perm[h + rk], L);
         L.slot = h + rk;
-        diag_pixel_start(P, L.gid, ctr == P.heavy ? 1ull : 2ull);
+        diag_pixel_start(P0, L.gid, ctr == P.heavy ? 1ull : 2ull);
     }
     if (h + room >= hi) done = true;
     return true;
 }
-template <bool kRefine = false>
-__device__ __forceinline__ void take_heavy(const KParams &P, const Frame &F, HeavyState &H, Lane &L) {
+template <bool kRefine = false, bool kLate = false>
+__device__ __forceinline__ void take_heavy(const KParams &P0, const Frame &F, HeavyState &H, Lane &L) {
+    const auto &P = params_at<kLate>(P0);  // the heavy slots' site
     const uint64_t act = __ballot(L.active);
     const uint32_t have = (uint32_t)__popcll(act);
     if (have == 0u) H.tier = 0;
-    if (have == 0u && !H.t1_done && take_from<kRefine>(P, F, P.heavy, 0, H.k1, kHeavy1, act, L, H.t1_done)) {
+    if (have == 0u && !H.t1_done && take_from<kRefine>(P0, P, F, P.heavy, 0, H.k1, kHeavy1, act, L, H.t1_done)) {
         H.tier = 1;
         return;
     }
     if (H.tier == 1u) return;  // tier-1 waves keep to their few rays
-    if (!H.t2_done && have < kHeavy2 && take_from<kRefine>(P, F, P.heavy + 2, H.k1, H.kh, kHeavy2 - have, act, L, H.t2_done))
+    if (!H.t2_done && have < kHeavy2 && take_from<kRefine>(P0, P, F, P.heavy + 2, H.k1, H.kh, kHeavy2 - have, act, L, H.t2_done))
         H.tier = 2;
 }
 
@@ -2410,7 +2484,8 @@ __device__ __forceinline__ void regroup(Lane &W, uint32_t lg, uint32_t nlg, uint
 // (kPromValveTicks: rtx_internal.h)
 constexpr unsigned long long kBeatTicks = kPromValveTicks / 16u;
 constexpr uint32_t kBeatShift = 10;  // prom[4] holds s_memrealtime >> 10 (10.24 us units, wraps every ~12 h)
-__device__ __forceinline__ void flag_error(const KParams &P, uint32_t bit) {
+template <typename PT>
+__device__ __forceinline__ void flag_error(const PT &P, uint32_t bit) {
     if (P.errors && (threadIdx.x & 63u) == 0u) atomicOr(P.errors, bit);
 }
 struct Valve {  // 32-bit s_memrealtime ticks (wrap after 42 s; the valve is shorter): few SGPRs in k_render
@@ -2438,7 +2513,8 @@ static_assert(kPromValveTicks < (1ull << 31), "the valve's 32-bit clock");
 // adds the launch's queue counters, which stay in memory after it). Kept to
 // one atomic: the record's code sits in k_render, whose registers are tight
 // (a larger record moved the C2 render's spill code).
-__device__ __forceinline__ void valve_fire(const KParams &P, uint32_t bit, uint32_t who, const Valve &V) {
+template <typename PT>
+__device__ __forceinline__ void valve_fire(const PT &P, uint32_t bit, uint32_t who, const Valve &V) {
     flag_error(P, bit);
     if (P.err_diag == nullptr || (threadIdx.x & 63u) != 0u) return;
     const unsigned long long now = __builtin_amdgcn_s_memrealtime();
@@ -2450,17 +2526,19 @@ __device__ __forceinline__ void valve_fire(const KParams &P, uint32_t bit, uint3
     atomicCAS(P.err_diag, 0ull, rec);
 }
 // The heartbeat (wave-uniform; `last` is the wave's previous beat).
+template <bool kLate = false>
 __device__ __forceinline__ void beat(const KParams &P, unsigned long long &last) {
     const unsigned long long now = __builtin_amdgcn_s_memrealtime();
     if (now - last > kBeatTicks) {
         last = now;
         if ((threadIdx.x & 63u) == 0u)
-            __hip_atomic_store(&P.prom[4], (uint32_t)(now >> kBeatShift), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&params_at<kLate>(P).prom[4], (uint32_t)(now >> kBeatShift), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
-template <bool kRefine = false>
-__device__ __forceinline__ bool take_promoted(const KParams &P, const Frame &F, uint32_t npix, uint32_t target,
+template <bool kRefine = false, bool kLate = false>
+__device__ __forceinline__ bool take_promoted(const KParams &P0, const Frame &F, uint32_t npix, uint32_t target,
                                               bool helper, Lane &W) {
+    const auto &P = params_at<kLate>(P0);  // the service's site: held while it polls, not across the render loop
     Valve V;
     V.start();
     uint32_t seen = ~0u;
@@ -2518,7 +2596,7 @@ __device__ __forceinline__ bool take_promoted(const KParams &P, const Frame &F, 
             W.slot = ~0u;
             W.active = true;
             begin_sample(P, F, W.x, W.y, W);
-            diag_pixel_start(P, W.gid, 3ull);
+            diag_pixel_start(P0, W.gid, 3ull);
             return true;
         }
         if (h >= t) __builtin_amdgcn_s_sleep(127);
@@ -2595,6 +2673,9 @@ template <bool kPersist, bool kCost = false, bool kPF = false, bool kLin = false
 __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
     static_assert(!kAdapt || (kPersist && kRefine && !kCost), "adaptive: the persistent refine render only");
     constexpr bool kCulled = kPF && !kLin;  // the culled scan (large scenes, not the linear mode)
+    // the small-scene instances read the launch's fields where they are used
+    // (params_at); the large-scene ones are compiled as before
+    constexpr bool kLate = !kPF;
     // dynamic LDS: [candidate list, list_bytes<kPF>][coop rays, kCoopBytes][coop LDS copy of the spheres]
     extern __shared__ __attribute__((aligned(16))) unsigned char s_mem[];
     uint32_t *list = reinterpret_cast<uint32_t *>(s_mem);
@@ -2656,23 +2737,25 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
     Diag D;
     D.begin();
     for (;;) {
-        if (!(H.t1_done && H.t2_done) && (H.tier != 0u || __ballot(L.active) == 0ull)) take_heavy<kRefine>(P, F, H, L);
+        if (!(H.t1_done && H.t2_done) && (H.tier != 0u || __ballot(L.active) == 0ull))
+            take_heavy<kRefine, kLate>(P, F, H, L);
         if (H.tier != 0u && __ballot(L.active) == 0ull) H.tier = 0;  // drained, no heavy slot left
         const bool heavy = H.tier != 0u;
-        if (!heavy && !exhausted) exhausted = refill<kRefine>(P, F, kh, qlen, L);
+        if (!heavy && !exhausted) exhausted = refill<kRefine, kLate>(P, F, kh, qlen, L);
         if (kPersist && kCost && P.pre_done && exhausted && pre_stop(P, npix, L)) continue;
         const uint64_t act = __ballot(L.active);
         D.section(0);
         if (act == 0ull) {  // spp, depth > 0: idle after both queues => drained
             if (!prom_on) break;
             if (written != 0u && (threadIdx.x & 63u) == 0u)
-                __hip_atomic_fetch_add(&P.prom[2], written, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(&params_at<kLate>(P).prom[2], written, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
             written = 0;
             uint32_t srv = 0;
             if ((threadIdx.x & 63u) == 0u) srv = atomicCAS(&s_server, 0u, threadIdx.x / 64u + 1u);
             srv = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)srv, 0, 64));
             if (srv != 0u && srv != threadIdx.x / 64u + 1u) break;  // another wave serves this block
-            if (!take_promoted<kRefine>(P, F, npix, owned, false, L)) {
+            if (!take_promoted<kRefine, kLate>(P, F, npix, owned, false, L)) {
                 // leaving: free the block's server slot, so that a wave of
                 // this block that goes idle later can serve in its place
                 if ((threadIdx.x & 63u) == 0u) atomicExch(&s_server, 0u);
@@ -2687,16 +2770,28 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
         // beats, not only those that have seen the queue exhausted: a wave
         // whose lanes are all busy never refills and never learns it (R7e: a
         // 2 ms stress valve fired while only such waves were tracing)
-        if (prom_on) beat(P, last_beat);
+        if (prom_on) beat<kLate>(P, last_beat);
         D.iteration(act);
-        if (heavy || (exhausted && (uint32_t)__popcll(act) <= P.coop_max)) {
+        // (two sites: the tail's size here, read once the queue is exhausted, and
+        // a heavy wave's priority inside. One pointer for both, formed before
+        // the branch, cost the C2 instance 13 more spilled VGPRs.)
+        if (heavy || (exhausted && (uint32_t)__popcll(act) <= params_at<kLate>(P).coop_max)) {
             D.tail_iteration();
             // Frame tail: the few pixels left in this wave are its critical
             // path; trace their rays together, several lanes per ray.
             float my_best = __uint_as_float(0x7f800000u);
             bool my_seq = false;
             // this wave carries the frame's critical path: tier 1 > tier 2 > tail
-            set_prio(H.tier == 1u ? P.prio_t1 : H.tier == 2u ? P.prio_t2 : (uint32_t)kTailPrio);
+            if constexpr (kLate) {
+                uint32_t prio = (uint32_t)kTailPrio;
+                if (H.tier != 0u) {  // the heavy wave's site
+                    const auto &K = params_at<true>(P);
+                    prio = H.tier == 1u ? K.prio_t1 : K.prio_t2;
+                }
+                set_prio(prio);
+            } else {
+                set_prio(H.tier == 1u ? P.prio_t1 : H.tier == 2u ? P.prio_t2 : (uint32_t)kTailPrio);
+            }
             unsigned long long *ctqp;
             unsigned long long *cp = D.coop_begin(H.tier, ctqp);
             bool promoted = false;
@@ -2715,8 +2810,13 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
                 // the tail's pixels may be promoted (tier-1 waves already
                 // trace one ray with every lane; promoting tier-2 pixels
                 // measured 1-6 ms slower at R = 2, 4, 8: profiles/R3r_*)
-                promoted = shade<kCost, kRefine, kAdapt, !kPF>(P, F, L, min(my_hit, last), my_best,
-                                        prom_on && exhausted && H.tier == 0u ? P.prom_min : 0u);
+                // (shade's promotion argument: the threshold, or with kLate only whether to look at it)
+                if constexpr (kLate)
+                    promoted = shade<kCost, kRefine, kAdapt, !kPF, true>(P, F, L, min(my_hit, last), my_best,
+                                            prom_on && exhausted && H.tier == 0u ? 1u : 0u);
+                else
+                    promoted = shade<kCost, kRefine, kAdapt, !kPF>(P, F, L, min(my_hit, last), my_best,
+                                            prom_on && exhausted && H.tier == 0u ? P.prom_min : 0u);
             }
             if (prom_on)
                 written += (uint32_t)__popcll(act & ~__ballot(L.active)) - (uint32_t)__popcll(__ballot(promoted));
@@ -2729,10 +2829,13 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
         // lane mode: a wave that holds one of the heaviest pixels of the
         // normal queue (its first prio_slots slots) runs at the top priority,
         // so its time per segment is not stretched by the SIMD's other waves
-        if (P.cost_in) {
-            set_prio(dyn_level<kRefine>(P, L, dyn_m));
-        } else {
-            set_prio(__ballot(L.active && L.slot < kh + P.prio_slots) != 0ull ? P.prio_hot : 0u);
+        {
+            const auto &K = params_at<kLate>(P);  // the priority's site: dyn_level's inputs, or the hot slots
+            if (K.cost_in) {
+                set_prio(dyn_level<kRefine>(K, L, dyn_m));
+            } else {
+                set_prio(__ballot(L.active && L.slot < kh + K.prio_slots) != 0ull ? K.prio_hot : 0u);
+            }
         }
         bool promoted = false;
         D.rays(P, L.o, L.d, L.active, L.slot);
@@ -2760,7 +2863,11 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
                                                         lmap)
                                 : hit_world_pre<kPF>(P.scene, L.o, L.d, L.a, L.inv_a, kTMin, best, list, pack);
             D.section(1);
-            promoted = shade<kCost, kRefine, kAdapt, !kPF>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
+            // (the small-scene instances' branch; compiled into the others too, where the argument is the threshold)
+            if constexpr (kLate)
+                promoted = shade<kCost, kRefine, kAdapt, !kPF, true>(P, F, L, min(hit, last), best, prom_on && exhausted ? 1u : 0u);
+            else
+                promoted = shade<kCost, kRefine, kAdapt, !kPF>(P, F, L, min(hit, last), best, prom_on && exhausted ? P.prom_min : 0u);
         }
         D.section(2);
         if (prom_on)  // pixels written this iteration (promoted ones are counted by whoever finishes them)

@@ -3,7 +3,13 @@
 ONE process, interleaved rounds (cdna_hip_programming.md §5.4 rule 24).
 Every variant's frame must be bit-identical to the first one's.
 
-    python tools/variant_bench.py [--rounds 3] [--frames 2] [--spp 100] [variant ...]
+    python tools/variant_bench.py [--rounds 3] [--frames 2] [--spp 100] [--schedule S] [variant ...]
+
+--schedule installs a schedule in every variant's context: `lane-only` (no
+heavy slots, no k_trace, no promotion, a tail of one lane: every pixel is
+traced in lane mode to its end, so a build without the cold regions computes
+the same frame; its times are not the product's, compare counters), or
+field=value pairs separated by commas (rtx_schedule's names).
 """
 import argparse
 import glob
@@ -26,6 +32,7 @@ ap.add_argument("--spp", type=int, default=100)
 ap.add_argument("--grid", type=int, default=11)
 ap.add_argument("--max-spheres", type=int, default=0)
 ap.add_argument("--rng", choices=["chain", "per-sample"], default="chain")
+ap.add_argument("--schedule", default="")
 ap.add_argument("names", nargs="*")
 a = ap.parse_args()
 
@@ -36,6 +43,17 @@ if a.names:
 world = rtx.random_world(a.grid, capacity=a.max_spheres or None, depth=50, spp=a.spp)
 frame = rtx.camera_look_at(a.width, a.height, aspect=a.width / a.height)
 frame.rng_mode = 1 if a.rng == "per-sample" else 0
+LANE_ONLY = dict(tier1_bar=1e30, tier1_bar_small=1e30, tier1_bar_low=1e30, tier2_bar_small=1e30, tier2_bar_medium=1e30,
+                 tier2_bar=1e30, trace_small=0.0, trace_low=0.0, trace_medium=0.0, trace_large=0.0, promote_small=0.0,
+                 promote_low=0.0, promote_medium=0.0, promote_large=0.0, promote_big_scene=0.0, tail_coop_max=1)
+sched = {}
+if a.schedule == "lane-only":
+    sched = LANE_ONLY
+elif a.schedule:
+    kinds = dict(rtx.rtx_schedule._fields_)
+    for kv in a.schedule.split(","):
+        k, v = kv.split("=")
+        sched[k] = int(v) if kinds[k] is rtx.C.c_uint32 else float(v)
 ctxs = {}
 for p in paths:
     name = os.path.basename(p)[len("librtx_"):-3]
@@ -43,6 +61,8 @@ for p in paths:
     c = rtx.Context(0, lib=lib)
     c.upload_world(world)
     c.set_frame(frame)
+    if sched:
+        c.set_schedule(**sched)
     ctxs[name] = c
 ref = None
 times = {n: [] for n in ctxs}
