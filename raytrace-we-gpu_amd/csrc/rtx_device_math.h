@@ -88,6 +88,21 @@ __device__ __forceinline__ f3 hash3(float &seed) {
               (float)((n * 48271u) & 0x7fffffffu) / 2147483648.0f};
 }
 
+// A constant the compiler sees as a value made right here, in a VGPR. For a
+// literal that ends up as one half of a packed (v_pk_*_f32) operand: the
+// compiler builds such a register pair once, outside the enclosing loop, and a
+// pair is not rematerialised when registers run short but kept in scratch and
+// reloaded at every use. The value, and the operation it enters, are
+// unchanged. Not for sincos_rt's two addends below, although they are such a
+// pair (the one the lane-mode render still keeps in scratch, 2 VGPRs): made
+// at their use they left the C2 instance without any scratch and the whole
+// frame 0.2 ms faster, but an R = 4 row share's parts 0.8 ms slower in the
+// mean, above the parent's (RESULTS.md S15k).
+__device__ __forceinline__ float vgpr_const(float k) {
+    asm volatile("" : "+v"(k));
+    return k;
+}
+
 // ---- sin/cos -------------------------------------------------------------
 // q = rint(x * 2/pi); r = x - q*pi/2 (two-constant Cody-Waite, fmaf);
 // sin/cos of r by degree-7/8 minimax polynomials; quadrant swap.

@@ -100,6 +100,58 @@ template <typename T>
 __device__ __forceinline__ global_p<T> as_global(T *p) {
     return (global_p<T>)(uintptr_t)p;
 }
+// Bits of m below this lane (v_mbcnt_lo/hi): a lane's rank in a ballot with
+// no per-lane 64-bit mask. Such masks ((1ull << lane) - 1 and the like) are
+// loop-invariant, so the compiler held them across the persistent loop, in
+// scratch: every rank was a scratch reload and its vmcnt(0) wait.
+__device__ __forceinline__ uint32_t below(uint64_t m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+// This lane's index in its wave, counted where it is used (two v_mbcnt on an
+// opaque zero, as kernarg_here: never hoisted), not taken from a threadIdx.x
+// held, and spilled, for the kernel's life. For the sites of the small-scene
+// persistent loop that run once per refill or less.
+__device__ __forceinline__ uint32_t lane_here() {
+    uint32_t z = 0u;
+    asm volatile("" : "+v"(z));
+    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
+}
+// Wave-uniform words that a persistent loop carries but touches once per
+// iteration or less, one per lane of a single VGPR (v_readlane / v_writelane:
+// both ignore EXEC, the values are SGPR operands). A uniform value carried
+// round a loop with divergent branches is a VGPR each to the compiler, and
+// with the fewest uses per iteration it is the first to be kept in scratch:
+// the small-scene render's 64-bit heartbeat time was, once the loop-invariant
+// values had left scratch (RESULTS.md S15).
+// INVARIANT: to the compiler `v` is an ordinary per-lane value, so every copy,
+// split or spill of it that the compiler inserts obeys EXEC. The words are
+// kept only as long as each such copy runs with the lanes that hold words
+// (0..3 today) enabled. That holds in k_render's persistent loop because `v`
+// is read and written at the loop's top level and in refill only, where every
+// branch condition is wave-uniform at run time and no lane has left the loop
+// (the loop's exits are wave-uniform), so EXEC is full. The register is live
+// across the per-lane regions (`if (L.active)` ...) too: a copy or spill the
+// allocator placed inside one would lose the words of idle lanes. It places
+// none today (the C2, refine and adaptive instances spill one constant pair,
+// sincos_rt's, and move `v` at the top level only); a change that raises their register pressure
+// has to recheck that in the assembly (`make asm`). A lost word would show as
+// a wrong queue slot (the bit-exact frame tests) or, for the heartbeat, as
+// valve timing only.
+struct WaveWords {
+    uint32_t v;
+    template <uint32_t kWord>
+    __device__ __forceinline__ uint32_t get() const {
+        return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)kWord);
+    }
+    // (the data operand is an SGPR and the lane an immediate: no wait states
+    // are owed after the v_readfirstlane that made the SGPR)
+    template <uint32_t kWord>
+    __device__ __forceinline__ void set(uint32_t x) {
+        static_assert(kWord < 64u, "WaveWords: one word per lane");
+        const uint32_t xs = (uint32_t)__builtin_amdgcn_readfirstlane((int)x);
+        asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(xs), "n"(kWord));
+    }
+};
 __device__ __forceinline__ FrameVals frame_vals() {
     kparams_cp kp = kernarg_here();
     FrameVals F;
@@ -963,11 +1015,10 @@ __device__ __forceinline__ uint64_t grid_wave_mask(const KScene &S, f3 o, f3 d, 
         RTX_DIAG_WALK(0u, 1u);
         return ~0ull;
     }
+    // (threadIdx.x is live in the scan's LDS addresses whatever is done here:
+    // lane_here() had the same registers and scratch for 9 more VALU, S15)
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t act = __ballot(1);
-    auto below = [](uint64_t m) {  // bits of m below this lane
-        return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    };
     const uint32_t nact = (uint32_t)__popcll(act), slot = below(act);
     // the items before this lane's and the wave's total: n <= kGridMaxSteps < 64, one ballot per bit
     static_assert(kGridMaxSteps < 64u, "grid_wave_mask: item counts of 6 bits");
@@ -983,8 +1034,11 @@ __device__ __forceinline__ uint64_t grid_wave_mask(const KScene &S, f3 o, f3 d, 
     const uint32_t last_cell = G.nx * G.nz - 1u;
     // the wave's columns of row 0. (Held as LDS byte addresses in SGPRs, so
     // that no round reloads an address from scratch, the C2 frame measured
-    // 37.1 ms against 31.8 ms: RESULTS.md S8b.)
-    uint32_t *marks = list + (threadIdx.x & ~63u);
+    // 37.1 ms against 31.8 ms: RESULTS.md S8b. The wave's first thread through
+    // readfirstlane: left to the compiler the base became a VGPR kept in
+    // scratch once the lane masks had left it, S15.)
+    const uint32_t wave0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
+    uint32_t *marks = list + wave0;
     uint32_t *my_mark = marks + slot;
     auto from = [](uint32_t lane4, uint32_t v) {  // v of lane lane4 / 4
         return (uint32_t)__builtin_amdgcn_ds_bpermute((int)lane4, (int)v);
@@ -1001,10 +1055,14 @@ __device__ __forceinline__ uint64_t grid_wave_mask(const KScene &S, f3 o, f3 d, 
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
         const uint32_t v = __hip_atomic_load(my_mark, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
-        // the nearest mark at or before this slot (slots ascend with the lanes)
-        const uint64_t le = __ballot(v != 0u) & ((2ull << lane) - 1ull);
+        // the nearest mark at or before this slot (slots ascend with the lanes):
+        // the ballot shifted so that this lane's bit is the top one, and its
+        // leading zeros counted. (No mask of the lanes up to this one: that
+        // is a 64-bit constant per lane, which was kept in scratch and
+        // reloaded, with a vmcnt(0) wait, in every round.)
+        const uint64_t le = __ballot(v != 0u) << (63u - lane);
         const bool valid = base + slot < total;  // (then le != 0: item 0 of the round is marked)
-        const uint32_t at = le != 0ull ? 63u - (uint32_t)__clzll((long long)le) : lane;
+        const uint32_t at = le != 0ull ? lane - (uint32_t)__clzll((long long)le) : lane;
         const uint32_t own4 = ((from(4u * at, v) - 1u) & 63u) * 4u;
         const uint32_t opack = from(own4, pack);
         const float olo = __uint_as_float(from(own4, __float_as_uint(R.lo)));
@@ -1023,7 +1081,13 @@ __device__ __forceinline__ uint64_t grid_wave_mask(const KScene &S, f3 o, f3 d, 
     }
     RTX_DIAG_WALK(R.n, rounds);
     (void)rounds;
-    unsigned long long *w = reinterpret_cast<unsigned long long *>(spare + (threadIdx.x & ~63u));
+    // the result word's address through a VGPR the compiler cannot see as
+    // uniform: given a uniform address its atomic optimizer reduces the or
+    // over the wave itself, in a scalar loop over the active lanes, ~300 SALU
+    // per segment (the C2 frame measured 33.0 ms against 28.8, RESULTS.md S15)
+    uint32_t wave_v = wave0;
+    asm volatile("" : "+v"(wave_v));
+    unsigned long long *w = reinterpret_cast<unsigned long long *>(spare + wave_v);
     if (slot == 0u) __hip_atomic_store(w, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
     __hip_atomic_fetch_or(w, (unsigned long long)mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1883,7 +1947,10 @@ __device__ __forceinline__ int path_segment_m(const KParams &P, LaneT &L, int hi
         const bool cant = ratio * sq > 1.0f;
         // FXC's `||` does not short-circuit: hash1 always advances the seed.
         const float refl = reflectance(cosine, ratio);
-        const float h = (float)hn / 4294967296.0f;  // hash1 (:30-34)
+        // hash1 (:30-34): / 2^32, written as the exact product by 2^-32 it is
+        // compiled to, so that the factor can be made here (vgpr_const: packed
+        // with reflectance's r0 * r0 it was half of a pair kept in scratch)
+        const float h = (float)hn * vgpr_const(2.3283064365386963e-10f);
         dir = (cant || refl > h) ? reflect3(ud, nrm) : refract3(ud, nrm, ratio);
     } else {
         // Lambert and metal share random_in_unit_sphere and normalize: run
@@ -1959,7 +2026,12 @@ __device__ __forceinline__ bool promote(const PT &P, const Lane &L, uint32_t min
     if (slot >= P.prom_cap) return false;  // queue full: the lane keeps its pixel
     // whoever finishes a promoted pixel writes it to out[gid] directly: its
     // staging slot says so (w = 0; an output pixel's w is 1), k_unpermute skips it
-    if (P.out_slot && L.slot != ~0u) P.out_slot[L.slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    // (the four zeros made here, vgpr_const: as a constant they were a register
+    // quad set up before the persistent loop and kept in scratch across it)
+    if (P.out_slot && L.slot != ~0u) {
+        const float z = vgpr_const(0.0f);
+        P.out_slot[L.slot] = make_float4(z, z, z, z);
+    }
     uint32_t *e = P.prom_q + 8u * slot;
     __hip_atomic_store(e + 0, L.gid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(e + 1, L.sample, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2093,18 +2165,26 @@ __device__ __forceinline__ void start_pixel(const PT &P, const Frame &F, uint32_
     L.gid = gid;
     lane_pixel(P, gid, L.x, L.y);
     L.seg0 = L.segs;
-    const float4 st = P.state && !P.cost_out ? P.state[gid] : make_float4(0.f, 0.f, 0.f, 0.f);
     L.c0 = 0u;
-    if (P.state && !P.cost_out && !__builtin_isnan(st.w)) {  // after the pre-pass's cost_spp samples (identical state)
-        L.acc = mk3(st.x, st.y, st.z);
-        L.sample = P.cost_spp;
-        L.seed = st.w;
-        if constexpr (kRefine) {  // the cost map counts them whether or not the dynamic priority is on
-            L.c0 = P.cost_map[gid];  // the pre-pass's record (write_pixel<true, true>), = cost_in[gid]
-        } else if (P.cost_in) {
-            L.c0 = P.cost_in[gid];
+    // (the state is read and used inside one branch, with no default value for
+    // a launch without one: four zeros were held across the persistent loop,
+    // in scratch, for every refill to reload)
+    bool resumed = false;
+    if (P.state && !P.cost_out) {
+        const float4 st = P.state[gid];
+        if (!__builtin_isnan(st.w)) {  // after the pre-pass's cost_spp samples (identical state)
+            resumed = true;
+            L.acc = mk3(st.x, st.y, st.z);
+            L.sample = P.cost_spp;
+            L.seed = st.w;
+            if constexpr (kRefine) {  // the cost map counts them whether or not the dynamic priority is on
+                L.c0 = P.cost_map[gid];  // the pre-pass's record (write_pixel<true, true>), = cost_in[gid]
+            } else if (P.cost_in) {
+                L.c0 = P.cost_in[gid];
+            }
         }
-    } else {  // a fresh pixel, or one the pre-pass stopped (cost_cap)
+    }
+    if (!resumed) {  // a fresh pixel, or one the pre-pass stopped (cost_cap)
         L.acc = mk3(0.0f, 0.0f, 0.0f);
         L.sample = 0;
         L.seed = pixel_seed(P, L.x, L.y, 0);
@@ -2162,10 +2242,17 @@ __device__ __forceinline__ uint32_t dyn_level(const PT &P, const Lane &L, float 
                                              fmaxf((float)L.sample + (float)P.carry_spp, 1.0f);
         }
     }
-    return __ballot(rem > P.dyn_bar[2] * m) != 0ull   ? 3u
-           : __ballot(rem > P.dyn_bar[1] * m) != 0ull ? 2u
-           : __ballot(rem > P.dyn_bar[0] * m) != 0ull ? 1u
-                                                      : 0u;
+    // the three bars in one scalar load and one wait, ahead of the compares
+    // (read one by one, each compare had its own load and lgkmcnt(0) wait)
+    const float b0 = P.dyn_bar[0], b1 = P.dyn_bar[1], b2 = P.dyn_bar[2];
+    // (m, an SGPR across the loop, copied to a VGPR once here: a product of two
+    // SGPRs costs a v_mov each time, v_mul_f32 takes one scalar operand)
+    float mv = m;
+    asm volatile("" : "+v"(mv));
+    return __ballot(rem > b2 * mv) != 0ull   ? 3u
+           : __ballot(rem > b1 * mv) != 0ull ? 2u
+           : __ballot(rem > b0 * mv) != 0ull ? 1u
+                                             : 0u;
 }
 
 // atomicAdd on the queue head (kLate: through a late-read pointer, global all the same)
@@ -2183,9 +2270,11 @@ __device__ __forceinline__ uint32_t queue_take(uint32_t *q, uint32_t n) {
 // per refill (ballot + lane rank). Returns true once the queue is
 // exhausted (wave-uniform).
 // kLate: the queue, perm and state fields (and start_pixel's) are read from
-// the kernel arguments here, once a lane is idle (params_at).
-template <bool kRefine = false, bool kLate = false>
-__device__ __forceinline__ bool refill(const KParams &P0, const Frame &F, uint32_t lo, uint32_t hi, Lane &L) {
+// the kernel arguments here, once a lane is idle (params_at), and the wave's
+// private run [cb, ce) is kept in words 2 and 3 of W (WaveWords), not in L.
+template <bool kRefine = false, bool kLate = false, typename Words>
+__device__ __forceinline__ bool refill(const KParams &P0, const Frame &F, uint32_t lo, uint32_t hi, Lane &L,
+                                       Words &W) {
     const uint64_t idle = __ballot(!L.active);
     if (idle == 0ull) return false;
     const auto &P = params_at<kLate>(P0);
@@ -2197,18 +2286,31 @@ __device__ __forceinline__ bool refill(const KParams &P0, const Frame &F, uint32
         // rays) instead of one slot per refill from wherever the queue head
         // is. Slot by slot for the last eighth of the queue (no pixel waits
         // in a busy wave's run while other waves are idle).
-        const uint32_t lane = threadIdx.x & 63u;
-        const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-        const uint32_t avail = L.ce - L.cb;
+        const uint32_t rank = below(idle);
+        uint32_t cb, ce;
+        if constexpr (kLate) {
+            cb = W.template get<2>(), ce = W.template get<3>();
+        } else {
+            cb = L.cb, ce = L.ce;
+        }
+        auto keep = [&](uint32_t b, uint32_t e, bool both) {
+            if constexpr (kLate) {
+                W.template set<2>(b);
+                if (both) W.template set<3>(e);
+            } else {
+                L.cb = b, L.ce = e;
+            }
+        };
+        const uint32_t avail = ce - cb;
         uint32_t nb = 0, n = 0;
         if (cnt > avail) {
             n = cnt - avail;
-            if (L.cb < hi - (hi - lo) / 8u) n = max(n, P.chunk);
-            if (lane == 0u) nb = queue_take<kLate>(P.queue, n);
+            if (cb < hi - (hi - lo) / 8u) n = max(n, P.chunk);
+            if (lane_here() == 0u) nb = queue_take<kLate>(P.queue, n);
             nb = lo + (uint32_t)__shfl((int)nb, 0, 64);
         }
         if (!L.active) {
-            const uint32_t g = rank < avail ? L.cb + rank : nb + (rank - avail);
+            const uint32_t g = rank < avail ? cb + rank : nb + (rank - avail);
             if (g < hi) {
                 start_pixel<kRefine>(P, F, P.perm ? P.perm[g] : g, L);
                 L.slot = g;
@@ -2216,20 +2318,18 @@ __device__ __forceinline__ bool refill(const KParams &P0, const Frame &F, uint32
             }
         }
         if (cnt > avail) {
-            L.cb = nb + (cnt - avail);
-            L.ce = min(nb + n, hi);
-            return L.cb >= hi;
+            keep(nb + (cnt - avail), min(nb + n, hi), true);
+            return nb + (cnt - avail) >= hi;
         }
-        L.cb += cnt;
+        keep(cb + cnt, ce, false);
         return false;
     }
     const int leader = __ffsll((long long)idle) - 1;
-    const uint32_t lane = threadIdx.x & 63u;
     uint32_t base = 0;
-    if ((int)lane == leader) base = queue_take<kLate>(P.queue, cnt);
+    if ((int)lane_here() == leader) base = queue_take<kLate>(P.queue, cnt);
     base = lo + __shfl(base, leader, 64);
     if (!L.active) {
-        const uint32_t g = base + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
+        const uint32_t g = base + below(idle);
         if (g < hi) {
             start_pixel<kRefine>(P, F, P.perm ? P.perm[g] : g, L);
             L.slot = g;
@@ -2257,16 +2357,15 @@ struct HeavyState {
 template <bool kRefine = false, typename PT>
 __device__ __forceinline__ bool take_from(const KParams &P0, const PT &P, const Frame &F, uint32_t *ctr, uint32_t lo, uint32_t hi,
                                           uint32_t room, uint64_t act, Lane &L, bool &done) {
-    const uint32_t lane = threadIdx.x & 63u;
     uint32_t h = 0;
-    if (lane == 0u) h = atomicAdd(ctr, room);
+    if (lane_here() == 0u) h = atomicAdd(ctr, room);
     h = lo + __shfl(h, 0, 64);
     if (h >= hi) {
         done = true;
         return false;
     }
     const uint32_t take = min(room, hi - h);
-    const uint32_t rk = (uint32_t)__popcll(~act & ((1ull << lane) - 1ull));
+    const uint32_t rk = below(~act);
     if (!L.active && rk < take) {
         start_pixel<kRefine>(P, F, P.perm[h + rk], L);
         L.slot = h + rk;
@@ -2535,6 +2634,17 @@ __device__ __forceinline__ void beat(const KParams &P, unsigned long long &last)
             __hip_atomic_store(&params_at<kLate>(P).prom[4], (uint32_t)(now >> kBeatShift), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
+// The heartbeat with the wave's previous beat in words 0 and 1 of W.
+template <bool kLate = false>
+__device__ __forceinline__ void beat(const KParams &P, WaveWords &W) {
+    unsigned long long last = ((unsigned long long)W.get<1>() << 32) | W.get<0>();
+    const unsigned long long was = last;
+    beat<kLate>(P, last);
+    if (last != was) {
+        W.set<0>((uint32_t)last);
+        W.set<1>((uint32_t)(last >> 32));
+    }
+}
 template <bool kRefine = false, bool kLate = false>
 __device__ __forceinline__ bool take_promoted(const KParams &P0, const Frame &F, uint32_t npix, uint32_t target,
                                               bool helper, Lane &W) {
@@ -2729,11 +2839,17 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
     H.tier = 0;
     const uint32_t kh = H.kh;
     // the mean pixel's segments (dynamic priority's unit)
-    const float dyn_m = (kPersist && P.cost_in && P.heavy) ? __uint_as_float(P.heavy[5]) : 0.0f;
+    // (wave-uniform: in an SGPR. Left to the vector load that reads it, it was
+    // a VGPR, kept in scratch and reloaded before each of dyn_level's compares.)
+    const float dyn_m = (kPersist && P.cost_in && P.heavy)
+                            ? __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)P.heavy[5]))
+                            : 0.0f;
     // promotion's exit count: the pixels this kernel owns (tier 1 is k_trace's when it runs beside it)
     const uint32_t owned = qlen - (P.trace_ext != 0u ? H.k1 : 0u);
     uint32_t written = 0;  // pixels this wave wrote since it last reported
-    unsigned long long last_beat = 0;  // the wave's last heartbeat (beat)
+    // the wave's last heartbeat (beat); the small-scene instances' cold words
+    // (WaveWords): 0, 1 the heartbeat, 2, 3 refill's private run
+    std::conditional_t<kLate, WaveWords, unsigned long long> cold{};
     Diag D;
     D.begin();
     for (;;) {
@@ -2741,7 +2857,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
             take_heavy<kRefine, kLate>(P, F, H, L);
         if (H.tier != 0u && __ballot(L.active) == 0ull) H.tier = 0;  // drained, no heavy slot left
         const bool heavy = H.tier != 0u;
-        if (!heavy && !exhausted) exhausted = refill<kRefine, kLate>(P, F, kh, qlen, L);
+        if (!heavy && !exhausted) exhausted = refill<kRefine, kLate>(P, F, kh, qlen, L, cold);
         if (kPersist && kCost && P.pre_done && exhausted && pre_stop(P, npix, L)) continue;
         const uint64_t act = __ballot(L.active);
         D.section(0);
@@ -2770,7 +2886,7 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
         // beats, not only those that have seen the queue exhausted: a wave
         // whose lanes are all busy never refills and never learns it (R7e: a
         // 2 ms stress valve fired while only such waves were tracing)
-        if (prom_on) beat<kLate>(P, last_beat);
+        if (prom_on) beat<kLate>(P, cold);
         D.iteration(act);
         // (two sites: the tail's size here, read once the queue is exhausted, and
         // a heavy wave's priority inside. One pointer for both, formed before

@@ -84,7 +84,17 @@ inline float prefilter_R(float cx, float cy, float cz, float r2) {
 #if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ float pf_rsq(float x) { return __builtin_amdgcn_rsqf(x); }
 __device__ __forceinline__ float pf_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
+// kPreMarginO as a value made at its use (an empty asm on a VGPR): thr's fma
+// is packed with nov's last one (v_pk_fma_f32), and as a literal the margin
+// was one half of a register pair that the persistent render kept in scratch
+// across its loop, reloaded and stored back by every segment's set-up.
+__device__ __forceinline__ float pf_margin_o() {
+    float k = kPreMarginO;
+    asm volatile("" : "+v"(k));
+    return k;
+}
 #else
+inline float pf_margin_o() { return kPreMarginO; }
 inline int pf_host_ulp[3] = {0, 0, 0};
 inline float pf_nudge(float v, int k) {
     return k > 0 ? nextafterf(v, INFINITY) : k < 0 ? nextafterf(v, -INFINITY) : v;
@@ -126,7 +136,7 @@ RTX_HD LineTest line_test_setup(float ox, float oy, float oz, float dx, float dy
     T.uz = (dx * dz) * w;
     T.nou = -fmaf(oz, T.uz, fmaf(oy, T.uy, ox * T.ux));
     T.nov = -fmaf(oz, T.vz, oy * T.vy);
-    T.thr = -fmaf(o2, kPreMarginO, kPreFloor);
+    T.thr = -fmaf(o2, pf_margin_o(), kPreFloor);
     return T;
 }
 

@@ -7,8 +7,10 @@ Makefile's HIPFLAGS) plus -gline-tables-only, and attributes every instruction
 of the named kernel to the function whose body its `.loc` line lies in (the
 innermost inlined function: a line table has no call stack). Per function:
 VALU, moves (v_mov*, v_readlane, v_writelane), transcendentals, v_div_scale,
-SALU, SMEM and scratch loads/stores. Static counts: what executes per
-iteration is for the counters to say.
+SALU, SMEM and scratch loads/stores; of those, ld@1 / st@1 lie in a loop of
+depth 1 (a persistent kernel's main loop) and ld@2+ / st@2+ in the loops
+inside it, by the assembler's own "Loop Header: Depth=" block comments.
+Static counts: what executes per iteration is for the counters to say.
 
     python tools/asm_by_source.py [--kernel SUBSTR] [--all] [--check make-asm.s] [--keep out.s | --asm in.s] [-DRTX_...]
 
@@ -145,13 +147,22 @@ def owner(fi, ln):
 start = next(i for i, l in enumerate(lines)
              if l.startswith("_Z") and a.kernel in l and l.split(";")[0].rstrip().endswith(":"))
 end = next(i for i in range(start, len(lines)) if "-- End function" in lines[i] or ".Lfunc_end" in lines[i])
-COLS = ["instrs", "valu", "moves", "trans", "div_scale", "salu", "smem", "scratch_ld", "scratch_st"]
-rows, cur = {}, "?"
+COLS = ["instrs", "valu", "moves", "trans", "div_scale", "salu", "smem", "scratch_ld", "scratch_st",
+        "ld@1", "ld@2+", "st@1", "st@2+"]
+rows, cur, depth = {}, "?", 0
 for l in lines[start + 1:end]:
     m = re.match(r"\s*\.loc\s+(\d+)\s+(\d+)", l)
     if m:
         cur = owner(int(m.group(1)), int(m.group(2)))
         continue
+    # the loop depth of the basic block, from the assembler's own comments: a
+    # block begins at a label (or "; %bb.N:"), which says "in Loop: Header=...
+    # Depth=D" or is followed by "=> This [Inner] Loop Header: Depth=D"
+    if re.match(r"\s*(\.LBB\w+:|; %bb\.\d+:)", l):
+        depth = 0
+    m = re.search(r"(?:in Loop: Header=\S+|=>\s*This (?:Inner )?Loop Header:) Depth=(\d+)", l)
+    if m:
+        depth = int(m.group(1))
     t = instruction(l)
     if t is None:
         continue
@@ -169,8 +180,12 @@ for l in lines[start + 1:end]:
         r["salu"] += not op.startswith(NOT_SALU)
     elif op.startswith("scratch_load_"):
         r["scratch_ld"] += 1
+        r["ld@1"] += depth == 1
+        r["ld@2+"] += depth >= 2
     elif op.startswith("scratch_st"):
         r["scratch_st"] += 1
+        r["st@1"] += depth == 1
+        r["st@2+"] += depth >= 2
 
 table, used = [], set()
 for g in GROUPS:
