@@ -40,6 +40,11 @@ extern "C" {
 
 #define RTX_VERSION 145 /* 1.4.5 */
 /* ABI notes.
+ *  1.4.5 (later builds, no version bump): rtx_trace_paths (rtx_path_query,
+ *         rtx_path_result, RTX_PATHS_*) and rtx_paths_last_order (what rays of
+ *         the caller's choosing see: path-traced sample sums along the RNG
+ *         chain, on device buffers); purely additive again: probe for the
+ *         symbol (dlsym "rtx_trace_paths").
  *  1.4.5 (later builds, no version bump): rtx_path_seed (the chain seed of a
  *         pixel, on the host; groundwork for path queries along rays of the
  *         caller's choosing); purely additive again: probe for the symbol
@@ -790,6 +795,49 @@ RTX_API int rtx_cast_last_order(rtx_ctx *ctx);   /* GIVEN or COHERENT: what the 
  * where fl(L - o) == d, zero horizontal and vertical, any img_w, img_h != 1 —
  * the zero-film twin of a path query. */
 RTX_API float rtx_path_seed(uint32_t x, uint32_t y, uint32_t frame_index);
+/* ---- what a ray sees: path queries along rays of the caller's choosing ---------
+ * (later builds, no version bump: probe with dlsym "rtx_trace_paths").
+ * For each of n queries (o, d, seed): `samples` samples of the reference's
+ * ray_color along the ray — bounces, materials, sky — with the random numbers
+ * of the RNG chain that starts at `seed`, to the uploaded world's depth.
+ * d_queries (n rtx_path_query), d_results (n rtx_path_result) and d_segments
+ * (n uint32, or NULL) are device pointers; overlapping buffers are the
+ * caller's business. Asynchronous on the context stream. Reads the world and
+ * needs no frame; touches no stats, framebuffer, chain state or cost map. With
+ * a group, call it on rtx_group_ctx(g, 0), as rtx_cast_rays.
+ * The contract: query i with ray (o, d) and seed = rtx_path_seed(x, y, f)
+ * gives, bit for bit (NaN sums included), pixel (x, y) of rtx_render_sum in
+ * the zero-film twin frame of (o, d) (rtx_path_seed above) with frame_index f,
+ * world.spp = samples, and RTX_FRAME_LAMBERT_GUARD set iff
+ * RTX_PATHS_LAMBERT_GUARD is.
+ *   result.sum   the linear sum of the samples' colours (divide by the number
+ *                of samples taken for the mean)
+ *   result.seed  the chain's seed after the last sample: with sum, the pixel's
+ *                chain state as rtx_refine keeps it (rtx_refine_export's w)
+ *   d_segments[i]  the hit_world calls this call spent on query i
+ * `tag` is the caller's and is ignored.
+ * RTX_PATHS_CONTINUE: query i starts from d_results[i] (sum and seed) instead
+ * of (0, query.seed), whose seed is then not read: `samples` = s1 followed by
+ * a continuing call with s2 equals one call with s1 + s2, bit for bit;
+ * d_segments holds the continuing call's own segments.
+ * `order` (RTX_CAST_ORDER_*) is a schedule and nothing else, as in
+ * rtx_cast_rays, whose COHERENT passes and scratch it uses; only a query's
+ * first segment follows the batch's order, so AUTO is GIVEN.
+ * rtx_paths_last_order: what the last call ran; GIVEN before any call.
+ * One kernel lane traces one query from its first sample to its last: a
+ * wave takes as long as its longest query, so give neighbouring queries
+ * similar work where there is a choice.
+ * RTX_ERR_INVALID, before any HIP call and before the context is looked at: a
+ * null ctx; n > 0 with d_queries or d_results NULL; samples == 0; unknown flag
+ * bits; an unknown order. RTX_ERR_STATE: no world. RTX_ERR_INVALID once the
+ * world is known: its depth is 0, or samples * depth >= 2^32. n == 0 returns
+ * RTX_OK and launches nothing. */
+typedef struct rtx_path_query  { float o[3]; float seed; float d[3]; uint32_t tag; } rtx_path_query;   /* 32 B */
+typedef struct rtx_path_result { float sum[3]; float seed; } rtx_path_result;                          /* 16 B */
+enum { RTX_PATHS_LAMBERT_GUARD = 1, RTX_PATHS_CONTINUE = 2 };
+RTX_API int rtx_trace_paths(rtx_ctx *ctx, const void *d_queries, uint32_t n, uint32_t samples,
+                            uint32_t flags, uint32_t order, void *d_results, void *d_segments);
+RTX_API int rtx_paths_last_order(rtx_ctx *ctx);  /* GIVEN or COHERENT: what the last call ran */
 /* Device pointer of the chain state (width*height float4; a part state: its
  * rows * width), NULL if none. */
 RTX_API void *rtx_refine_state(rtx_ctx *ctx);

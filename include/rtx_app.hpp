@@ -160,6 +160,19 @@ public:
               float t_min = 0.001f);
     // RTX_CAST_ORDER_GIVEN or _COHERENT: what the last Cast ran (rtx_cast_last_order).
     int CastLastOrder() const;
+    // What rays of the caller's choosing see (rtx_trace_paths): `samples`
+    // path-traced samples per query along the RNG chain from its seed, to the
+    // world's depth; one record per query (the linear sample sum and the seed
+    // after the last sample), through device buffers of the call's own;
+    // synchronous. flags: RTX_PATHS_LAMBERT_GUARD, RTX_PATHS_CONTINUE — then
+    // *results holds, on entry, the records to continue from, one per query.
+    // segments (may be NULL): the hit_world calls this call spent per query.
+    // Needs a world and no frame. With a group: member 0.
+    bool TracePaths(const std::vector<rtx_path_query> &queries, uint32_t samples,
+                    std::vector<rtx_path_result> *results, uint32_t flags = 0, int order = RTX_CAST_ORDER_AUTO,
+                    std::vector<uint32_t> *segments = nullptr);
+    // RTX_CAST_ORDER_GIVEN or _COHERENT: what the last TracePaths ran (rtx_paths_last_order).
+    int PathsLastOrder() const;
     // Click to focus: picks the pixel, takes the hit's plane depth
     // dot(p - cam_pos, normalize(cam_look_at - cam_pos)) as the focus distance,
     // rebuilds the frame through rtx_camera_look_at with it and sets the thin

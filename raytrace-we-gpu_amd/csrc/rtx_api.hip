@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -18,6 +19,7 @@
 #include "../../include/rtx.h"
 #include "rtx_internal.h"
 #include "rtx_layout.h"
+#include "rtx_paths.h"
 #include "rtx_prefilter.h"
 
 namespace {
@@ -142,6 +144,7 @@ struct rtx_ctx {
     uint32_t *d_cast = nullptr;
     size_t cast_rays = 0;
     int cast_last = RTX_CAST_ORDER_GIVEN;
+    int paths_last = RTX_CAST_ORDER_GIVEN;  // rtx_trace_paths: the order its last call ran
     // measurement
     unsigned long long *d_counters = nullptr;
     unsigned long long *d_wave_times = nullptr;  // diagnostic (rtx_debug_wave_times)
@@ -1990,6 +1993,68 @@ int rtx_cast_rays(rtx_ctx *c, const void *d_rays, uint32_t n, float t_min, uint3
 int rtx_cast_last_order(rtx_ctx *c) {
     if (!c) return fail(RTX_ERR_INVALID, "rtx_cast_last_order: null ctx");
     return c->cast_last;
+}
+
+// ---- path queries along caller-chosen rays (rtx_paths.h) ----------------------
+static_assert(sizeof(rtx_path_query) == rtx::kPathRayBytes && sizeof(rtx_path_result) == rtx::kPathResultBytes,
+              "rtx_trace_paths: two float4 per query, one per result");
+static_assert(offsetof(rtx_path_query, o) == offsetof(rtx_ray, o) && offsetof(rtx_path_query, d) == offsetof(rtx_ray, d),
+              "the COHERENT passes read a query's o and d where a ray's are");
+static_assert(RTX_PATHS_LAMBERT_GUARD == rtx::kPathsLambertGuard && RTX_PATHS_CONTINUE == rtx::kPathsContinue &&
+                  RTX_CAST_ORDER_COHERENT == rtx::kPathsOrderMax && rtx::kFrameLambertGuard == 1u,
+              "rtx_paths.h restates these");
+
+int rtx_trace_paths(rtx_ctx *c, const void *d_queries, uint32_t n, uint32_t samples, uint32_t flags, uint32_t order,
+                    void *d_results, void *d_segments) {
+    // the argument rules first (rtx_paths.h): none of them looks at the context
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_trace_paths: null ctx");
+    switch (rtx::paths_args(d_queries != nullptr, d_results != nullptr, n, samples, flags, order)) {
+    case rtx::kPathsArgQueries: return fail(RTX_ERR_INVALID, "rtx_trace_paths: d_queries is NULL");
+    case rtx::kPathsArgResults: return fail(RTX_ERR_INVALID, "rtx_trace_paths: d_results is NULL");
+    case rtx::kPathsArgSamples: return fail(RTX_ERR_INVALID, "rtx_trace_paths: samples is 0");
+    case rtx::kPathsArgFlags: return fail(RTX_ERR_INVALID, "rtx_trace_paths: unknown flags");
+    case rtx::kPathsArgOrder: return fail(RTX_ERR_INVALID, "rtx_trace_paths: unknown order");
+    case rtx::kPathsArgOk: break;
+    }
+    if (!c->have_world) return fail(RTX_ERR_STATE, "rtx_trace_paths: no world uploaded");
+    switch (rtx::paths_world(samples, c->depth)) {
+    case rtx::kPathsWorldDepth0: return fail(RTX_ERR_INVALID, "rtx_trace_paths: the world's depth is 0");
+    case rtx::kPathsWorldCount: return fail(RTX_ERR_INVALID, "rtx_trace_paths: samples * depth does not fit 32 bits");
+    case rtx::kPathsWorldOk: break;
+    }
+    if (n == 0) return RTX_OK;
+    rtx::KPaths p;
+    p.scene = scene_of(c);
+    p.depth = c->depth;
+    p.flags = rtx::paths_frame_flags(flags);
+    p.samples = samples;
+    p.n = n;
+    p.mode = flags & rtx::kPathsContinue;
+    // AUTO is GIVEN: only a query's first segment follows the batch's order
+    // (RESULTS.md: where COHERENT was measured against GIVEN)
+    const bool sort = order == RTX_CAST_ORDER_COHERENT;
+    int rc = set_device(c);
+    if (rc) return rc;
+    const float4 *queries = static_cast<const float4 *>(d_queries);
+    const uint32_t *perm = nullptr;
+    if (sort) {  // rtx_cast_rays' passes and scratch, unchanged: a query holds o and d where a ray does
+        rc = ensure_cast(c, n);
+        if (rc) return rc;
+        const rtx::KCastScratch k{c->d_cast, c->d_cast + rtx::kCastBuckets, c->d_cast + rtx::kCastBuckets + c->cast_rays};
+        const hipError_t e = rtx::launch_cast_order(queries, n, c->cast_box, k, c->stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_cast_order");
+        perm = k.perm;
+    }
+    const hipError_t e = rtx::launch_paths(p, queries, perm, static_cast<float4 *>(d_results),
+                                           static_cast<uint32_t *>(d_segments), c->stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_paths");
+    c->paths_last = sort ? RTX_CAST_ORDER_COHERENT : RTX_CAST_ORDER_GIVEN;
+    return RTX_OK;
+}
+
+int rtx_paths_last_order(rtx_ctx *c) {
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_paths_last_order: null ctx");
+    return c->paths_last;
 }
 
 int rtx_debug_pixel_cost(rtx_ctx *c, uint32_t spp, uint32_t *host_cost) {

@@ -15,6 +15,16 @@
 //           [--refine-adaptive S,THRESHOLD[,MAX] --steps K] [--dump-counts FILE]
 //           [--aov PREFIX] [--pick X,Y] [--focus-at X,Y] [--refine-ids S,ID[,ID...] --grow G --steps K]
 //           [--cast RAYS.bin --hits OUT.bin [--cast-order auto|given|coherent] [--t-min T]]
+//           [--paths QUERIES.bin --samples S [--continue] --results OUT.bin [--segments SEG.bin]]
+// --paths QUERIES.bin traces the file's path queries in the scene
+// (rtx_trace_paths) instead of rendering: QUERIES.bin is raw little-endian
+// rtx_path_query records (32 bytes: o, seed, d, tag), OUT.bin receives one
+// rtx_path_result (16 bytes: the linear sum of --samples S samples, the chain's
+// seed after them) per query in the same order, SEG.bin one uint32 per query
+// (the hit_world calls spent). --continue reads OUT.bin first and continues
+// every query from its record. The depth is --depth's, the schedule
+// --cast-order's, --lambert-guard sets RTX_PATHS_LAMBERT_GUARD. The JSON line is
+// {"paths": {"queries", "samples", "segments", "order", "continued", "ms"}}.
 // --cast RAYS.bin casts the file's rays into the scene (rtx_cast_rays) instead
 // of rendering: RAYS.bin is raw little-endian rtx_ray records (32 bytes: o,
 // t_max, d, tag), OUT.bin receives one rtx_ray_hit record (32 bytes) per ray
@@ -109,7 +119,8 @@ static void usage() {
                  "               [--refine-adaptive S,THRESHOLD[,MAX] --steps K] [--dump-counts FILE]\n"
                  "               [--aov PREFIX] [--pick X,Y] [--focus-at X,Y]\n"
                  "               [--refine-ids S,ID[,ID...] --grow G --steps K]\n"
-                 "               [--cast RAYS.bin --hits OUT.bin [--cast-order auto|given|coherent] [--t-min T]]\n");
+                 "               [--cast RAYS.bin --hits OUT.bin [--cast-order auto|given|coherent] [--t-min T]]\n"
+                 "               [--paths QUERIES.bin --samples S [--continue] --results OUT.bin [--segments SEG.bin]]\n");
 }
 
 int main(int argc, char **argv) {
@@ -143,6 +154,9 @@ int main(int argc, char **argv) {
     std::string cast_in, cast_out;             // --cast RAYS.bin, --hits OUT.bin
     int cast_order = RTX_CAST_ORDER_AUTO;      // --cast-order
     float cast_t_min = 0.001f;                 // --t-min
+    std::string paths_in, paths_out, paths_seg;  // --paths QUERIES.bin, --results OUT.bin, --segments SEG.bin
+    long paths_samples = 0;                    // --samples
+    bool paths_continue = false;               // --continue
     std::vector<int> devices;  // non-empty: a group
     int gather = RTX_GATHER_AUTO;
     bool group_opts = false;   // --gather / --tile-rows given
@@ -231,6 +245,11 @@ int main(int argc, char **argv) {
         else if (a == "--dump-counts") dump_counts = next();
         else if (a == "--cast") cast_in = next();
         else if (a == "--hits") cast_out = next();
+        else if (a == "--paths") paths_in = next();
+        else if (a == "--results") paths_out = next();
+        else if (a == "--segments") paths_seg = next();
+        else if (a == "--samples") paths_samples = std::atol(next());
+        else if (a == "--continue") paths_continue = true;
         else if (a == "--t-min") cast_t_min = (float)std::atof(next());
         else if (a == "--cast-order") {
             const std::string m = next();
@@ -349,6 +368,18 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "rtx_cli: --cast RAYS.bin and --hits OUT.bin go together\n");
         return 2;
     }
+    if (paths_in.empty() != paths_out.empty() || (!paths_in.empty() && !cast_in.empty())) {
+        std::fprintf(stderr, "rtx_cli: --paths QUERIES.bin and --results OUT.bin go together, without --cast\n");
+        return 2;
+    }
+    if (!paths_in.empty() && (paths_samples < 1 || paths_samples > 0xffffffffl)) {
+        std::fprintf(stderr, "rtx_cli: --paths needs --samples S >= 1\n");
+        return 2;
+    }
+    if (paths_in.empty() && (paths_continue || !paths_seg.empty() || paths_samples != 0)) {
+        std::fprintf(stderr, "rtx_cli: --samples, --continue and --segments go with --paths\n");
+        return 2;
+    }
     const bool adaptive = ad_samples != 0u;
     if (adaptive && (!refine.empty() || !load_state.empty() || ad_steps < 1)) {
         std::fprintf(stderr, "rtx_cli: --refine-adaptive takes --steps K >= 1, without --refine and --load-state\n");
@@ -437,6 +468,73 @@ int main(int argc, char **argv) {
         std::printf("{\"cast\": {\"rays\": %zu, \"hits\": %zu, \"order\": \"%s\", \"t_min\": %.9g, \"ms\": %.3f}}\n",
                     rays.size(), nhit, app.CastLastOrder() == RTX_CAST_ORDER_COHERENT ? "coherent" : "given",
                     (double)cast_t_min, ms);
+        return 0;
+    }
+    if (!paths_in.empty()) {  // trace the file's path queries instead of rendering
+        // a file of whole records; false: unreadable, or not a multiple of the record size
+        auto slurp = [](const std::string &path, size_t rec, std::vector<unsigned char> &out) {
+            std::FILE *f = std::fopen(path.c_str(), "rb");
+            bool ok = f != nullptr;
+            if (ok) {
+                ok = std::fseek(f, 0, SEEK_END) == 0;
+                const long bytes = ok ? std::ftell(f) : -1;
+                ok = ok && bytes >= 0 && bytes % (long)rec == 0 && std::fseek(f, 0, SEEK_SET) == 0;
+                if (ok) {
+                    out.resize((size_t)bytes);
+                    ok = std::fread(out.data(), 1, out.size(), f) == out.size();
+                }
+                std::fclose(f);
+            }
+            return ok;
+        };
+        auto spill = [](const std::string &path, const void *data, size_t bytes) {
+            std::FILE *f = std::fopen(path.c_str(), "wb");
+            bool ok = f != nullptr && std::fwrite(data, 1, bytes, f) == bytes;
+            if (f) ok = std::fclose(f) == 0 && ok;
+            return ok;
+        };
+        std::vector<unsigned char> raw;
+        if (!slurp(paths_in, sizeof(rtx_path_query), raw)) {
+            std::fprintf(stderr, "rtx_cli: --paths: cannot read %s as 32-byte query records\n", paths_in.c_str());
+            return 1;
+        }
+        std::vector<rtx_path_query> queries(raw.size() / sizeof(rtx_path_query));
+        if (!raw.empty()) std::memcpy(queries.data(), raw.data(), raw.size());
+        std::vector<rtx_path_result> results;
+        if (paths_continue) {
+            if (!slurp(paths_out, sizeof(rtx_path_result), raw) ||
+                raw.size() != queries.size() * sizeof(rtx_path_result)) {
+                std::fprintf(stderr, "rtx_cli: --continue: cannot read %s as one 16-byte record per query\n",
+                             paths_out.c_str());
+                return 1;
+            }
+            results.resize(queries.size());
+            if (!raw.empty()) std::memcpy(results.data(), raw.data(), raw.size());
+        }
+        std::vector<uint32_t> segs;
+        const uint32_t pflags = (paths_continue ? (uint32_t)RTX_PATHS_CONTINUE : 0u) |
+                                (cfg.lambert_guard ? (uint32_t)RTX_PATHS_LAMBERT_GUARD : 0u);
+        const auto t0 = std::chrono::steady_clock::now();
+        if (!app.TracePaths(queries, (uint32_t)paths_samples, &results, pflags, cast_order, &segs)) {
+            std::fprintf(stderr, "rtx_cli: --paths failed: %s\n", app.last_error().c_str());
+            return 1;
+        }
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (!spill(paths_out, results.data(), results.size() * sizeof(rtx_path_result))) {
+            std::fprintf(stderr, "rtx_cli: --results: cannot write %s\n", paths_out.c_str());
+            return 1;
+        }
+        if (!paths_seg.empty() && !spill(paths_seg, segs.data(), segs.size() * sizeof(uint32_t))) {
+            std::fprintf(stderr, "rtx_cli: --segments: cannot write %s\n", paths_seg.c_str());
+            return 1;
+        }
+        unsigned long long total = 0;
+        for (const uint32_t v : segs) total += v;
+        std::printf("{\"paths\": {\"queries\": %zu, \"samples\": %ld, \"segments\": %llu, \"order\": \"%s\", "
+                    "\"continued\": %s, \"ms\": %.3f}}\n",
+                    queries.size(), paths_samples, total,
+                    app.PathsLastOrder() == RTX_CAST_ORDER_COHERENT ? "coherent" : "given",
+                    paths_continue ? "true" : "false", ms);
         return 0;
     }
     std::string extra;  // further fields of the JSON line: "focus_dist", "pick"

@@ -343,6 +343,21 @@ hipError_t launch_cast_order(const float4 *rays, uint32_t n, const CastBox &box,
 // k_cast: lane g casts ray perm[g] (perm NULL: ray g) over (t_min, its own t_max).
 hipError_t launch_cast(const KScene &s, const float4 *rays, uint32_t n, float t_min, const uint32_t *perm,
                        float4 *hits, uint8_t *occluded, hipStream_t stream);
+// Path queries along rays of the caller's choosing (rtx_paths.h; include/rtx.h
+// rtx_trace_paths). The parameter block of k_paths, its first kernel argument:
+// what path_segment reads of a launch (scene, depth, flags: the frame flags,
+// kFrameLambertGuard) and the batch. mode: kPathsContinue or 0.
+struct KPaths {
+    KScene scene;
+    uint32_t depth, flags, samples, n, mode;
+};
+// k_paths: lane g traces query perm[g] (perm NULL: query g), p.samples samples
+// along the RNG chain from the query's seed — or (kPathsContinue) from
+// results[i], sum and seed — and writes results[i] = (sum.xyz, seed) and, if
+// segments is not NULL, segments[i] = the hit_world calls it spent. p.n > 0,
+// p.samples > 0, p.depth > 0.
+hipError_t launch_paths(const KPaths &p, const float4 *queries, const uint32_t *perm, float4 *results,
+                        uint32_t *segments, hipStream_t stream);
 // k_feature_listed + k_feature_mask (rtx_mask_from_ids): ids is host memory
 // (1 <= n <= kFeatureIdsMax), listed a width * height byte scratch, *n_set
 // (device, zeroed here first) the number of set pixels.

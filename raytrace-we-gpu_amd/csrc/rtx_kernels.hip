@@ -33,6 +33,7 @@
 #include "rtx_device_math.h"
 #include "rtx_diag.h"
 #include "rtx_internal.h"
+#include "rtx_paths.h"
 #include "rtx_prefilter.h"
 
 // The device code is written for gfx950 only: its wave64 DPP/permlane
@@ -1892,8 +1893,10 @@ __device__ __forceinline__ HitMat hit_mat(const KScene &S, int hit) {
 // path_segment with the hit's record inputs given (hit >= 0; M unused on a
 // miss) and, with kSpec, the scatter's seed-determined part precomputed.
 // kInvA false: a scattered lane's inv_a is left to the caller (set_dir).
-template <bool kSpec, bool kInvA = true, typename LaneT>
-__device__ __forceinline__ int path_segment_m(const KParams &P, LaneT &L, int hit, float t, const HitMat &M,
+// PT: the launch's parameter block, of which only scene (path_segment), depth
+// and flags are read here (KParams; KPaths for k_paths).
+template <bool kSpec, bool kInvA = true, typename PT, typename LaneT>
+__device__ __forceinline__ int path_segment_m(const PT &P, LaneT &L, int hit, float t, const HitMat &M,
                                               const ScatterSpec &sp, f3 &sky_col) {
     int mt = 3;
     f3 p = L.o, nrm = L.d;
@@ -1981,8 +1984,8 @@ __device__ __forceinline__ int path_segment_m(const KParams &P, LaneT &L, int hi
 // (The three scene pointers hit_mat reads stay held in SGPRs: read late like
 // the sample-end fields, once per segment, they cost more VALU than their
 // restores did, RESULTS.md S14.)
-template <bool kInvA = true, typename LaneT>
-__device__ __forceinline__ int path_segment(const KParams &P, LaneT &L, int hit, float t, f3 &sky_col) {
+template <bool kInvA = true, typename PT, typename LaneT>
+__device__ __forceinline__ int path_segment(const PT &P, LaneT &L, int hit, float t, f3 &sky_col) {
     HitMat M;
     if (hit >= 0) M = hit_mat(P.scene, hit);
     return path_segment_m<false, kInvA>(P, L, hit, t, M, ScatterSpec{}, sky_col);
@@ -4218,6 +4221,90 @@ __global__ void __launch_bounds__(kRB) k_cast(const KScene S, const float4 *__re
     if (occluded) occluded[i] = hit ? 1u : 0u;
 }
 
+// ---- path queries along caller-chosen rays (rtx_trace_paths; rtx_paths.h) -----
+// One lane per query on k_cast's exact grid, and in each lane the whole of the
+// query: P.samples samples along the RNG chain, one path segment per loop
+// iteration — k_cast's choice of scan under `if (L.active)`, then
+// path_segment, the render's. No queue, no atomics, no barrier, no dynamic LDS,
+// and nothing that reads the kernel arguments by address (kernarg_here and what
+// is built on it: frame_vals, start_sample, begin_sample, params_at<true>): this
+// kernel's arguments do not begin with a KParams. A wave runs as long as its
+// longest lane (the deliberately plain form: DESIGN.md §3j has the audit of
+// every access below and the measurement against the scheduled render).
+//
+// A sample starts as start_sample starts it in a frame without a lens — two
+// hash2 calls, whose values the zero-film twin multiplies by zero — and then as
+// begin_sample's tail does, on the query's own ray.
+struct PathLane {
+    f3 o, d, col, acc;
+    float a, inv_a, seed;
+    uint32_t bounce, sample, segs;
+    bool active;
+};
+__device__ __forceinline__ void paths_begin_sample(PathLane &L, f3 o, f3 d) {
+    float h0, h1;
+    hash2(L.seed, h0, h1);  // u's (the seed moves; the twin's u * 0 drops the value)
+    hash2(L.seed, h0, h1);  // v's
+    L.o = o;
+    L.d = d;
+    L.a = dir_len2(d);
+    L.inv_a = 1.0f / L.a;
+    L.col = mk3(1.0f, 1.0f, 1.0f);
+    L.bounce = 0;
+}
+__global__ void __launch_bounds__(kRB) k_paths(const KPaths P, const float4 *__restrict__ queries,
+                                               const uint32_t *__restrict__ perm, float4 *results,
+                                               uint32_t *__restrict__ segments) {
+    __shared__ uint32_t list[list_bytes<true>() > kListBytes ? list_bytes<true>() / sizeof(uint32_t)
+                                                             : kListBytes / sizeof(uint32_t)];
+    const uint32_t g = blockIdx.x * kRB + threadIdx.x;
+    if (!paths_lane_live((uint64_t)blockIdx.x * kRB + threadIdx.x, P.n)) return;
+    const uint32_t i = paths_lane_query(g, perm != nullptr, perm ? perm[g] : 0u, P.n);
+    const float4 q0 = queries[2 * (size_t)i], q1 = queries[2 * (size_t)i + 1];
+    const f3 qo = mk3(q0.x, q0.y, q0.z);
+    const f3 qd = mk3(q1.x, q1.y, q1.z);
+    PathLane L;
+    L.acc = mk3(0.0f, 0.0f, 0.0f);
+    L.seed = q0.w;
+    if ((P.mode & kPathsContinue) != 0u) {  // from the record an earlier call left
+        const float4 r = results[i];
+        L.acc = mk3(r.x, r.y, r.z);
+        L.seed = r.w;
+    }
+    L.sample = 0;
+    L.segs = 0;
+    L.active = true;
+    paths_begin_sample(L, qo, qd);
+    const KScene &S = P.scene;
+    const int last = (int)S.n - 1;
+    while (__ballot(L.active) != 0ull) {
+        if (L.active) {
+            float best = __uint_as_float(0x7f800000u);
+            // (an empty world is all sky: its scan would have nothing to clamp a list position to)
+            const int hit = S.n == 0u ? -1
+                            : min((S.cpre && S.n_pad > kScanPfMin)
+                                      ? hit_world_culled(S, L.o, L.d, L.a, L.inv_a, kTMin, best, list)
+                                  : S.n_pad > kScanPfMin ? hit_world_pre<true>(S, L.o, L.d, L.a, L.inv_a, kTMin, best, list)
+                                                         : hit_world_pre<false>(S, L.o, L.d, L.a, L.inv_a, kTMin, best, list),
+                                  last);
+            L.segs++;
+            f3 c = mk3(0.0f, 0.0f, 0.0f);
+            const int r = path_segment(P, L, hit, best, c);
+            if (r == kSegSky) L.acc = L.acc + c;  // shade's add; a black path adds nothing
+            if (r != kSegContinue) {
+                L.sample++;
+                if (L.sample >= P.samples) {
+                    results[i] = make_float4(L.acc.x, L.acc.y, L.acc.z, L.seed);
+                    if (segments) segments[i] = L.segs;
+                    L.active = false;
+                } else {
+                    paths_begin_sample(L, qo, qd);
+                }
+            }
+        }
+    }
+}
+
 // rtx_mask_from_ids, two passes (rtx_features.h): which pixels are listed, then
 // the Chebyshev growth and the number of set pixels (one atomic per wave that
 // has any). The id list travels as a kernel argument.
@@ -4925,6 +5012,14 @@ hipError_t launch_cast(const KScene &s, const float4 *rays, uint32_t n, float t_
                        float4 *hits, uint8_t *occluded, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_cast, dim3(ceil_div(n, kRB)), dim3(kRB), 0, stream, s, rays, n, t_min, perm, hits, occluded);
+    return hipGetLastError();
+}
+
+hipError_t launch_paths(const KPaths &p, const float4 *queries, const uint32_t *perm, float4 *results,
+                        uint32_t *segments, hipStream_t stream) {
+    if (p.n == 0) return hipSuccess;
+    if (p.samples == 0 || p.depth == 0) return hipErrorInvalidValue;  // (the loop's end needs both)
+    hipLaunchKernelGGL(k_paths, dim3(paths_blocks(p.n, kRB)), dim3(kRB), 0, stream, p, queries, perm, results, segments);
     return hipGetLastError();
 }
 

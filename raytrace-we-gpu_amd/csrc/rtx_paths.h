@@ -1,8 +1,9 @@
 // rtx_paths.h — the host-side rules of path queries along caller-chosen rays
-// (include/rtx.h rtx_path_seed): a query record's layout and the seed of a
-// pixel's RNG chain. HIP-free: the host (rtx_host.cpp) and the CPU checker
-// (tests/paths_check.cpp) run this one text, and a device entry point that
-// traces such queries is to run it too.
+// (include/rtx.h rtx_path_seed, rtx_trace_paths): a query record's layout, the
+// seed of a pixel's RNG chain, the entry point's argument rules and the
+// launch's index arithmetic. HIP-free: the host (rtx_host.cpp, rtx_api.hip),
+// the kernel (rtx_kernels.hip k_paths) and the CPU checkers
+// (tests/paths_check.cpp, tests/paths_args_check.cpp) run this one text.
 //
 // The rule the seed serves. In a frame whose horizontal and vertical rows are
 // zero, get_ray gives every pixel the same ray, d = fl(lower_left - origin)
@@ -56,5 +57,63 @@ RTX_PATHS_HD float path_seed(uint32_t x, uint32_t y, uint32_t frame_index) {
 RTX_PATHS_HD bool paths_count_ok(uint32_t samples, uint32_t depth) {
     return (uint64_t)samples * (uint64_t)depth < (1ull << 32);
 }
+
+// ---- rtx_trace_paths: the argument rules and the launch's arithmetic ---------
+// A result record is one float4: (sum.xyz, the chain's seed after the last
+// sample): a one-pixel chain state (rtx_refine_export's layout).
+constexpr uint32_t kPathResultBytes = 16u;
+constexpr uint32_t kPathsLambertGuard = 1u;  // = RTX_PATHS_LAMBERT_GUARD
+constexpr uint32_t kPathsContinue = 2u;      // = RTX_PATHS_CONTINUE
+constexpr uint32_t kPathsFlagMask = kPathsLambertGuard | kPathsContinue;
+constexpr uint32_t kPathsOrderMax = 2u;      // RTX_CAST_ORDER_AUTO, _GIVEN, _COHERENT = 0, 1, 2
+
+// What rtx_trace_paths refuses before it looks at the context, in the order it
+// tests them (a null ctx comes before all of these).
+enum PathsArg : int {
+    kPathsArgOk = 0,
+    kPathsArgQueries,  // n > 0 with d_queries NULL
+    kPathsArgResults,  // n > 0 with d_results NULL
+    kPathsArgSamples,  // samples == 0
+    kPathsArgFlags,    // a bit outside kPathsFlagMask
+    kPathsArgOrder,    // order > kPathsOrderMax
+};
+RTX_PATHS_HD PathsArg paths_args(bool have_queries, bool have_results, uint32_t n, uint32_t samples, uint32_t flags,
+                                 uint32_t order) {
+    if (n != 0u && !have_queries) return kPathsArgQueries;
+    if (n != 0u && !have_results) return kPathsArgResults;
+    if (samples == 0u) return kPathsArgSamples;
+    if ((flags & ~kPathsFlagMask) != 0u) return kPathsArgFlags;
+    if (order > kPathsOrderMax) return kPathsArgOrder;
+    return kPathsArgOk;
+}
+// ... and once the world is known: its depth.
+enum PathsWorld : int { kPathsWorldOk = 0, kPathsWorldDepth0, kPathsWorldCount };
+RTX_PATHS_HD PathsWorld paths_world(uint32_t samples, uint32_t depth) {
+    if (depth == 0u) return kPathsWorldDepth0;
+    if (!paths_count_ok(samples, depth)) return kPathsWorldCount;
+    return kPathsWorldOk;
+}
+// The frame flags path_segment sees (rtx_internal.h kFrameLambertGuard = 1).
+RTX_PATHS_HD uint32_t paths_frame_flags(uint32_t flags) { return (flags & kPathsLambertGuard) != 0u ? 1u : 0u; }
+
+// The exact grid: ceil(n / block) workgroups, for every n below 2^32 (n +
+// block - 1 in 32 bits wraps from n = 2^32 - block + 1).
+RTX_PATHS_HD uint32_t paths_blocks(uint32_t n, uint32_t block) {
+    return (uint32_t)(((uint64_t)n + block - 1u) / block);
+}
+// Lane g of that grid: whether it owns a query (g counted in 64 bits: the
+// grid's last lanes lie past 2^32 - 1 for the largest n), and which — the g-th
+// of the order `perm` (an entry, whatever it holds, is clamped to n - 1) or
+// query g itself. n > 0.
+RTX_PATHS_HD bool paths_lane_live(uint64_t g, uint32_t n) { return g < (uint64_t)n; }
+RTX_PATHS_HD uint32_t paths_lane_query(uint32_t g, bool have_perm, uint32_t perm_g, uint32_t n) {
+    if (!have_perm) return g;
+    return perm_g < n - 1u ? perm_g : n - 1u;
+}
+// Byte offsets of query i's two float4, of its result and of its segment word:
+// 64-bit, so that i * 32 does not wrap from i = 2^27.
+RTX_PATHS_HD uint64_t paths_query_offset(uint32_t i) { return (uint64_t)i * kPathRayBytes; }
+RTX_PATHS_HD uint64_t paths_result_offset(uint32_t i) { return (uint64_t)i * kPathResultBytes; }
+RTX_PATHS_HD uint64_t paths_segment_offset(uint32_t i) { return (uint64_t)i * 4u; }
 
 }  // namespace rtx

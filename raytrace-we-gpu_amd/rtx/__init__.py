@@ -57,6 +57,10 @@ CAST_ORDERS = {"auto": 0, "given": 1, "coherent": 2}  # rtx_cast_rays (RTX_CAST_
 RAY_DTYPE = np.dtype([("o", "<f4", (3,)), ("t_max", "<f4"), ("d", "<f4", (3,)), ("tag", "<u4")])
 RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("index", "<i4"), ("normal", "<f4", (3,)), ("front_face", "<u4"),
                           ("reserved", "<u4", (2,))])
+# rtx_path_query (32 bytes; also a row of 8 float32: o, seed, d, tag) / rtx_path_result (16 bytes: a float4)
+PATH_QUERY_DTYPE = np.dtype([("o", "<f4", (3,)), ("seed", "<f4"), ("d", "<f4", (3,)), ("tag", "<u4")])
+PATH_RESULT_DTYPE = np.dtype([("sum", "<f4", (3,)), ("seed", "<f4")])
+PATHS_LAMBERT_GUARD, PATHS_CONTINUE = 1, 2  # rtx_trace_paths flags (RTX_PATHS_*)
 GATHER_MODES = {"auto": 0, "rccl": 1, "copy": 2}  # rtx_group_create (RTX_GATHER_*)
 GROUP_MAX = 64  # RTX_GROUP_MAX
 
@@ -184,6 +188,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_cast_rays": (C.c_int, [ctx, vp, u32, C.c_float, u32, vp, vp]),
         "rtx_cast_last_order": (C.c_int, [ctx]),
         "rtx_path_seed": (C.c_float, [u32, u32, u32]),
+        "rtx_trace_paths": (C.c_int, [ctx, vp, u32, u32, u32, u32, vp, vp]),
+        "rtx_paths_last_order": (C.c_int, [ctx]),
         "rtx_camera_set_aperture": (C.c_int, [C.POINTER(rtx_frame), C.c_float]),
         "rtx_part_rows": (u32, [u32, u32, u32, u32]),
         "rtx_deinterleave_rows": (C.c_int, [ctx, vp, u32, u32, u32, u32, vp]),
@@ -252,6 +258,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     optional |= {"rtx_features", "rtx_features_rows", "rtx_pick", "rtx_mask_from_ids"}  # ... probe "rtx_features"
     optional |= {"rtx_cast_rays", "rtx_cast_last_order"}         # ... probe "rtx_cast_rays"
     optional |= {"rtx_path_seed"}                                # ... probe "rtx_path_seed"
+    optional |= {"rtx_trace_paths", "rtx_paths_last_order"}      # ... probe "rtx_trace_paths"
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -288,6 +295,19 @@ def path_seed(x: int, y: int, frame_index: int = 0) -> np.float32:
     if not hasattr(lib, "rtx_path_seed"):
         raise RtxError("this librtx has no rtx_path_seed")
     return np.float32(lib.rtx_path_seed(x, y, frame_index))
+
+
+def path_queries(o, d, seeds, tags=None) -> np.ndarray:
+    """n PATH_QUERY_DTYPE records from origins and directions ((n, 3), or one (3,) for all) and seeds
+    ((n,), e.g. path_seed(x, y, f) per query); tags: the caller's words, 0 when None."""
+    seeds = np.ascontiguousarray(seeds, np.float32).reshape(-1)
+    q = np.zeros(seeds.size, PATH_QUERY_DTYPE)
+    q["o"] = np.asarray(o, np.float32)
+    q["d"] = np.asarray(d, np.float32)
+    q["seed"] = seeds
+    if tags is not None:
+        q["tag"] = np.asarray(tags, np.uint32)
+    return q
 
 
 def _check(rc: int, what: str, lib: Optional[C.CDLL] = None):
@@ -814,6 +834,84 @@ class Context:
             if v == code:
                 return name
         raise RtxError(f"rtx_cast_last_order returned {code}")
+
+    def trace_paths(self, queries, samples: int, flags: int = 0, order: str = "auto", results=None,
+                    segments=False, cont: bool = False, n: Optional[int] = None):
+        """What the rays of `queries` see: `samples` path-traced samples each,
+        along the RNG chain from the query's seed, to the world's depth
+        (rtx_trace_paths). Returns (results, segments), segments None when not
+        asked for.
+
+        queries: a numpy array — (n, 8) float32 rows (o, seed, d, tag) or n
+        PATH_QUERY_DTYPE records (path_queries) — is uploaded, and numpy arrays
+        come back (n PATH_RESULT_DTYPE records, n uint32), after a wait. A
+        device pointer, a DeviceArray or a torch tensor is used in place,
+        asynchronously on the context's stream, and the device buffers come
+        back (`n`: the number of queries, when the object has no shape).
+        results: None (allocate one), or the caller's buffer, which is filled
+        and returned as it is; with numpy queries, a numpy array of n records
+        (or (n, 4) float32) to continue from. segments: True (allocate one),
+        False (none), or the caller's device buffer. cont: continue from what
+        `results` holds (RTX_PATHS_CONTINUE; also as a bit of `flags`). order:
+        "auto", "given" or "coherent" — a schedule, never a different
+        record."""
+        flags = int(flags) | (PATHS_CONTINUE if cont else 0)
+        if not hasattr(self._lib, "rtx_trace_paths"):
+            raise RtxError("this librtx has no rtx_trace_paths")
+        if isinstance(queries, np.ndarray):
+            host = np.ascontiguousarray(queries)
+            if host.dtype != PATH_QUERY_DTYPE:
+                host = np.ascontiguousarray(host, np.float32).reshape(-1, 8)
+            n = host.shape[0]
+            start = None
+            if flags & PATHS_CONTINUE:
+                if not isinstance(results, np.ndarray):
+                    raise RtxError("Context.trace_paths: continuing numpy queries needs numpy results")
+                start = np.ascontiguousarray(results)
+                if start.dtype != PATH_RESULT_DTYPE:
+                    start = np.ascontiguousarray(start, np.float32).reshape(-1, 4)
+                if start.shape[0] != n:
+                    raise RtxError("Context.trace_paths: results and queries differ in length")
+            elif results is not None:
+                raise RtxError("Context.trace_paths: numpy queries take results only to continue from")
+            d_q = self.alloc((max(n, 1),), PATH_QUERY_DTYPE)
+            d_r = self.alloc((max(n, 1),), PATH_RESULT_DTYPE)
+            d_s = self.alloc((max(n, 1),), np.uint32) if segments is True else None
+            try:
+                if n:
+                    _check(self._lib.rtx_copy_to_device(self._h, C.c_void_p(d_q.ptr), host.ctypes.data, 32 * n),
+                           "rtx_copy_to_device", self._lib)
+                    if start is not None:
+                        _check(self._lib.rtx_copy_to_device(self._h, C.c_void_p(d_r.ptr), start.ctypes.data, 16 * n),
+                               "rtx_copy_to_device", self._lib)
+                self.trace_paths(d_q, samples, flags, order, d_r, d_s if d_s is not None else segments, False, n)
+                return d_r.numpy()[:n], (d_s.numpy()[:n] if d_s is not None else (None if segments is False else segments))
+            finally:
+                d_q.free()
+                d_r.free()
+                if d_s is not None:
+                    d_s.free()
+        if n is None:
+            if not hasattr(queries, "shape"):
+                raise RtxError("Context.trace_paths: n is needed with a bare pointer")
+            n = int(queries.shape[0])
+        if results is None:
+            if flags & PATHS_CONTINUE:
+                raise RtxError("Context.trace_paths: continuing needs the results to continue from")
+            results = self.alloc((max(n, 1),), PATH_RESULT_DTYPE)
+        d_seg = self.alloc((max(n, 1),), np.uint32) if segments is True else (None if segments is False else segments)
+        _check(self._lib.rtx_trace_paths(self._h, C.c_void_p(_dev_ptr(queries)), n, samples, flags, CAST_ORDERS[order],
+                                         C.c_void_p(_dev_ptr(results)), C.c_void_p(_dev_ptr(d_seg))),
+               "rtx_trace_paths", self._lib)
+        return results, d_seg
+
+    def paths_last_order(self) -> str:
+        """"given" or "coherent": what the last trace_paths ran (rtx_paths_last_order)."""
+        code = self._lib.rtx_paths_last_order(self._h)
+        for name, v in CAST_ORDERS.items():
+            if v == code:
+                return name
+        raise RtxError(f"rtx_paths_last_order returned {code}")
 
     def deinterleave(self, d_gathered: int, width: int, height: int, tile_rows: int, nparts: int,
                      d_image: int):
