@@ -40,6 +40,11 @@ extern "C" {
 
 #define RTX_VERSION 145 /* 1.4.5 */
 /* ABI notes.
+ *  1.4.5 (later builds, no version bump): rtx_trace_paths_keyed
+ *         (RTX_PATHS_ORDER_COST) and rtx_debug_paths_order (path queries in
+ *         cost order, by the caller's keys or the library's own probe; the
+ *         records are rtx_trace_paths'); purely additive again: probe for the
+ *         symbol (dlsym "rtx_trace_paths_keyed").
  *  1.4.5 (later builds, no version bump): rtx_trace_paths (rtx_path_query,
  *         rtx_path_result, RTX_PATHS_*) and rtx_paths_last_order (what rays of
  *         the caller's choosing see: path-traced sample sums along the RNG
@@ -838,6 +843,47 @@ enum { RTX_PATHS_LAMBERT_GUARD = 1, RTX_PATHS_CONTINUE = 2 };
 RTX_API int rtx_trace_paths(rtx_ctx *ctx, const void *d_queries, uint32_t n, uint32_t samples,
                             uint32_t flags, uint32_t order, void *d_results, void *d_segments);
 RTX_API int rtx_paths_last_order(rtx_ctx *ctx);  /* GIVEN or COHERENT: what the last call ran */
+/* ---- path queries in cost order -----------------------------------------------
+ * (later builds, no version bump: probe with dlsym "rtx_trace_paths_keyed").
+ * rtx_trace_paths with the schedule chosen by keys: every record — sum, end
+ * seed, and the call's own segment count per query, NaN sums included,
+ * RTX_PATHS_CONTINUE and RTX_PATHS_LAMBERT_GUARD honoured — is bit for bit
+ * what rtx_trace_paths(ctx, d_queries, n, samples, flags, RTX_CAST_ORDER_GIVEN,
+ * d_results, d_segments) writes. The order is a schedule and nothing else: the
+ * longest queries first, so that the 64 lanes of a wave hold queries of
+ * similar length. Asynchronous on the context stream; needs no frame; touches
+ * no stats, framebuffer, chain state or cost map.
+ * d_keys != NULL: n uint32 on the device, and probe must be 0. Lane g of the
+ * one launch takes the g-th query in non-increasing order of min(key, 65535);
+ * the order among equal keys is unspecified (a workgroup's queries of one key
+ * stay together). d_keys may be d_segments: the keys are copied to the
+ * context's scratch before the trace is enqueued, so "order this step by the
+ * segments the last step wrote" works in place.
+ * d_keys == NULL: the library probes. p = probe, or with probe == 0 the
+ * default: 2, or 1 for a world of more than 1,024 spheres after padding. With
+ * samples <= p the call is one plain launch in the given order. Otherwise p
+ * samples run in the given order, their segment counts are the keys, and the
+ * remaining samples - p follow in cost order as a continuing call;
+ * d_segments[i] is the whole call's count.
+ * rtx_paths_last_order returns RTX_PATHS_ORDER_COST after a call that sorted
+ * and GIVEN after a samples <= p call. rtx_trace_paths itself still refuses
+ * order 3.
+ * rtx_debug_paths_order: the permutation the last sorted keyed call used, to
+ * host memory (synchronous; bytes == n * 4). RTX_ERR_STATE when the last path
+ * call did not sort by cost, or when a later rtx_cast_rays or COHERENT path
+ * call has reused the scratch; RTX_ERR_INVALID for a null argument or a wrong
+ * bytes.
+ * RTX_ERR_INVALID, before any HIP call and before the context is looked at,
+ * first failure first: a null ctx; n > 0 with d_queries NULL, then with
+ * d_results NULL; samples == 0; unknown flag bits; d_keys != NULL with
+ * probe != 0. RTX_ERR_STATE: no world. RTX_ERR_INVALID once the world is
+ * known: its depth is 0, or samples * depth >= 2^32. n == 0 returns RTX_OK and
+ * launches nothing. */
+enum { RTX_PATHS_ORDER_COST = 3 };   /* reported by rtx_paths_last_order; rtx_trace_paths still refuses order 3 */
+RTX_API int rtx_trace_paths_keyed(rtx_ctx *ctx, const void *d_queries, uint32_t n, uint32_t samples,
+                                  uint32_t flags, const void *d_keys, uint32_t probe,
+                                  void *d_results, void *d_segments);
+RTX_API int rtx_debug_paths_order(rtx_ctx *ctx, uint32_t *host_perm, size_t bytes);
 /* Device pointer of the chain state (width*height float4; a part state: its
  * rows * width), NULL if none. */
 RTX_API void *rtx_refine_state(rtx_ctx *ctx);

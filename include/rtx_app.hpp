@@ -171,7 +171,16 @@ public:
     bool TracePaths(const std::vector<rtx_path_query> &queries, uint32_t samples,
                     std::vector<rtx_path_result> *results, uint32_t flags = 0, int order = RTX_CAST_ORDER_AUTO,
                     std::vector<uint32_t> *segments = nullptr);
-    // RTX_CAST_ORDER_GIVEN or _COHERENT: what the last TracePaths ran (rtx_paths_last_order).
+    // TracePaths in cost order, the longest queries first
+    // (rtx_trace_paths_keyed): the records are TracePaths(..., RTX_CAST_ORDER_GIVEN)'s,
+    // bit for bit. keys: NULL — the library probes with `probe` samples (0: its
+    // default) — or one uint32 per query, larger for longer (probe must be 0).
+    bool TracePathsKeyed(const std::vector<rtx_path_query> &queries, uint32_t samples,
+                         std::vector<rtx_path_result> *results, uint32_t flags = 0,
+                         const std::vector<uint32_t> *keys = nullptr, uint32_t probe = 0,
+                         std::vector<uint32_t> *segments = nullptr);
+    // RTX_CAST_ORDER_GIVEN or _COHERENT: what the last TracePaths ran; RTX_PATHS_ORDER_COST
+    // after a TracePathsKeyed that sorted (rtx_paths_last_order).
     int PathsLastOrder() const;
     // Click to focus: picks the pixel, takes the hit's plane depth
     // dot(p - cam_pos, normalize(cam_look_at - cam_pos)) as the focus distance,

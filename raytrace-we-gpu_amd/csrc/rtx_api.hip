@@ -145,6 +145,14 @@ struct rtx_ctx {
     size_t cast_rays = 0;
     int cast_last = RTX_CAST_ORDER_GIVEN;
     int paths_last = RTX_CAST_ORDER_GIVEN;  // rtx_trace_paths: the order its last call ran
+    // rtx_trace_paths_keyed: the probe's segment counts (paths_probe_cap words,
+    // grown on demand; its own buffer, so d_cast's size rule stays), and
+    // whether d_cast's perm still holds the cost order of paths_perm_n queries
+    // (rtx_debug_paths_order): every call that sorts into d_cast clears it first
+    uint32_t *d_paths_probe = nullptr;
+    size_t paths_probe_cap = 0;
+    bool paths_perm_valid = false;
+    uint32_t paths_perm_n = 0;
     // measurement
     unsigned long long *d_counters = nullptr;
     unsigned long long *d_wave_times = nullptr;  // diagnostic (rtx_debug_wave_times)
@@ -365,6 +373,7 @@ void rtx_destroy(rtx_ctx *c) {
     (void)hipFree(c->d_adapt);
     (void)hipFree(c->d_feat);
     (void)hipFree(c->d_cast);
+    (void)hipFree(c->d_paths_probe);
     (void)hipFree(c->d_counters);
     (void)hipFree(c->d_wave_times);
     (void)hipFree(c->d_sched);
@@ -1976,6 +1985,7 @@ int rtx_cast_rays(rtx_ctx *c, const void *d_rays, uint32_t n, float t_min, uint3
     const float4 *rays = static_cast<const float4 *>(d_rays);
     const uint32_t *perm = nullptr;
     if (sort) {
+        c->paths_perm_valid = false;  // (the scratch is about to hold another order)
         rc = ensure_cast(c, n);
         if (rc) return rc;
         const rtx::KCastScratch k{c->d_cast, c->d_cast + rtx::kCastBuckets, c->d_cast + rtx::kCastBuckets + c->cast_rays};
@@ -2037,6 +2047,7 @@ int rtx_trace_paths(rtx_ctx *c, const void *d_queries, uint32_t n, uint32_t samp
     if (rc) return rc;
     const float4 *queries = static_cast<const float4 *>(d_queries);
     const uint32_t *perm = nullptr;
+    c->paths_perm_valid = false;  // (rtx_debug_paths_order: this call is not a cost-ordered one)
     if (sort) {  // rtx_cast_rays' passes and scratch, unchanged: a query holds o and d where a ray does
         rc = ensure_cast(c, n);
         if (rc) return rc;
@@ -2055,6 +2066,105 @@ int rtx_trace_paths(rtx_ctx *c, const void *d_queries, uint32_t n, uint32_t samp
 int rtx_paths_last_order(rtx_ctx *c) {
     if (!c) return fail(RTX_ERR_INVALID, "rtx_paths_last_order: null ctx");
     return c->paths_last;
+}
+
+// ---- path queries in cost order (rtx_paths.h: the cost order) ------------------
+static_assert(RTX_PATHS_ORDER_COST == rtx::kPathsOrderCost && rtx::kPathsCostBuckets == rtx::kCastBuckets,
+              "rtx_paths.h restates these");
+// The probe's segment counts for n queries. Once it fits there is no host wait.
+static int ensure_paths_probe(rtx_ctx *c, size_t n) {
+    if (c->d_paths_probe && c->paths_probe_cap >= n) return RTX_OK;
+    RTX_HIP(hipStreamSynchronize(c->stream));
+    (void)hipFree(c->d_paths_probe);
+    c->d_paths_probe = nullptr;
+    c->paths_probe_cap = 0;
+    RTX_HIP(hipMalloc(&c->d_paths_probe, n * sizeof(uint32_t)));
+    c->paths_probe_cap = n;
+    return RTX_OK;
+}
+
+int rtx_trace_paths_keyed(rtx_ctx *c, const void *d_queries, uint32_t n, uint32_t samples, uint32_t flags,
+                          const void *d_keys, uint32_t probe, void *d_results, void *d_segments) {
+    // the argument rules first (rtx_paths.h): none of them looks at the context
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_trace_paths_keyed: null ctx");
+    switch (rtx::paths_keyed_args(d_queries != nullptr, d_results != nullptr, n, samples, flags, d_keys != nullptr,
+                                  probe)) {
+    case rtx::kPathsKeyedArgQueries: return fail(RTX_ERR_INVALID, "rtx_trace_paths_keyed: d_queries is NULL");
+    case rtx::kPathsKeyedArgResults: return fail(RTX_ERR_INVALID, "rtx_trace_paths_keyed: d_results is NULL");
+    case rtx::kPathsKeyedArgSamples: return fail(RTX_ERR_INVALID, "rtx_trace_paths_keyed: samples is 0");
+    case rtx::kPathsKeyedArgFlags: return fail(RTX_ERR_INVALID, "rtx_trace_paths_keyed: unknown flags");
+    case rtx::kPathsKeyedArgProbe: return fail(RTX_ERR_INVALID, "rtx_trace_paths_keyed: probe must be 0 with d_keys");
+    case rtx::kPathsKeyedArgOk: break;
+    }
+    if (!c->have_world) return fail(RTX_ERR_STATE, "rtx_trace_paths_keyed: no world uploaded");
+    switch (rtx::paths_world(samples, c->depth)) {
+    case rtx::kPathsWorldDepth0: return fail(RTX_ERR_INVALID, "rtx_trace_paths_keyed: the world's depth is 0");
+    case rtx::kPathsWorldCount:
+        return fail(RTX_ERR_INVALID, "rtx_trace_paths_keyed: samples * depth does not fit 32 bits");
+    case rtx::kPathsWorldOk: break;
+    }
+    if (n == 0) return RTX_OK;
+    rtx::KPaths p;
+    p.scene = scene_of(c);
+    p.depth = c->depth;
+    p.flags = rtx::paths_frame_flags(flags);
+    p.samples = samples;
+    p.n = n;
+    p.mode = flags & rtx::kPathsContinue;
+    int rc = set_device(c);
+    if (rc) return rc;
+    const float4 *queries = static_cast<const float4 *>(d_queries);
+    float4 *results = static_cast<float4 *>(d_results);
+    uint32_t *segments = static_cast<uint32_t *>(d_segments);
+    c->paths_perm_valid = false;
+    const uint32_t pr = d_keys ? 0u : (probe != 0u ? probe : rtx::paths_default_probe(p.scene.n_pad));
+    if (!d_keys && !rtx::paths_two_phase(samples, pr)) {  // nothing left to order: one plain launch
+        const hipError_t e = rtx::launch_paths(p, queries, nullptr, results, segments, c->stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_paths");
+        c->paths_last = RTX_CAST_ORDER_GIVEN;
+        return RTX_OK;
+    }
+    rc = ensure_cast(c, n);
+    if (rc) return rc;
+    const uint32_t *src = static_cast<const uint32_t *>(d_keys);
+    if (!d_keys) {  // phase A: the probe, in the given order, its counts kept aside
+        rc = ensure_paths_probe(c, n);
+        if (rc) return rc;
+        p.samples = pr;
+        const hipError_t e = rtx::launch_paths(p, queries, nullptr, results, c->d_paths_probe, c->stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_paths");
+        src = c->d_paths_probe;
+        p.samples = samples - pr;
+        p.mode = rtx::kPathsContinue;
+    }
+    // the sort reads src in its first pass only, before the trace below is enqueued: d_keys may be d_segments
+    const rtx::KCastScratch k{c->d_cast, c->d_cast + rtx::kCastBuckets, c->d_cast + rtx::kCastBuckets + c->cast_rays};
+    hipError_t e = rtx::launch_paths_cost_order(src, n, k, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_paths_cost_order");
+    e = rtx::launch_paths(p, queries, k.perm, results, segments, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_paths");
+    if (!d_keys && segments) {  // the whole call's count: the probe's plus the rest's
+        e = rtx::launch_paths_add_segments(segments, c->d_paths_probe, n, c->stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_paths_add_segments");
+    }
+    c->paths_last = RTX_PATHS_ORDER_COST;
+    c->paths_perm_valid = true;
+    c->paths_perm_n = n;
+    return RTX_OK;
+}
+
+int rtx_debug_paths_order(rtx_ctx *c, uint32_t *host_perm, size_t bytes) {
+    if (!c || !host_perm) return fail(RTX_ERR_INVALID, "rtx_debug_paths_order: null argument");
+    if (!c->paths_perm_valid || c->paths_last != RTX_PATHS_ORDER_COST || !c->d_cast)
+        return fail(RTX_ERR_STATE, "rtx_debug_paths_order: the last path call's cost order is not at hand");
+    if (bytes != (size_t)c->paths_perm_n * sizeof(uint32_t))
+        return fail(RTX_ERR_INVALID, "rtx_debug_paths_order: bytes != n * 4");
+    int rc = set_device(c);
+    if (rc) return rc;
+    const uint32_t *perm = c->d_cast + rtx::kCastBuckets + c->cast_rays;
+    RTX_HIP(hipMemcpyAsync(host_perm, perm, bytes, hipMemcpyDeviceToHost, c->stream));
+    RTX_HIP(hipStreamSynchronize(c->stream));
+    return RTX_OK;
 }
 
 int rtx_debug_pixel_cost(rtx_ctx *c, uint32_t spp, uint32_t *host_cost) {

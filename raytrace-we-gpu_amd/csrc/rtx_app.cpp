@@ -324,6 +324,50 @@ bool RtxCSApp::TracePaths(const std::vector<rtx_path_query> &queries, uint32_t s
     return ok;
 }
 
+bool RtxCSApp::TracePathsKeyed(const std::vector<rtx_path_query> &queries, uint32_t samples,
+                               std::vector<rtx_path_result> *results, uint32_t flags,
+                               const std::vector<uint32_t> *keys, uint32_t probe, std::vector<uint32_t> *segments) {
+    if (!m_ok) return false;
+    if (!results) {
+        m_error = "TracePathsKeyed: results is NULL";
+        return false;
+    }
+    if (queries.size() > 0xffffffffull) {
+        m_error = "TracePathsKeyed: more than 2^32 - 1 queries";
+        return false;
+    }
+    if (keys && keys->size() != queries.size()) {
+        m_error = "TracePathsKeyed: one key per query";
+        return false;
+    }
+    const bool cont = (flags & RTX_PATHS_CONTINUE) != 0u;
+    if (cont && results->size() != queries.size()) {
+        m_error = "TracePathsKeyed: RTX_PATHS_CONTINUE needs one record per query to continue from";
+        return false;
+    }
+    results->resize(queries.size());
+    if (segments) segments->resize(queries.size());
+    const uint32_t n = (uint32_t)queries.size();
+    const size_t qbytes = (size_t)n * sizeof(rtx_path_query), rbytes = (size_t)n * sizeof(rtx_path_result);
+    const size_t sbytes = (size_t)n * sizeof(uint32_t);
+    void *d[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool ok = n == 0 || (rtx_alloc(m_ctx, qbytes, &d[0]) == RTX_OK && rtx_alloc(m_ctx, rbytes, &d[1]) == RTX_OK &&
+                         (!segments || rtx_alloc(m_ctx, sbytes, &d[2]) == RTX_OK) &&
+                         (!keys || (rtx_alloc(m_ctx, sbytes, &d[3]) == RTX_OK &&
+                                    rtx_copy_to_device(m_ctx, d[3], keys->data(), sbytes) == RTX_OK)) &&
+                         rtx_copy_to_device(m_ctx, d[0], queries.data(), qbytes) == RTX_OK &&
+                         (!cont || rtx_copy_to_device(m_ctx, d[1], results->data(), rbytes) == RTX_OK));
+    // (an empty batch with keys: any non-null pointer says "keys given", and nothing reads it)
+    const void *kp = keys ? (n != 0 ? d[3] : static_cast<const void *>(keys)) : nullptr;
+    ok = ok && rtx_trace_paths_keyed(m_ctx, d[0], n, samples, flags, kp, probe, d[1], d[2]) == RTX_OK;
+    if (ok && n != 0) ok = rtx_copy_to_host(m_ctx, results->data(), d[1], rbytes) == RTX_OK;
+    if (ok && n != 0 && segments) ok = rtx_copy_to_host(m_ctx, segments->data(), d[2], sbytes) == RTX_OK;
+    if (!ok) m_error = rtx_last_error();
+    for (void *p : d)
+        if (p) rtx_free(m_ctx, p);
+    return ok;
+}
+
 int RtxCSApp::PathsLastOrder() const { return m_ctx ? rtx_paths_last_order(m_ctx) : RTX_CAST_ORDER_GIVEN; }
 
 bool RtxCSApp::Pick(uint32_t x, uint32_t y, rtx_hit *out) {

@@ -15,7 +15,8 @@
 //           [--refine-adaptive S,THRESHOLD[,MAX] --steps K] [--dump-counts FILE]
 //           [--aov PREFIX] [--pick X,Y] [--focus-at X,Y] [--refine-ids S,ID[,ID...] --grow G --steps K]
 //           [--cast RAYS.bin --hits OUT.bin [--cast-order auto|given|coherent] [--t-min T]]
-//           [--paths QUERIES.bin --samples S [--continue] --results OUT.bin [--segments SEG.bin]]
+//           [--paths QUERIES.bin --samples S [--continue] --results OUT.bin [--segments SEG.bin]
+//            [--paths-order cost [--paths-probe P]] [--paths-keys KEYS.bin]]
 // --paths QUERIES.bin traces the file's path queries in the scene
 // (rtx_trace_paths) instead of rendering: QUERIES.bin is raw little-endian
 // rtx_path_query records (32 bytes: o, seed, d, tag), OUT.bin receives one
@@ -25,6 +26,11 @@
 // every query from its record. The depth is --depth's, the schedule
 // --cast-order's, --lambert-guard sets RTX_PATHS_LAMBERT_GUARD. The JSON line is
 // {"paths": {"queries", "samples", "segments", "order", "continued", "ms"}}.
+// --paths-order cost traces them in cost order instead (rtx_trace_paths_keyed;
+// the same records, "order" says "cost" when the call sorted): by the library's
+// probe of --paths-probe P samples (default 0: its own choice), or with
+// --paths-keys KEYS.bin by the file's keys, one raw uint32 per query, larger
+// for longer (--paths-keys alone implies --paths-order cost).
 // --cast RAYS.bin casts the file's rays into the scene (rtx_cast_rays) instead
 // of rendering: RAYS.bin is raw little-endian rtx_ray records (32 bytes: o,
 // t_max, d, tag), OUT.bin receives one rtx_ray_hit record (32 bytes) per ray
@@ -120,7 +126,8 @@ static void usage() {
                  "               [--aov PREFIX] [--pick X,Y] [--focus-at X,Y]\n"
                  "               [--refine-ids S,ID[,ID...] --grow G --steps K]\n"
                  "               [--cast RAYS.bin --hits OUT.bin [--cast-order auto|given|coherent] [--t-min T]]\n"
-                 "               [--paths QUERIES.bin --samples S [--continue] --results OUT.bin [--segments SEG.bin]]\n");
+                 "               [--paths QUERIES.bin --samples S [--continue] --results OUT.bin [--segments SEG.bin]\n"
+                 "                [--paths-order cost [--paths-probe P]] [--paths-keys KEYS.bin]]\n");
 }
 
 int main(int argc, char **argv) {
@@ -157,6 +164,9 @@ int main(int argc, char **argv) {
     std::string paths_in, paths_out, paths_seg;  // --paths QUERIES.bin, --results OUT.bin, --segments SEG.bin
     long paths_samples = 0;                    // --samples
     bool paths_continue = false;               // --continue
+    bool paths_cost = false;                   // --paths-order cost
+    long paths_probe = 0;                      // --paths-probe
+    std::string paths_keys;                    // --paths-keys KEYS.bin
     std::vector<int> devices;  // non-empty: a group
     int gather = RTX_GATHER_AUTO;
     bool group_opts = false;   // --gather / --tile-rows given
@@ -250,6 +260,11 @@ int main(int argc, char **argv) {
         else if (a == "--segments") paths_seg = next();
         else if (a == "--samples") paths_samples = std::atol(next());
         else if (a == "--continue") paths_continue = true;
+        else if (a == "--paths-order") {
+            if (std::string(next()) != "cost") usage();
+            paths_cost = true;
+        } else if (a == "--paths-probe") paths_probe = std::atol(next());
+        else if (a == "--paths-keys") paths_keys = next(), paths_cost = true;
         else if (a == "--t-min") cast_t_min = (float)std::atof(next());
         else if (a == "--cast-order") {
             const std::string m = next();
@@ -378,6 +393,12 @@ int main(int argc, char **argv) {
     }
     if (paths_in.empty() && (paths_continue || !paths_seg.empty() || paths_samples != 0)) {
         std::fprintf(stderr, "rtx_cli: --samples, --continue and --segments go with --paths\n");
+        return 2;
+    }
+    if ((paths_in.empty() && (paths_cost || paths_probe != 0)) || paths_probe < 0 || paths_probe > 0xffffffffl ||
+        (paths_probe != 0 && !paths_keys.empty())) {
+        std::fprintf(stderr, "rtx_cli: --paths-order, --paths-probe P >= 0 and --paths-keys go with --paths; "
+                             "--paths-probe goes without --paths-keys\n");
         return 2;
     }
     const bool adaptive = ad_samples != 0u;
@@ -511,11 +532,22 @@ int main(int argc, char **argv) {
             results.resize(queries.size());
             if (!raw.empty()) std::memcpy(results.data(), raw.data(), raw.size());
         }
-        std::vector<uint32_t> segs;
+        std::vector<uint32_t> segs, keys;
+        if (!paths_keys.empty()) {
+            if (!slurp(paths_keys, sizeof(uint32_t), raw) || raw.size() != queries.size() * sizeof(uint32_t)) {
+                std::fprintf(stderr, "rtx_cli: --paths-keys: cannot read %s as one uint32 per query\n",
+                             paths_keys.c_str());
+                return 1;
+            }
+            keys.resize(queries.size());
+            if (!raw.empty()) std::memcpy(keys.data(), raw.data(), raw.size());
+        }
         const uint32_t pflags = (paths_continue ? (uint32_t)RTX_PATHS_CONTINUE : 0u) |
                                 (cfg.lambert_guard ? (uint32_t)RTX_PATHS_LAMBERT_GUARD : 0u);
         const auto t0 = std::chrono::steady_clock::now();
-        if (!app.TracePaths(queries, (uint32_t)paths_samples, &results, pflags, cast_order, &segs)) {
+        if (!(paths_cost ? app.TracePathsKeyed(queries, (uint32_t)paths_samples, &results, pflags,
+                                               paths_keys.empty() ? nullptr : &keys, (uint32_t)paths_probe, &segs)
+                         : app.TracePaths(queries, (uint32_t)paths_samples, &results, pflags, cast_order, &segs))) {
             std::fprintf(stderr, "rtx_cli: --paths failed: %s\n", app.last_error().c_str());
             return 1;
         }
@@ -533,7 +565,9 @@ int main(int argc, char **argv) {
         std::printf("{\"paths\": {\"queries\": %zu, \"samples\": %ld, \"segments\": %llu, \"order\": \"%s\", "
                     "\"continued\": %s, \"ms\": %.3f}}\n",
                     queries.size(), paths_samples, total,
-                    app.PathsLastOrder() == RTX_CAST_ORDER_COHERENT ? "coherent" : "given",
+                    app.PathsLastOrder() == RTX_PATHS_ORDER_COST      ? "cost"
+                    : app.PathsLastOrder() == RTX_CAST_ORDER_COHERENT ? "coherent"
+                                                                      : "given",
                     paths_continue ? "true" : "false", ms);
         return 0;
     }

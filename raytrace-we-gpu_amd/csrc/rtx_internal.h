@@ -358,6 +358,13 @@ struct KPaths {
 // p.samples > 0, p.depth > 0.
 hipError_t launch_paths(const KPaths &p, const float4 *queries, const uint32_t *perm, float4 *results,
                         uint32_t *segments, hipStream_t stream);
+// The cost order (rtx_trace_paths_keyed): k_paths_cost_keys, then k_cast_prefix
+// and k_cast_scatter as they stand: scratch.perm becomes the order of the n
+// words of src by non-increasing min(word, 65535), a permutation of 0 .. n-1.
+// src is read only by the first pass, which copies its buckets to scratch.keys.
+hipError_t launch_paths_cost_order(const uint32_t *src, uint32_t n, const KCastScratch &scratch, hipStream_t stream);
+// k_paths_add_segments: segments[i] += probe_segs[i] for i < n.
+hipError_t launch_paths_add_segments(uint32_t *segments, const uint32_t *probe_segs, uint32_t n, hipStream_t stream);
 // k_feature_listed + k_feature_mask (rtx_mask_from_ids): ids is host memory
 // (1 <= n <= kFeatureIdsMax), listed a width * height byte scratch, *n_set
 // (device, zeroed here first) the number of set pixels.

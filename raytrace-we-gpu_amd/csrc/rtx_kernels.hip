@@ -4305,6 +4305,40 @@ __global__ void __launch_bounds__(kRB) k_paths(const KPaths P, const float4 *__r
     }
 }
 
+// ---- the cost order of path queries (rtx_trace_paths_keyed; rtx_paths.h) ------
+// k_cast_keys with paths_cost_bucket(src[i]) in the place of cast_key: src is
+// the caller's keys or the probe's segment counts, n words. A 2-sample probe
+// leaves a batch a few dozen distinct keys, the case the LDS table was written
+// for. keys[i] is written from src[i] here, so src may be the buffer the trace
+// that follows writes its segment counts to. k_cast_prefix and k_cast_scatter
+// then run as they stand: buckets ascend, so keys descend along perm.
+static_assert(kPathsCostBuckets == kCastBuckets, "the cost order sorts into rtx_cast_rays' buckets");
+__global__ void __launch_bounds__(kBlock) k_paths_cost_keys(const uint32_t *src, uint32_t n, uint32_t *keys,
+                                                            uint32_t *counts) {
+    __shared__ CastTable t;
+    cast_table_clear(t);
+    const uint32_t base = blockIdx.x * kCastChunk;
+    for (uint32_t k = 0; k < kCastPerThread; ++k) {
+        const uint32_t i = base + k * kBlock + threadIdx.x;
+        if ((uint64_t)base + k * kBlock + threadIdx.x >= n) continue;
+        const uint32_t key = paths_cost_bucket(src[i]);  // < kCastBuckets for every input
+        keys[i] = key;
+        uint32_t rank;
+        if (cast_table_add(t, key, rank) == kCastSlots) atomicAdd(&counts[key], 1u);
+    }
+    __syncthreads();
+    for (uint32_t s = threadIdx.x; s < kCastSlots; s += kBlock)
+        if (t.key[s] != kCastEmpty) atomicAdd(&counts[t.key[s]], t.cnt[s]);
+}
+// segments[i] += probe_segs[i]: a probed call's two phases as one count. One
+// lane per word on the exact grid.
+__global__ void __launch_bounds__(kBlock) k_paths_add_segments(uint32_t *__restrict__ segments,
+                                                               const uint32_t *__restrict__ probe_segs, uint32_t n) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (!paths_lane_live((uint64_t)blockIdx.x * kBlock + threadIdx.x, n)) return;
+    segments[i] += probe_segs[i];
+}
+
 // rtx_mask_from_ids, two passes (rtx_features.h): which pixels are listed, then
 // the Chebyshev growth and the number of set pixels (one atomic per wave that
 // has any). The id list travels as a kernel argument.
@@ -5020,6 +5054,25 @@ hipError_t launch_paths(const KPaths &p, const float4 *queries, const uint32_t *
     if (p.n == 0) return hipSuccess;
     if (p.samples == 0 || p.depth == 0) return hipErrorInvalidValue;  // (the loop's end needs both)
     hipLaunchKernelGGL(k_paths, dim3(paths_blocks(p.n, kRB)), dim3(kRB), 0, stream, p, queries, perm, results, segments);
+    return hipGetLastError();
+}
+
+hipError_t launch_paths_cost_order(const uint32_t *src, uint32_t n, const KCastScratch &scratch, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(scratch.counts, 0, kCastBuckets * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    const uint32_t blocks = ceil_div(n, kCastChunk);
+    hipLaunchKernelGGL(k_paths_cost_keys, dim3(blocks), dim3(kBlock), 0, stream, src, n, scratch.keys, scratch.counts);
+    hipLaunchKernelGGL(k_cast_prefix, dim3(1), dim3(kBlock), 0, stream, scratch.counts);
+    hipLaunchKernelGGL(k_cast_scatter, dim3(blocks), dim3(kBlock), 0, stream, scratch.keys, n, scratch.counts,
+                       scratch.perm);
+    return hipGetLastError();
+}
+
+hipError_t launch_paths_add_segments(uint32_t *segments, const uint32_t *probe_segs, uint32_t n, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_paths_add_segments, dim3(paths_blocks(n, kBlock)), dim3(kBlock), 0, stream, segments,
+                       probe_segs, n);
     return hipGetLastError();
 }
 

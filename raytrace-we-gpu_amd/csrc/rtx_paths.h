@@ -116,4 +116,45 @@ RTX_PATHS_HD uint64_t paths_query_offset(uint32_t i) { return (uint64_t)i * kPat
 RTX_PATHS_HD uint64_t paths_result_offset(uint32_t i) { return (uint64_t)i * kPathResultBytes; }
 RTX_PATHS_HD uint64_t paths_segment_offset(uint32_t i) { return (uint64_t)i * 4u; }
 
+// ---- rtx_trace_paths_keyed: the cost order -------------------------------------
+// Lane g of the one k_paths launch takes the g-th query in non-increasing order
+// of min(key, 65535): the longest queries first, so that a wave's 64 lanes
+// hold queries of similar length. The keys are the caller's (d_keys) or the
+// segment counts of the library's own probe, a first call of p samples. A
+// schedule and nothing else: every record is what the given order writes.
+constexpr uint32_t kPathsOrderCost = 3u;   // = RTX_PATHS_ORDER_COST (rtx_paths_last_order; never an `order` argument)
+constexpr uint32_t kPathsKeyMax = 65535u;  // keys above it sort with it
+constexpr uint32_t kPathsCostBuckets = kPathsKeyMax + 1u;  // = kCastBuckets (asserted where rtx_cast.h is in sight)
+
+// What rtx_trace_paths_keyed refuses before it looks at the context, in the
+// order it tests them (a null ctx comes before all of these).
+enum PathsKeyedArg : int {
+    kPathsKeyedArgOk = 0,
+    kPathsKeyedArgQueries,  // n > 0 with d_queries NULL
+    kPathsKeyedArgResults,  // n > 0 with d_results NULL
+    kPathsKeyedArgSamples,  // samples == 0
+    kPathsKeyedArgFlags,    // a bit outside kPathsFlagMask
+    kPathsKeyedArgProbe,    // d_keys given and probe != 0
+};
+RTX_PATHS_HD PathsKeyedArg paths_keyed_args(bool have_queries, bool have_results, uint32_t n, uint32_t samples,
+                                            uint32_t flags, bool have_keys, uint32_t probe) {
+    if (n != 0u && !have_queries) return kPathsKeyedArgQueries;
+    if (n != 0u && !have_results) return kPathsKeyedArgResults;
+    if (samples == 0u) return kPathsKeyedArgSamples;
+    if ((flags & ~kPathsFlagMask) != 0u) return kPathsKeyedArgFlags;
+    if (have_keys && probe != 0u) return kPathsKeyedArgProbe;
+    return kPathsKeyedArgOk;
+}
+// The probe's samples when the caller passes 0: the refine pre-pass's rule, 2,
+// or 1 for a world of more than 1,024 spheres after padding.
+RTX_PATHS_HD uint32_t paths_default_probe(uint32_t n_pad) { return n_pad > 1024u ? 1u : 2u; }
+// Whether a probed call of `samples` with probe p sorts at all: with nothing
+// left after the probe it is one plain launch in the given order.
+RTX_PATHS_HD bool paths_two_phase(uint32_t samples, uint32_t p) { return samples > p; }
+// The counting sort's bucket of a key: buckets ascend, keys descend. Below
+// kPathsCostBuckets for every input.
+RTX_PATHS_HD uint32_t paths_cost_bucket(uint32_t key) {
+    return kPathsKeyMax - (key < kPathsKeyMax ? key : kPathsKeyMax);
+}
+
 }  // namespace rtx

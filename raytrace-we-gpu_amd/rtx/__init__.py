@@ -61,6 +61,7 @@ RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("index", "<i4"), ("normal", "<f4", (3,)
 PATH_QUERY_DTYPE = np.dtype([("o", "<f4", (3,)), ("seed", "<f4"), ("d", "<f4", (3,)), ("tag", "<u4")])
 PATH_RESULT_DTYPE = np.dtype([("sum", "<f4", (3,)), ("seed", "<f4")])
 PATHS_LAMBERT_GUARD, PATHS_CONTINUE = 1, 2  # rtx_trace_paths flags (RTX_PATHS_*)
+PATHS_ORDER_COST = 3  # RTX_PATHS_ORDER_COST: rtx_paths_last_order after rtx_trace_paths_keyed sorted
 GATHER_MODES = {"auto": 0, "rccl": 1, "copy": 2}  # rtx_group_create (RTX_GATHER_*)
 GROUP_MAX = 64  # RTX_GROUP_MAX
 
@@ -190,6 +191,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_path_seed": (C.c_float, [u32, u32, u32]),
         "rtx_trace_paths": (C.c_int, [ctx, vp, u32, u32, u32, u32, vp, vp]),
         "rtx_paths_last_order": (C.c_int, [ctx]),
+        "rtx_trace_paths_keyed": (C.c_int, [ctx, vp, u32, u32, u32, vp, u32, vp, vp]),
+        "rtx_debug_paths_order": (C.c_int, [ctx, C.POINTER(u32), C.c_size_t]),
         "rtx_camera_set_aperture": (C.c_int, [C.POINTER(rtx_frame), C.c_float]),
         "rtx_part_rows": (u32, [u32, u32, u32, u32]),
         "rtx_deinterleave_rows": (C.c_int, [ctx, vp, u32, u32, u32, u32, vp]),
@@ -259,6 +262,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     optional |= {"rtx_cast_rays", "rtx_cast_last_order"}         # ... probe "rtx_cast_rays"
     optional |= {"rtx_path_seed"}                                # ... probe "rtx_path_seed"
     optional |= {"rtx_trace_paths", "rtx_paths_last_order"}      # ... probe "rtx_trace_paths"
+    optional |= {"rtx_trace_paths_keyed", "rtx_debug_paths_order"}  # ... probe "rtx_trace_paths_keyed"
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -906,12 +910,98 @@ class Context:
         return results, d_seg
 
     def paths_last_order(self) -> str:
-        """"given" or "coherent": what the last trace_paths ran (rtx_paths_last_order)."""
+        """"given" or "coherent": what the last trace_paths ran; "cost" after a
+        trace_paths_keyed that sorted (rtx_paths_last_order)."""
         code = self._lib.rtx_paths_last_order(self._h)
+        if code == PATHS_ORDER_COST:
+            return "cost"
         for name, v in CAST_ORDERS.items():
             if v == code:
                 return name
         raise RtxError(f"rtx_paths_last_order returned {code}")
+
+    def trace_paths_keyed(self, queries, samples: int, keys=None, probe: int = 0, flags: int = 0, results=None,
+                          segments=False, cont: bool = False, n: Optional[int] = None):
+        """trace_paths in cost order, the longest queries first
+        (rtx_trace_paths_keyed): the records are trace_paths(order="given")'s,
+        bit for bit; only the schedule differs. Returns (results, segments).
+
+        keys: None — the library probes (`probe` samples in the given order,
+        0: its default; their segment counts are the keys) — or n uint32, one
+        per query, larger for longer (`probe` must then be 0). With numpy
+        queries keys is a numpy array; with device queries a device buffer,
+        which may be the `segments` buffer itself (the keys are read before
+        the trace writes it). queries, results, segments, cont, n: as
+        trace_paths takes them."""
+        flags = int(flags) | (PATHS_CONTINUE if cont else 0)
+        if not hasattr(self._lib, "rtx_trace_paths_keyed"):
+            raise RtxError("this librtx has no rtx_trace_paths_keyed")
+        if isinstance(queries, np.ndarray):
+            host = np.ascontiguousarray(queries)
+            if host.dtype != PATH_QUERY_DTYPE:
+                host = np.ascontiguousarray(host, np.float32).reshape(-1, 8)
+            n = host.shape[0]
+            start = None
+            if flags & PATHS_CONTINUE:
+                if not isinstance(results, np.ndarray):
+                    raise RtxError("Context.trace_paths_keyed: continuing numpy queries needs numpy results")
+                start = np.ascontiguousarray(results)
+                if start.dtype != PATH_RESULT_DTYPE:
+                    start = np.ascontiguousarray(start, np.float32).reshape(-1, 4)
+                if start.shape[0] != n:
+                    raise RtxError("Context.trace_paths_keyed: results and queries differ in length")
+            elif results is not None:
+                raise RtxError("Context.trace_paths_keyed: numpy queries take results only to continue from")
+            host_keys = None
+            if keys is not None:
+                if not isinstance(keys, np.ndarray):
+                    raise RtxError("Context.trace_paths_keyed: numpy queries take numpy keys")
+                host_keys = np.ascontiguousarray(keys, np.uint32).reshape(-1)
+                if host_keys.shape[0] != n:
+                    raise RtxError("Context.trace_paths_keyed: keys and queries differ in length")
+            d_q = self.alloc((max(n, 1),), PATH_QUERY_DTYPE)
+            d_r = self.alloc((max(n, 1),), PATH_RESULT_DTYPE)
+            d_s = self.alloc((max(n, 1),), np.uint32) if segments is True else None
+            d_k = self.alloc((max(n, 1),), np.uint32) if host_keys is not None else None
+            try:
+                if n:
+                    for d, h, size in ((d_q, host, 32), (d_r, start, 16), (d_k, host_keys, 4)):
+                        if h is not None:
+                            _check(self._lib.rtx_copy_to_device(self._h, C.c_void_p(d.ptr), h.ctypes.data, size * n),
+                                   "rtx_copy_to_device", self._lib)
+                self.trace_paths_keyed(d_q, samples, d_k, probe, flags, d_r, d_s if d_s is not None else segments,
+                                       False, n)
+                return d_r.numpy()[:n], (d_s.numpy()[:n] if d_s is not None else (None if segments is False else segments))
+            finally:
+                for d in (d_q, d_r, d_s, d_k):
+                    if d is not None:
+                        d.free()
+        if n is None:
+            if not hasattr(queries, "shape"):
+                raise RtxError("Context.trace_paths_keyed: n is needed with a bare pointer")
+            n = int(queries.shape[0])
+        if results is None:
+            if flags & PATHS_CONTINUE:
+                raise RtxError("Context.trace_paths_keyed: continuing needs the results to continue from")
+            results = self.alloc((max(n, 1),), PATH_RESULT_DTYPE)
+        d_seg = self.alloc((max(n, 1),), np.uint32) if segments is True else (None if segments is False else segments)
+        _check(self._lib.rtx_trace_paths_keyed(self._h, C.c_void_p(_dev_ptr(queries)), n, samples, flags,
+                                               C.c_void_p(_dev_ptr(keys)), probe, C.c_void_p(_dev_ptr(results)),
+                                               C.c_void_p(_dev_ptr(d_seg))),
+               "rtx_trace_paths_keyed", self._lib)
+        self._paths_keyed_n = n
+        return results, d_seg
+
+    def paths_order(self, n: Optional[int] = None) -> np.ndarray:
+        """The permutation the last trace_paths_keyed ran, one uint32 per
+        query: lane g took query perm[g] (rtx_debug_paths_order; a wait). n:
+        that call's number of queries (None: what this object's last
+        trace_paths_keyed had). RtxError (RTX_ERR_STATE, -3) when the last
+        path call did not sort by cost or the scratch has been reused since."""
+        perm = np.empty(int(getattr(self, "_paths_keyed_n", 0) if n is None else n), np.uint32)
+        _check(self._lib.rtx_debug_paths_order(self._h, perm.ctypes.data_as(C.POINTER(C.c_uint32)), perm.nbytes),
+               "rtx_debug_paths_order", self._lib)
+        return perm
 
     def deinterleave(self, d_gathered: int, width: int, height: int, tile_rows: int, nparts: int,
                      d_image: int):
