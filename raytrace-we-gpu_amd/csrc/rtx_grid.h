@@ -310,6 +310,24 @@ RTX_GD int grid_share_mark(uint32_t start, uint32_t n, uint32_t base, uint32_t n
     return (int)(start > base ? start - base : 0u);
 }
 
+// The prefix itself, from ballots of the bits of n (n <= kGridMaxSteps < 64:
+// 6 bits): bits(b) is the mask of the lanes whose n has bit b, below(m) the
+// count of m's lanes before this one, any_high whether some lane's n is 8 or
+// more. Bits 3..5 are looked at only then: in every other wave they are 0 in
+// every lane and add nothing to start or total. The kernel passes ballots and
+// v_mbcnt, the CPU check (tests/walk_prefix_check.cpp) masks of an array.
+template <typename Bits, typename Below>
+RTX_GD void grid_item_prefix(Bits bits, bool any_high, Below below, uint32_t &start, uint32_t &total) {
+    start = 0u, total = 0u;
+    auto bit = [&](uint32_t b) {
+        const uint64_t mb = bits(b);
+        start += below(mb) << b;
+        total += (uint32_t)__builtin_popcountll(mb) << b;
+    };
+    bit(0u), bit(1u), bit(2u);
+    if (any_high) bit(3u), bit(4u), bit(5u);
+}
+
 // Host: the geometry of a layer grid over `m` spheres sph[4 j] = (cx, cy,
 // cz, r) (every cy equal: y0) and, for each, every cell its disc of radius
 // rho_j + kGridFat meets: add(cell, j). Returns false (no grid) past

@@ -127,14 +127,18 @@ __device__ __forceinline__ uint32_t lane_here() {
 // INVARIANT: to the compiler `v` is an ordinary per-lane value, so every copy,
 // split or spill of it that the compiler inserts obeys EXEC. The words are
 // kept only as long as each such copy runs with the lanes that hold words
-// (0..3 today) enabled. That holds in k_render's persistent loop because `v`
+// (0..4 today) enabled. That holds in k_render's persistent loop because `v`
 // is read and written at the loop's top level and in refill only, where every
 // branch condition is wave-uniform at run time and no lane has left the loop
 // (the loop's exits are wave-uniform), so EXEC is full. The register is live
 // across the per-lane regions (`if (L.active)` ...) too: a copy or spill the
 // allocator placed inside one would lose the words of idle lanes. It places
 // none today (the C2, refine and adaptive instances spill one constant pair,
-// sincos_rt's, and move `v` at the top level only); a change that raises their register pressure
+// sincos_rt's, and move `v` at the top level and, since word 4 is written in
+// the lane-mode arm alone, once in each arm of the loop's lane-mode / tail
+// branch: its condition is wave-uniform, so EXEC inside an arm is the top
+// level's, full; rechecked in the assembly of the C2, refine and adaptive
+// instances, RESULTS.md S16); a change that raises their register pressure
 // has to recheck that in the assembly (`make asm`). A lost word would show as
 // a wrong queue slot (the bit-exact frame tests) or, for the heartbeat, as
 // valve timing only.
@@ -706,12 +710,23 @@ struct GiLayout {
 // kPos: ld takes the list position (clamped to n - 1) instead of the scene
 // index (the culled layout keeps a copy of the spheres in position order, so
 // the data load and the index load are independent).
-template <typename Ld, typename Gi = GiIdentity, bool kPos = false>
+// kLean (the small-scene scan's resolve, hit_world_pre_ld with a layout or a
+// grid allowed): the same candidates in the same order, with less per round.
+// The loop's condition is the ballot of next()'s own compare, carried as a
+// wave-uniform flag (the ballot of the carried `live` was a v_cndmask and a
+// v_cmp per round); the list length is clamped once, not the row of every
+// read (j <= m, and the next entry is read only by the lanes that advance);
+// a lane without a candidate decodes whatever its column held (ffs of an
+// empty mask is 0: the position it makes is clamped before any use, as
+// before). C2: -224 M VALU per frame (RESULTS.md S16). The large-scene
+// kernels keep the loop they had.
+template <typename Ld, typename Gi = GiIdentity, bool kPos = false, bool kLean = false>
 __device__ __forceinline__ bool resolve_pre_t(Ld ld, uint32_t n, const uint32_t *list, uint32_t m, f3 o, f3 d,
                                               float a, float inv_a, float t_min, float &best, int &idx,
                                               uint32_t cap = (uint32_t)kCand, Gi gi = Gi()) {
     bool ok = true;
     uint32_t j = 0;
+    if constexpr (kLean) m = min(m, cap);
     uint32_t e = list[threadIdx.x];  // entry 0 (unused when m == 0)
     RTX_DIAG_ADD(4, (uint32_t)__popcll(__ballot(m != 0u)));
 #if RTX_DIAG_PROF
@@ -724,24 +739,35 @@ __device__ __forceinline__ bool resolve_pre_t(Ld ld, uint32_t n, const uint32_t 
     }
 #endif
     // next candidate: sphere index i (live = the lane has one), then advance
-    uint32_t pos = 0;  // (kPos) the position of the candidate next() returns
+    uint32_t pos = 0;   // (kPos) the position of the candidate next() returns
+    bool more = false;  // (kLean) some lane of the wave has one: wave-uniform
     auto next = [&](uint32_t &i, bool &live) {
         live = j < m;
-        pos = (e & 0xffffffu) + (uint32_t)__builtin_ctz(live ? (e >> 24) : 1u);
+        if constexpr (kLean) {
+            more = __ballot(live) != 0ull;
+            pos = (e & 0xffffffu) + (uint32_t)(__builtin_ffs((int)(e >> 24)) - 1);
+        } else {
+            pos = (e & 0xffffffu) + (uint32_t)__builtin_ctz(live ? (e >> 24) : 1u);
+        }
         if constexpr (kPos) pos = min(pos, n - 1u);
         i = gi(pos);
         e &= e - (1u << 24);  // drop that candidate from the mask
         const bool adv = live && (e >> 24) == 0u;
         j += adv ? 1u : 0u;
-        const uint32_t nx = list[min(j, cap) * kRB + threadIdx.x];
-        e = adv ? nx : e;
+        if constexpr (kLean) {
+            if (adv) e = list[j * kRB + threadIdx.x];
+        } else {
+            const uint32_t nx = list[min(j, cap) * kRB + threadIdx.x];
+            e = adv ? nx : e;
+        }
     };
     uint32_t i0;
     bool l0;
+    uint64_t key = hit_key(best, idx);
     next(i0, l0);
     float4 v0 = kPos ? ld(pos) : ld(min(i0, n - 1u));
-    uint64_t key = hit_key(best, idx);
-    while (__ballot(l0) != 0ull) {
+    bool m0 = more;
+    while (kLean ? m0 : __ballot(l0) != 0ull) {
         RTX_DIAG_ADD(2, 1u);
         uint32_t i1;
         bool l1;
@@ -751,6 +777,7 @@ __device__ __forceinline__ bool resolve_pre_t(Ld ld, uint32_t n, const uint32_t 
         i0 = i1;
         l0 = l1;
         v0 = v1;
+        m0 = more;
     }
     key_hit(key, best, idx);
     return ok;
@@ -1023,13 +1050,12 @@ __device__ __forceinline__ uint64_t grid_wave_mask(const KScene &S, f3 o, f3 d, 
     const uint32_t nact = (uint32_t)__popcll(act), slot = below(act);
     // the items before this lane's and the wave's total: n <= kGridMaxSteps < 64, one ballot per bit
     static_assert(kGridMaxSteps < 64u, "grid_wave_mask: item counts of 6 bits");
-    uint32_t start = 0, total = 0;
-#pragma unroll
-    for (uint32_t b = 0; b < 6u; ++b) {
-        const uint64_t mb = __ballot(((R.n >> b) & 1u) != 0u);
-        start += below(mb) << b;
-        total += (uint32_t)__popcll(mb) << b;
-    }
+    // (bits 3..5 only in a wave where some lane has 8 items or more: one
+    // compare more, 15 VALU fewer in every other wave; C2 -215 M VALU per
+    // frame, RESULTS.md S16)
+    uint32_t start, total;
+    grid_item_prefix([&](uint32_t b) { return (uint64_t)__ballot(((R.n >> b) & 1u) != 0u); },
+                     __ballot(R.n >= 8u) != 0ull, [](uint64_t m) { return below(m); }, start, total);
     const uint32_t pack = start | (R.c0 << 12) | (R.zmajor << 24);  // start <= 63 * 48, c0 < kGridMaxCells
     static_assert(63u * kGridMaxSteps < 4096u && kGridMaxCells <= 4096u, "grid_wave_mask: packed owner word");
     const uint32_t last_cell = G.nx * G.nz - 1u;
@@ -1157,9 +1183,11 @@ __device__ __forceinline__ int hit_world_pre_ld(const KScene &S, Ld ld, f3 o, f3
         b = scan_prefilter<kPF, kTile>(pre, b, end, T, S, list, cnt, pack, lds_pr, gm);
         RTX_DIAG_HW(1);
         if constexpr (!kLay)
-            ok = resolve_pre_t(ld, S.n, list, cnt, o, d, a, inv_a, t_min, best, idx, cand_of<kPF>()) && ok;
+            ok = resolve_pre_t<Ld, GiIdentity, false, false>(ld, S.n, list, cnt, o, d, a, inv_a, t_min, best, idx,
+                                                             cand_of<kPF>()) && ok;
         else
-            ok = resolve_pre_t(ld, S.n, list, cnt, o, d, a, inv_a, t_min, best, idx, cand_of<kPF>(), gi) && ok;
+            ok = resolve_pre_t<Ld, GiLayout<Map>, false, true>(ld, S.n, list, cnt, o, d, a, inv_a, t_min, best, idx,
+                                                                cand_of<kPF>(), gi) && ok;
         RTX_DIAG_HW(2);
         if (b < end) continue;
         if (end == nblk && b0 != 0u) {  // wrap round to the start
@@ -2851,7 +2879,8 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
     const uint32_t owned = qlen - (P.trace_ext != 0u ? H.k1 : 0u);
     uint32_t written = 0;  // pixels this wave wrote since it last reported
     // the wave's last heartbeat (beat); the small-scene instances' cold words
-    // (WaveWords): 0, 1 the heartbeat, 2, 3 refill's private run
+    // (WaveWords): 0, 1 the heartbeat, 2, 3 refill's private run, 4 the
+    // priority site's iteration count
     std::conditional_t<kLate, WaveWords, unsigned long long> cold{};
     Diag D;
     D.begin();
@@ -2950,10 +2979,27 @@ __global__ void RTX_RENDER_BOUNDS_T2(kPF, kLin) k_render(const KParams P) {
         // so its time per segment is not stretched by the SIMD's other waves
         {
             const auto &K = params_at<kLate>(P);  // the priority's site: dyn_level's inputs, or the hot slots
-            if (K.cost_in) {
-                set_prio(dyn_level<kRefine>(K, L, dyn_m));
-            } else {
-                set_prio(__ballot(L.active && L.slot < kh + K.prio_slots) != 0ull ? K.prio_hot : 0u);
+            // A whole-frame launch of the persistent small-scene render looks
+            // at its priority every 4th iteration (a wave-uniform count in
+            // word 4 of `cold`): the dynamic priority does not move the R = 1
+            // frame and dyn_level is 28 VALU. Row parts, where
+            // it pays, look every iteration as before. Timing only: between
+            // looks a wave keeps the priority it had, so one that comes back
+            // from a tail iteration (which ends at priority 0) runs up to
+            // three lane-mode iterations at 0 before it looks again; the
+            // whole frame measured no slower for it (RESULTS.md S16).
+            bool look = true;
+            if constexpr (kLate && kPersist) {
+                const uint32_t tick = cold.template get<4>();
+                cold.template set<4>(tick + 1u);
+                look = K.nparts != 1u || (tick & 3u) == 0u;
+            }
+            if (look) {
+                if (K.cost_in) {
+                    set_prio(dyn_level<kRefine>(K, L, dyn_m));
+                } else {
+                    set_prio(__ballot(L.active && L.slot < kh + K.prio_slots) != 0ull ? K.prio_hot : 0u);
+                }
             }
         }
         bool promoted = false;

@@ -12,7 +12,11 @@ depth 1 (a persistent kernel's main loop) and ld@2+ / st@2+ in the loops
 inside it, by the assembler's own "Loop Header: Depth=" block comments.
 Static counts: what executes per iteration is for the counters to say.
 
-    python tools/asm_by_source.py [--kernel SUBSTR] [--all] [--check make-asm.s] [--keep out.s | --asm in.s] [-DRTX_...]
+    python tools/asm_by_source.py [--kernel SUBSTR] [--all | --loops] [--check make-asm.s] [--keep out.s | --asm in.s] [-DRTX_...]
+
+--loops: instead of the table by function, one row per loop of the kernel
+(its header's label and depth): the static VALU, packed VALU, SALU, LDS, VMEM
+and SMEM counts of its own body and the source lines most VALU come from.
 
 --check: the instruction stream (everything but directives, labels and
 comments) must equal that of the given `make asm` output.
@@ -102,6 +106,9 @@ ap.add_argument("--all", action="store_true", help="a row for every function, no
 ap.add_argument("--check")
 ap.add_argument("--keep")
 ap.add_argument("--asm", help="read this -gline-tables-only assembly instead of compiling")
+ap.add_argument("--loops", action="store_true",
+                help="per loop header of the kernel: depth, VALU, packed VALU, SALU, LDS, VMEM, SMEM of its own "
+                     "body and the source lines most of its VALU come from")
 a, extra = ap.parse_known_args()
 
 tmp = None
@@ -186,6 +193,63 @@ for l in lines[start + 1:end]:
         r["scratch_st"] += 1
         r["st@1"] += depth == 1
         r["st@2+"] += depth >= 2
+
+if a.loops:
+    # Static body of every loop of the kernel: the instructions of the blocks
+    # whose innermost loop it is (an inner loop's blocks count for the inner
+    # loop alone), by the assembler's block comments; and the source lines
+    # (function:line, by VALU count) they come from.
+    LCOLS = ["valu", "pk_valu", "salu", "lds", "vmem", "smem"]
+    loops, order, cur_loop, cur_src, label = {}, [], None, "?", None
+    for l in lines[start + 1:end]:
+        m = re.match(r"\s*\.loc\s+(\d+)\s+(\d+)", l)
+        if m:
+            cur_src = f"{owner(int(m.group(1)), int(m.group(2)))}:{m.group(2)}"
+            continue
+        m = re.match(r"\s*\.L(BB\w+):", l)
+        if m:
+            label, cur_loop = m.group(1), None
+        elif re.match(r"\s*; %bb\.\d+:", l):
+            label, cur_loop = None, None
+        m = re.search(r"in Loop: Header=(\S+) Depth=(\d+)", l)
+        if m:
+            cur_loop = m.group(1)
+        m = re.search(r"=>\s*This (?:Inner )?Loop Header: Depth=(\d+)", l)
+        if m and label:
+            cur_loop = label
+            if label not in loops:
+                order.append(label)
+            loops.setdefault(label, dict.fromkeys(LCOLS, 0) | {"src": {}})["depth"] = int(m.group(1))
+        t = instruction(l)
+        if t is None or cur_loop is None:
+            continue
+        if cur_loop not in loops:
+            order.append(cur_loop)
+        r = loops.setdefault(cur_loop, dict.fromkeys(LCOLS, 0) | {"src": {}, "depth": 0})
+        op = t.split()[0]
+        if op.startswith("v_"):
+            r["valu"] += 1
+            r["pk_valu"] += op.startswith("v_pk_")
+            r["src"][cur_src] = r["src"].get(cur_src, 0) + 1
+        elif op.startswith(("s_load_", "s_buffer_load_")):
+            r["smem"] += 1
+        elif op.startswith("s_"):
+            r["salu"] += not op.startswith(NOT_SALU)
+        elif op.startswith("ds_"):
+            r["lds"] += 1
+        elif op.startswith(("global_", "buffer_", "flat_", "scratch_")):
+            r["vmem"] += 1
+    print(f"# {lines[start].split(':')[0]}: loop bodies (static; inner loops excluded)")
+    print(f"{'header':12s} {'depth':>5s} " + " ".join(f"{c:>8s}" for c in LCOLS) + "  top source lines (VALU)")
+    for h in order:
+        r = loops[h]
+        top = sorted(r["src"].items(), key=lambda kv: -kv[1])[:4]
+        print(f"{h:12s} {r['depth']:>5d} " + " ".join(f"{r[c]:>8d}" for c in LCOLS) + "  " +
+              ", ".join(f"{s} ({n})" for s, n in top))
+    if tmp:
+        os.remove(asm)
+        os.rmdir(tmp)
+    sys.exit(0)
 
 table, used = [], set()
 for g in GROUPS:
