@@ -40,6 +40,13 @@ extern "C" {
 
 #define RTX_VERSION 145 /* 1.4.5 */
 /* ABI notes.
+ *  1.4.5 (later builds, no version bump): rtx_trace_film (rtx_film_query,
+ *         rtx_film_lens_query, RTX_FILM_LENS), rtx_film_last_order and the
+ *         host generators rtx_film_from_frame and rtx_film_camera
+ *         (RTX_FILM_EQUIRECT, RTX_FILM_FISHEYE): path queries whose every
+ *         sample is jittered over a film footprint of the query's own, and
+ *         goes through its lens; purely additive again: probe for the symbol
+ *         (dlsym "rtx_trace_film").
  *  1.4.5 (later builds, no version bump): rtx_trace_paths_keyed
  *         (RTX_PATHS_ORDER_COST) and rtx_debug_paths_order (path queries in
  *         cost order, by the caller's keys or the library's own probe; the
@@ -884,6 +891,106 @@ RTX_API int rtx_trace_paths_keyed(rtx_ctx *ctx, const void *d_queries, uint32_t 
                                   uint32_t flags, const void *d_keys, uint32_t probe,
                                   void *d_results, void *d_segments);
 RTX_API int rtx_debug_paths_order(rtx_ctx *ctx, uint32_t *host_perm, size_t bytes);
+/* ---- film queries: path queries with a per-sample film footprint ---------------
+ * (later builds, no version bump: probe with dlsym "rtx_trace_film").
+ * rtx_trace_paths starts every sample of a query on one fixed ray. A film
+ * query is a pixel of a frame of its own: the record carries that frame's
+ * origin o, lower-left corner L, horizontal and vertical rows H and V, the
+ * pixel's coordinates (fx, fy) and the seed of its RNG chain; img_w and img_h
+ * are the call's. Every sample starts as the render's does, in fp32, in this
+ * order, without fused multiply-adds:
+ *   hash2(seed) -> h0, _ ;  u = (fx + h0 * 1.1f) / (img_w - 1.0f)
+ *   hash2(seed) -> _, g1 ;  v = (fy + g1 * 1.1f) / (img_h - 1.0f)
+ *   o' = o ;  d = ((L + u * H) + v * V) - o
+ *   with RTX_FILM_LENS and lens_r > 0:
+ *     rd = lens_r * random_in_unit_disk(seed); off = rd.x * lens_u + rd.y * lens_v;
+ *     o' = o' + off; d = d - off
+ * and is from there a sample of rtx_trace_paths along (o', d).
+ * The contract: query i with fx = (float)x, fy = (float)y (x, y < 2^24) and
+ * seed = rtx_path_seed(x, y, f) gives, bit for bit (NaN sums included), pixel
+ * (x, y) of rtx_render_sum in the frame {origin o, lower_left L, horizontal H,
+ * vertical V, img_w, img_h, lens_u = (lens_u, lens_r), lens_v, chain RNG,
+ * frame_index f}, world.spp = samples, RTX_FRAME_LAMBERT_GUARD set iff
+ * RTX_PATHS_LAMBERT_GUARD is. So it renders any subset of a frame's pixels, in
+ * any order, at the cost of those pixels; and with one frame per record it
+ * renders cameras that are no pinhole:
+ *   H = V = 0 without a lens is rtx_trace_paths' query (o, fl(L - o), seed).
+ *   The unit form: fx = fy = 0 with img_w = img_h = 2 gives u = h0 * 1.1f and
+ *   v = g1 * 1.1f exactly; L is then the footprint's corner and H, V its
+ *   edges divided by 1.1 (rtx_film_camera writes such records).
+ * img_w, img_h, fx, fy and the vectors are not checked (rtx_set_frame checks
+ * none either): whatever the arithmetic gives is the answer.
+ * d_queries: n rtx_film_query (64 B), or with RTX_FILM_LENS n
+ * rtx_film_lens_query (96 B; a record with lens_r <= 0 has no lens, record by
+ * record). d_results (n rtx_path_result), d_segments (n uint32, or NULL),
+ * RTX_PATHS_CONTINUE and RTX_PATHS_LAMBERT_GUARD: as in rtx_trace_paths.
+ * Device pointers; asynchronous on the context stream; needs no frame; touches
+ * no stats, framebuffer, chain state or cost map. `tag` is the caller's.
+ * `order` is a schedule and nothing else: RTX_CAST_ORDER_AUTO and _GIVEN run
+ * lane g on query g; RTX_PATHS_ORDER_COST is rtx_trace_paths_keyed's probe (the
+ * first 2 samples, or 1 for a world of more than 1,024 spheres after padding,
+ * in the given order; the rest in non-increasing order of their segment
+ * counts; with samples <= that probe, one plain launch). RTX_CAST_ORDER_COHERENT
+ * is refused: its key pass reads a direction where a film record holds L.
+ * rtx_film_last_order: GIVEN or RTX_PATHS_ORDER_COST, what the last call ran;
+ * GIVEN before any call. A film call that sorts reuses the scratch of
+ * rtx_debug_paths_order, which then returns RTX_ERR_STATE.
+ * The image of a batch: d_results is a row of linear sums, so
+ * rtx_fold_frames(ctx, zeroed accum, d_results, 1, n, n, samples, d_image)
+ * gives toGamma(sum / samples).
+ * RTX_ERR_INVALID, before any HIP call and before the context is looked at,
+ * first failure first: a null ctx; n > 0 with d_queries NULL, then with
+ * d_results NULL; samples == 0; unknown flag bits; COHERENT or an unknown
+ * order. RTX_ERR_STATE: no world. RTX_ERR_INVALID once the world is known: its
+ * depth is 0, or samples * depth >= 2^32. n == 0 returns RTX_OK and launches
+ * nothing. */
+typedef struct rtx_film_query      { float o[3], seed, lower_left[3]; uint32_t tag;
+                                     float horizontal[3], fx, vertical[3], fy; } rtx_film_query;       /* 64 B */
+typedef struct rtx_film_lens_query { rtx_film_query q; float lens_u[3], lens_r, lens_v[3];
+                                     uint32_t reserved; } rtx_film_lens_query;                          /* 96 B */
+enum { RTX_FILM_LENS = 4 };   /* with RTX_PATHS_LAMBERT_GUARD = 1 and RTX_PATHS_CONTINUE = 2 */
+RTX_API int rtx_trace_film(rtx_ctx *ctx, const void *d_queries, uint32_t n, uint32_t samples,
+                           float img_w, float img_h, uint32_t flags, uint32_t order,
+                           void *d_results, void *d_segments);
+RTX_API int rtx_film_last_order(rtx_ctx *ctx);   /* GIVEN or RTX_PATHS_ORDER_COST: what the last call ran */
+/* Host, no GPU, no context: the film records of the n listed pixels (xs[i],
+ * ys[i]) of a frame, values copied, fx = (float)x, fy = (float)y, seed =
+ * rtx_path_seed(x, y, frame_index), tag 0; *img_w and *img_h (either may be
+ * NULL) receive the frame's. lens != 0 writes rtx_film_lens_query records with
+ * the frame's lens_u, lens radius and lens_v. RTX_ERR_INVALID: a null frame or
+ * (n > 0) list or buffer; a frame with rng_mode RTX_RNG_PER_SAMPLE; lens == 0
+ * for a frame whose lens radius is > 0; a pixel outside width x height. The
+ * frame's own frame_index and flags are not read. */
+RTX_API int rtx_film_from_frame(const rtx_frame *frame, const uint32_t *xs, const uint32_t *ys, uint32_t n,
+                                uint32_t frame_index, void *host_queries, int lens,
+                                float *img_w, float *img_h);
+/* Host, no GPU, no context: width * height unit-form records (trace them with
+ * img_w = img_h = 2), one per pixel, record y * width + x, row 0 at the
+ * bottom, of a camera at `from` looking at `at`: forward w = normalize(at -
+ * from), right u = normalize(cross(w, vup)), up v = cross(u, w). With c(x, y)
+ * the model's unit direction at pixel corner (x, y), in double: L = o + c(x,
+ * y), H = (c(x + 1, y) - c(x, y)) / 1.1, V = (c(x, y + 1) - c(x, y)) / 1.1,
+ * each rounded once; seed = rtx_path_seed(x, y, frame_index).
+ *   RTX_FILM_EQUIRECT  longitude (x / width - 0.5) * 2 pi over the width (0:
+ *       forward, positive to the right), latitude (y / height - 0.5) * pi over
+ *       the height; c = cos(lat) sin(lon) u + sin(lat) v + cos(lat) cos(lon) w.
+ *       fov_deg is unused.
+ *   RTX_FILM_FISHEYE   equidistant, fov_deg (0 < fov <= 360) across the
+ *       shorter side: p = ((x, y) - (width, height) / 2) / (min(width, height)
+ *       / 2), r = |p|, theta = r * fov / 2, c = sin(theta) (p.x u + p.y v) / r
+ *       + cos(theta) w. A pixel with a corner outside the image circle (r > 1)
+ *       gets a zero direction (L = o, H = V = 0): every root of such a ray
+ *       is NaN, each sample ends black at the world's depth, and the query
+ *       returns the sum (0, 0, 0) with `depth` segments per sample — black
+ *       in the image (an empty world has no root: there the sky colour of a
+ *       zero direction is NaN).
+ * RTX_ERR_INVALID: a null pointer, an unknown model, width or height 0 or
+ * width * height >= 2^32, a fisheye fov outside (0, 360], from == at or vup
+ * parallel to the view direction. */
+enum { RTX_FILM_EQUIRECT = 0, RTX_FILM_FISHEYE = 1 };
+RTX_API int rtx_film_camera(int model, const float from[3], const float at[3], const float vup[3],
+                            float fov_deg, uint32_t width, uint32_t height, uint32_t frame_index,
+                            rtx_film_query *host_queries);
 /* Device pointer of the chain state (width*height float4; a part state: its
  * rows * width), NULL if none. */
 RTX_API void *rtx_refine_state(rtx_ctx *ctx);

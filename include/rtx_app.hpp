@@ -182,6 +182,20 @@ public:
     // RTX_CAST_ORDER_GIVEN or _COHERENT: what the last TracePaths ran; RTX_PATHS_ORDER_COST
     // after a TracePathsKeyed that sorted (rtx_paths_last_order).
     int PathsLastOrder() const;
+    // Film queries (rtx_trace_film): `n` records at `queries` — rtx_film_query,
+    // or with RTX_FILM_LENS in `flags` rtx_film_lens_query — each a pixel (fx,
+    // fy) of the frame it states, `samples` jittered samples each, img_w and
+    // img_h the call's (2, 2 for the unit-form records of rtx_film_camera).
+    // results, flags (RTX_PATHS_*), segments: as in TracePaths. order:
+    // RTX_CAST_ORDER_AUTO, _GIVEN or RTX_PATHS_ORDER_COST. Synchronous.
+    bool TraceFilm(const void *queries, size_t n, uint32_t samples, float img_w, float img_h,
+                   std::vector<rtx_path_result> *results, uint32_t flags = 0, int order = RTX_CAST_ORDER_AUTO,
+                   std::vector<uint32_t> *segments = nullptr);
+    // RTX_CAST_ORDER_GIVEN or RTX_PATHS_ORDER_COST: what the last TraceFilm ran (rtx_film_last_order).
+    int FilmLastOrder() const;
+    // The image of a film batch: rgba[4 * i ..] = toGamma(results[i].sum /
+    // samples), alpha 1 (rtx_fold_frames on a zeroed accumulator).
+    bool FilmImage(const std::vector<rtx_path_result> &results, uint32_t samples, std::vector<float> *rgba);
     // Click to focus: picks the pixel, takes the hit's plane depth
     // dot(p - cam_pos, normalize(cam_look_at - cam_pos)) as the focus distance,
     // rebuilds the frame through rtx_camera_look_at with it and sets the thin

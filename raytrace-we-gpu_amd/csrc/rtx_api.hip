@@ -19,6 +19,7 @@
 #include "../../include/rtx.h"
 #include "rtx_internal.h"
 #include "rtx_layout.h"
+#include "rtx_film.h"
 #include "rtx_paths.h"
 #include "rtx_prefilter.h"
 
@@ -145,6 +146,7 @@ struct rtx_ctx {
     size_t cast_rays = 0;
     int cast_last = RTX_CAST_ORDER_GIVEN;
     int paths_last = RTX_CAST_ORDER_GIVEN;  // rtx_trace_paths: the order its last call ran
+    int film_last = RTX_CAST_ORDER_GIVEN;   // rtx_trace_film: the order its last call ran
     // rtx_trace_paths_keyed: the probe's segment counts (paths_probe_cap words,
     // grown on demand; its own buffer, so d_cast's size rule stays), and
     // whether d_cast's perm still holds the cost order of paths_perm_n queries
@@ -2165,6 +2167,100 @@ int rtx_debug_paths_order(rtx_ctx *c, uint32_t *host_perm, size_t bytes) {
     RTX_HIP(hipMemcpyAsync(host_perm, perm, bytes, hipMemcpyDeviceToHost, c->stream));
     RTX_HIP(hipStreamSynchronize(c->stream));
     return RTX_OK;
+}
+
+// ---- film queries: a pixel of a frame of its own (rtx_film.h) -------------------
+static_assert(sizeof(rtx_film_query) == rtx::kFilmBytes && sizeof(rtx_film_lens_query) == rtx::kFilmLensBytes,
+              "rtx_trace_film: four float4 per query, six with a lens");
+static_assert(offsetof(rtx_film_query, o) == 4 * rtx::kFilmO && offsetof(rtx_film_query, seed) == 4 * rtx::kFilmSeed &&
+                  offsetof(rtx_film_query, lower_left) == 4 * rtx::kFilmL &&
+                  offsetof(rtx_film_query, tag) == 4 * rtx::kFilmTag &&
+                  offsetof(rtx_film_query, horizontal) == 4 * rtx::kFilmH &&
+                  offsetof(rtx_film_query, fx) == 4 * rtx::kFilmFx &&
+                  offsetof(rtx_film_query, vertical) == 4 * rtx::kFilmV &&
+                  offsetof(rtx_film_query, fy) == 4 * rtx::kFilmFy &&
+                  offsetof(rtx_film_lens_query, lens_u) == 4 * rtx::kFilmLensU &&
+                  offsetof(rtx_film_lens_query, lens_r) == 4 * rtx::kFilmLensR &&
+                  offsetof(rtx_film_lens_query, lens_v) == 4 * rtx::kFilmLensV &&
+                  offsetof(rtx_film_lens_query, reserved) == 4 * rtx::kFilmReserved,
+              "rtx_film.h restates the record");
+static_assert(RTX_FILM_LENS == rtx::kFilmLens && RTX_CAST_ORDER_AUTO == rtx::kFilmOrderAuto &&
+                  RTX_CAST_ORDER_GIVEN == rtx::kFilmOrderGiven && RTX_CAST_ORDER_COHERENT == rtx::kFilmOrderCoherent &&
+                  RTX_FILM_EQUIRECT == rtx::kFilmEquirect && RTX_FILM_FISHEYE == rtx::kFilmFisheye,
+              "rtx_film.h restates these");
+
+int rtx_trace_film(rtx_ctx *c, const void *d_queries, uint32_t n, uint32_t samples, float img_w, float img_h,
+                   uint32_t flags, uint32_t order, void *d_results, void *d_segments) {
+    // the argument rules first (rtx_film.h): none of them looks at the context
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_trace_film: null ctx");
+    switch (rtx::film_args(d_queries != nullptr, d_results != nullptr, n, samples, flags, order)) {
+    case rtx::kFilmArgQueries: return fail(RTX_ERR_INVALID, "rtx_trace_film: d_queries is NULL");
+    case rtx::kFilmArgResults: return fail(RTX_ERR_INVALID, "rtx_trace_film: d_results is NULL");
+    case rtx::kFilmArgSamples: return fail(RTX_ERR_INVALID, "rtx_trace_film: samples is 0");
+    case rtx::kFilmArgFlags: return fail(RTX_ERR_INVALID, "rtx_trace_film: unknown flags");
+    case rtx::kFilmArgOrder:
+        return fail(RTX_ERR_INVALID, order == RTX_CAST_ORDER_COHERENT
+                                         ? "rtx_trace_film: the coherent order does not apply to film records"
+                                         : "rtx_trace_film: unknown order");
+    case rtx::kFilmArgOk: break;
+    }
+    if (!c->have_world) return fail(RTX_ERR_STATE, "rtx_trace_film: no world uploaded");
+    switch (rtx::paths_world(samples, c->depth)) {
+    case rtx::kPathsWorldDepth0: return fail(RTX_ERR_INVALID, "rtx_trace_film: the world's depth is 0");
+    case rtx::kPathsWorldCount: return fail(RTX_ERR_INVALID, "rtx_trace_film: samples * depth does not fit 32 bits");
+    case rtx::kPathsWorldOk: break;
+    }
+    if (n == 0) return RTX_OK;
+    rtx::KFilm f;
+    f.p.scene = scene_of(c);
+    f.p.depth = c->depth;
+    f.p.flags = rtx::paths_frame_flags(flags);
+    f.p.samples = samples;
+    f.p.n = n;
+    f.p.mode = flags & rtx::kPathsContinue;
+    f.img_w = img_w;
+    f.img_h = img_h;
+    const bool lens = (flags & rtx::kFilmLens) != 0u;
+    int rc = set_device(c);
+    if (rc) return rc;
+    const float4 *queries = static_cast<const float4 *>(d_queries);
+    float4 *results = static_cast<float4 *>(d_results);
+    uint32_t *segments = static_cast<uint32_t *>(d_segments);
+    const uint32_t pr = rtx::paths_default_probe(f.p.scene.n_pad);
+    if (order != RTX_PATHS_ORDER_COST || !rtx::paths_two_phase(samples, pr)) {  // AUTO is GIVEN; nothing left to order
+        const hipError_t e = rtx::launch_film(f, lens, queries, nullptr, results, segments, c->stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_film");
+        c->film_last = RTX_CAST_ORDER_GIVEN;
+        return RTX_OK;
+    }
+    // rtx_trace_paths_keyed's probe: pr samples in the given order with their
+    // counts kept aside, the sort, the rest as a continuing launch through perm
+    c->paths_perm_valid = false;  // (the scratch is about to hold another order)
+    rc = ensure_cast(c, n);
+    if (rc) return rc;
+    rc = ensure_paths_probe(c, n);
+    if (rc) return rc;
+    f.p.samples = pr;
+    hipError_t e = rtx::launch_film(f, lens, queries, nullptr, results, c->d_paths_probe, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_film");
+    f.p.samples = samples - pr;
+    f.p.mode = rtx::kPathsContinue;
+    const rtx::KCastScratch k{c->d_cast, c->d_cast + rtx::kCastBuckets, c->d_cast + rtx::kCastBuckets + c->cast_rays};
+    e = rtx::launch_paths_cost_order(c->d_paths_probe, n, k, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_paths_cost_order");
+    e = rtx::launch_film(f, lens, queries, k.perm, results, segments, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_film");
+    if (segments) {  // the whole call's count: the probe's plus the rest's
+        e = rtx::launch_paths_add_segments(segments, c->d_paths_probe, n, c->stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_paths_add_segments");
+    }
+    c->film_last = RTX_PATHS_ORDER_COST;
+    return RTX_OK;
+}
+
+int rtx_film_last_order(rtx_ctx *c) {
+    if (!c) return fail(RTX_ERR_INVALID, "rtx_film_last_order: null ctx");
+    return c->film_last;
 }
 
 int rtx_debug_pixel_cost(rtx_ctx *c, uint32_t spp, uint32_t *host_cost) {

@@ -324,6 +324,66 @@ bool RtxCSApp::TracePaths(const std::vector<rtx_path_query> &queries, uint32_t s
     return ok;
 }
 
+bool RtxCSApp::TraceFilm(const void *queries, size_t count, uint32_t samples, float img_w, float img_h,
+                         std::vector<rtx_path_result> *results, uint32_t flags, int order,
+                         std::vector<uint32_t> *segments) {
+    if (!m_ok) return false;
+    if (!results || (count != 0 && !queries)) {
+        m_error = "TraceFilm: queries or results is NULL";
+        return false;
+    }
+    if (count > 0xffffffffull) {
+        m_error = "TraceFilm: more than 2^32 - 1 queries";
+        return false;
+    }
+    const bool cont = (flags & RTX_PATHS_CONTINUE) != 0u;
+    if (cont && results->size() != count) {
+        m_error = "TraceFilm: RTX_PATHS_CONTINUE needs one record per query to continue from";
+        return false;
+    }
+    results->resize(count);
+    if (segments) segments->resize(count);
+    const uint32_t n = (uint32_t)count;
+    const size_t rec = (flags & RTX_FILM_LENS) != 0u ? sizeof(rtx_film_lens_query) : sizeof(rtx_film_query);
+    const size_t qbytes = (size_t)n * rec, rbytes = (size_t)n * sizeof(rtx_path_result);
+    const size_t sbytes = (size_t)n * sizeof(uint32_t);
+    void *d[3] = {nullptr, nullptr, nullptr};
+    bool ok = n == 0 || (rtx_alloc(m_ctx, qbytes, &d[0]) == RTX_OK && rtx_alloc(m_ctx, rbytes, &d[1]) == RTX_OK &&
+                         (!segments || rtx_alloc(m_ctx, sbytes, &d[2]) == RTX_OK) &&
+                         rtx_copy_to_device(m_ctx, d[0], queries, qbytes) == RTX_OK &&
+                         (!cont || rtx_copy_to_device(m_ctx, d[1], results->data(), rbytes) == RTX_OK));
+    ok = ok && rtx_trace_film(m_ctx, d[0], n, samples, img_w, img_h, flags, (uint32_t)order, d[1], d[2]) == RTX_OK;
+    if (ok && n != 0) ok = rtx_copy_to_host(m_ctx, results->data(), d[1], rbytes) == RTX_OK;
+    if (ok && n != 0 && segments) ok = rtx_copy_to_host(m_ctx, segments->data(), d[2], sbytes) == RTX_OK;
+    if (!ok) m_error = rtx_last_error();
+    for (void *p : d)
+        if (p) rtx_free(m_ctx, p);
+    return ok;
+}
+
+int RtxCSApp::FilmLastOrder() const { return m_ctx ? rtx_film_last_order(m_ctx) : RTX_CAST_ORDER_GIVEN; }
+
+bool RtxCSApp::FilmImage(const std::vector<rtx_path_result> &results, uint32_t samples, std::vector<float> *rgba) {
+    if (!m_ok) return false;
+    if (!rgba || results.empty() || samples == 0u) {
+        m_error = "FilmImage: no records, no samples or rgba is NULL";
+        return false;
+    }
+    const size_t n = results.size(), bytes = n * sizeof(rtx_path_result);
+    rgba->assign(4 * n, 0.0f);
+    void *d[3] = {nullptr, nullptr, nullptr};  // accumulator (zeroed), sums, image
+    bool ok = rtx_alloc(m_ctx, bytes, &d[0]) == RTX_OK && rtx_alloc(m_ctx, bytes, &d[1]) == RTX_OK &&
+              rtx_alloc(m_ctx, bytes, &d[2]) == RTX_OK &&
+              rtx_copy_to_device(m_ctx, d[0], rgba->data(), bytes) == RTX_OK &&
+              rtx_copy_to_device(m_ctx, d[1], results.data(), bytes) == RTX_OK &&
+              rtx_fold_frames(m_ctx, d[0], d[1], 1, n, n, samples, d[2]) == RTX_OK &&
+              rtx_copy_to_host(m_ctx, rgba->data(), d[2], bytes) == RTX_OK;
+    if (!ok) m_error = rtx_last_error();
+    for (void *p : d)
+        if (p) rtx_free(m_ctx, p);
+    return ok;
+}
+
 bool RtxCSApp::TracePathsKeyed(const std::vector<rtx_path_query> &queries, uint32_t samples,
                                std::vector<rtx_path_result> *results, uint32_t flags,
                                const std::vector<uint32_t> *keys, uint32_t probe, std::vector<uint32_t> *segments) {

@@ -26,6 +26,18 @@
 // every query from its record. The depth is --depth's, the schedule
 // --cast-order's, --lambert-guard sets RTX_PATHS_LAMBERT_GUARD. The JSON line is
 // {"paths": {"queries", "samples", "segments", "order", "continued", "ms"}}.
+//           [--film QUERIES.bin --film-dim W,H [--film-lens] [--film-order given|cost] --samples S
+//            --results OUT.bin [--segments SEG.bin] [--continue]]
+//           [--film-camera equirect|fisheye [--film-fov D] --samples S --out IMAGE.pfm|IMAGE.ppm]
+// --film QUERIES.bin traces the file's film queries (rtx_trace_film) instead of
+// rendering: raw 64-byte rtx_film_query records, or with --film-lens 96-byte
+// rtx_film_lens_query records; --film-dim W,H are the call's img_w, img_h (2,2
+// for unit-form records); --samples, --results, --segments and --continue as
+// with --paths. stdout is one JSON line: {"film": {"queries", "samples",
+// "segments", "order", "continued", "lens", "ms"}}. --film-camera renders the
+// scene through rtx_film_camera's records of --width x --height pixels from
+// the configured camera position (--film-fov: the fisheye's angle, default
+// 180) and writes toGamma(sum / samples) to --out, a .pfm or a .ppm.
 // --paths-order cost traces them in cost order instead (rtx_trace_paths_keyed;
 // the same records, "order" says "cost" when the call sorted): by the library's
 // probe of --paths-probe P samples (default 0: its own choice), or with
@@ -127,7 +139,10 @@ static void usage() {
                  "               [--refine-ids S,ID[,ID...] --grow G --steps K]\n"
                  "               [--cast RAYS.bin --hits OUT.bin [--cast-order auto|given|coherent] [--t-min T]]\n"
                  "               [--paths QUERIES.bin --samples S [--continue] --results OUT.bin [--segments SEG.bin]\n"
-                 "                [--paths-order cost [--paths-probe P]] [--paths-keys KEYS.bin]]\n");
+                 "                [--paths-order cost [--paths-probe P]] [--paths-keys KEYS.bin]]\n"
+                 "               [--film QUERIES.bin --film-dim W,H [--film-lens] [--film-order given|cost] --samples S\n"
+                 "                --results OUT.bin [--segments SEG.bin] [--continue]]\n"
+                 "               [--film-camera equirect|fisheye [--film-fov D] --samples S --out IMAGE.pfm|IMAGE.ppm]\n");
 }
 
 int main(int argc, char **argv) {
@@ -167,6 +182,12 @@ int main(int argc, char **argv) {
     bool paths_cost = false;                   // --paths-order cost
     long paths_probe = 0;                      // --paths-probe
     std::string paths_keys;                    // --paths-keys KEYS.bin
+    std::string film_in, film_out;             // --film QUERIES.bin, --out IMAGE
+    float film_dim[2] = {0.0f, 0.0f};          // --film-dim W,H
+    bool film_lens = false, film_dim_set = false;  // --film-lens
+    int film_order = RTX_CAST_ORDER_GIVEN;     // --film-order
+    int film_camera = -1;                      // --film-camera (RTX_FILM_*; -1: not given)
+    float film_fov = 180.0f;                   // --film-fov
     std::vector<int> devices;  // non-empty: a group
     int gather = RTX_GATHER_AUTO;
     bool group_opts = false;   // --gather / --tile-rows given
@@ -265,6 +286,34 @@ int main(int argc, char **argv) {
             paths_cost = true;
         } else if (a == "--paths-probe") paths_probe = std::atol(next());
         else if (a == "--paths-keys") paths_keys = next(), paths_cost = true;
+        else if (a == "--film") film_in = next();
+        else if (a == "--out") film_out = next();
+        else if (a == "--film-lens") film_lens = true;
+        else if (a == "--film-fov") film_fov = (float)std::atof(next());
+        else if (a == "--film-dim") {
+            char tail = 0;
+            if (std::sscanf(next(), "%f,%f%c", &film_dim[0], &film_dim[1], &tail) != 2) {
+                usage();
+                return 2;
+            }
+            film_dim_set = true;
+        } else if (a == "--film-order") {
+            const std::string m = next();
+            if (m == "given") film_order = RTX_CAST_ORDER_GIVEN;
+            else if (m == "cost") film_order = RTX_PATHS_ORDER_COST;
+            else {
+                usage();
+                return 2;
+            }
+        } else if (a == "--film-camera") {
+            const std::string m = next();
+            if (m == "equirect") film_camera = RTX_FILM_EQUIRECT;
+            else if (m == "fisheye") film_camera = RTX_FILM_FISHEYE;
+            else {
+                usage();
+                return 2;
+            }
+        }
         else if (a == "--t-min") cast_t_min = (float)std::atof(next());
         else if (a == "--cast-order") {
             const std::string m = next();
@@ -383,7 +432,7 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "rtx_cli: --cast RAYS.bin and --hits OUT.bin go together\n");
         return 2;
     }
-    if (paths_in.empty() != paths_out.empty() || (!paths_in.empty() && !cast_in.empty())) {
+    if ((paths_in.empty() && film_in.empty()) != paths_out.empty() || (!paths_in.empty() && !cast_in.empty())) {
         std::fprintf(stderr, "rtx_cli: --paths QUERIES.bin and --results OUT.bin go together, without --cast\n");
         return 2;
     }
@@ -391,7 +440,31 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "rtx_cli: --paths needs --samples S >= 1\n");
         return 2;
     }
-    if (paths_in.empty() && (paths_continue || !paths_seg.empty() || paths_samples != 0)) {
+    const bool filming = !film_in.empty() || film_camera >= 0;
+    if (filming && (!paths_in.empty() || !cast_in.empty() || (!film_in.empty() && film_camera >= 0))) {
+        std::fprintf(stderr, "rtx_cli: --film and --film-camera go alone, without --paths and --cast\n");
+        return 2;
+    }
+    if (!film_in.empty() && (paths_out.empty() || !film_dim_set || !film_out.empty())) {
+        std::fprintf(stderr, "rtx_cli: --film QUERIES.bin needs --film-dim W,H and --results OUT.bin (no --out)\n");
+        return 2;
+    }
+    if (film_camera >= 0 && (film_out.size() < 5 || (film_out.substr(film_out.size() - 4) != ".pfm" &&
+                                                      film_out.substr(film_out.size() - 4) != ".ppm") ||
+                             !paths_out.empty() || !paths_seg.empty() || paths_continue)) {
+        std::fprintf(stderr, "rtx_cli: --film-camera needs --out IMAGE.pfm or IMAGE.ppm, without --results, "
+                             "--segments and --continue\n");
+        return 2;
+    }
+    if (filming && (paths_samples < 1 || paths_samples > 0xffffffffl)) {
+        std::fprintf(stderr, "rtx_cli: --film and --film-camera need --samples S >= 1\n");
+        return 2;
+    }
+    if (!filming && (film_lens || film_dim_set || !film_out.empty())) {
+        std::fprintf(stderr, "rtx_cli: --film-dim and --film-lens go with --film, --out with --film-camera\n");
+        return 2;
+    }
+    if (paths_in.empty() && !filming && (paths_continue || !paths_seg.empty() || paths_samples != 0)) {
         std::fprintf(stderr, "rtx_cli: --samples, --continue and --segments go with --paths\n");
         return 2;
     }
@@ -489,6 +562,96 @@ int main(int argc, char **argv) {
         std::printf("{\"cast\": {\"rays\": %zu, \"hits\": %zu, \"order\": \"%s\", \"t_min\": %.9g, \"ms\": %.3f}}\n",
                     rays.size(), nhit, app.CastLastOrder() == RTX_CAST_ORDER_COHERENT ? "coherent" : "given",
                     (double)cast_t_min, ms);
+        return 0;
+    }
+    if (filming) {  // trace film queries instead of rendering: the file's, or a camera model's
+        std::vector<unsigned char> raw;
+        const size_t rec = film_lens ? sizeof(rtx_film_lens_query) : sizeof(rtx_film_query);
+        float img_w = film_dim[0], img_h = film_dim[1];
+        auto read_all = [](const std::string &path, size_t unit, std::vector<unsigned char> &out) {
+            std::FILE *f = std::fopen(path.c_str(), "rb");
+            bool ok = f != nullptr;
+            if (ok) {
+                ok = std::fseek(f, 0, SEEK_END) == 0;
+                const long bytes = ok ? std::ftell(f) : -1;
+                ok = ok && bytes >= 0 && bytes % (long)unit == 0 && std::fseek(f, 0, SEEK_SET) == 0;
+                if (ok) {
+                    out.resize((size_t)bytes);
+                    ok = std::fread(out.data(), 1, out.size(), f) == out.size();
+                }
+                std::fclose(f);
+            }
+            return ok;
+        };
+        auto write_all = [](const std::string &path, const void *data, size_t bytes) {
+            std::FILE *f = std::fopen(path.c_str(), "wb");
+            bool ok = f != nullptr && std::fwrite(data, 1, bytes, f) == bytes;
+            if (f) ok = std::fclose(f) == 0 && ok;
+            return ok;
+        };
+        if (film_camera >= 0) {
+            const float up[3] = {0.0f, 1.0f, 0.0f};
+            raw.resize((size_t)cfg.width * cfg.height * sizeof(rtx_film_query));
+            if (rtx_film_camera(film_camera, cfg.cam_pos, cfg.cam_look_at, up, film_fov, cfg.width, cfg.height, 0,
+                                reinterpret_cast<rtx_film_query *>(raw.data())) != RTX_OK) {
+                std::fprintf(stderr, "rtx_cli: --film-camera: bad --film-fov, --width or --height\n");
+                return 2;
+            }
+            img_w = img_h = 2.0f;  // unit-form records
+        } else if (!read_all(film_in, rec, raw)) {
+            std::fprintf(stderr, "rtx_cli: --film: cannot read %s as %zu-byte query records\n", film_in.c_str(), rec);
+            return 1;
+        }
+        const size_t nq = raw.size() / rec;
+        std::vector<rtx_path_result> results;
+        if (paths_continue) {
+            std::vector<unsigned char> prev;
+            if (!read_all(paths_out, sizeof(rtx_path_result), prev) || prev.size() != nq * sizeof(rtx_path_result)) {
+                std::fprintf(stderr, "rtx_cli: --continue: cannot read %s as one 16-byte record per query\n",
+                             paths_out.c_str());
+                return 1;
+            }
+            results.resize(nq);
+            if (!prev.empty()) std::memcpy(results.data(), prev.data(), prev.size());
+        }
+        std::vector<uint32_t> segs;
+        const uint32_t fflags = (paths_continue ? (uint32_t)RTX_PATHS_CONTINUE : 0u) |
+                                (cfg.lambert_guard ? (uint32_t)RTX_PATHS_LAMBERT_GUARD : 0u) |
+                                (film_lens ? (uint32_t)RTX_FILM_LENS : 0u);
+        const auto t0 = std::chrono::steady_clock::now();
+        if (!app.TraceFilm(raw.data(), nq, (uint32_t)paths_samples, img_w, img_h, &results, fflags, film_order, &segs)) {
+            std::fprintf(stderr, "rtx_cli: --film failed: %s\n", app.last_error().c_str());
+            return 1;
+        }
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (film_camera >= 0) {
+            std::vector<float> img;
+            if (!app.FilmImage(results, (uint32_t)paths_samples, &img)) {
+                std::fprintf(stderr, "rtx_cli: --film-camera failed: %s\n", app.last_error().c_str());
+                return 1;
+            }
+            const bool is_pfm = film_out.substr(film_out.size() - 4) == ".pfm";
+            if (!(is_pfm ? rtx::write_pfm(film_out, img.data(), cfg.width, cfg.height)
+                         : rtx::write_ppm(film_out, img.data(), cfg.width, cfg.height))) {
+                std::fprintf(stderr, "rtx_cli: --out: cannot write %s\n", film_out.c_str());
+                return 1;
+            }
+        } else {
+            if (!write_all(paths_out, results.data(), results.size() * sizeof(rtx_path_result))) {
+                std::fprintf(stderr, "rtx_cli: --results: cannot write %s\n", paths_out.c_str());
+                return 1;
+            }
+            if (!paths_seg.empty() && !write_all(paths_seg, segs.data(), segs.size() * sizeof(uint32_t))) {
+                std::fprintf(stderr, "rtx_cli: --segments: cannot write %s\n", paths_seg.c_str());
+                return 1;
+            }
+        }
+        unsigned long long total = 0;
+        for (const uint32_t v : segs) total += v;
+        std::printf("{\"film\": {\"queries\": %zu, \"samples\": %ld, \"segments\": %llu, \"order\": \"%s\", "
+                    "\"continued\": %s, \"lens\": %s, \"ms\": %.3f}}\n",
+                    nq, paths_samples, total, app.FilmLastOrder() == RTX_PATHS_ORDER_COST ? "cost" : "given",
+                    paths_continue ? "true" : "false", film_lens ? "true" : "false", ms);
         return 0;
     }
     if (!paths_in.empty()) {  // trace the file's path queries instead of rendering

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "../../include/rtx.h"
+#include "rtx_film.h"   // rtx_film_from_frame, rtx_film_camera: the generators, shared with tests/film_check.cpp
 #include "rtx_paths.h"  // rtx_path_seed: the seed rule, shared with tests/paths_check.cpp
 
 namespace {
@@ -214,6 +215,26 @@ int rtx_camera_set_aperture(rtx_frame *frame, float aperture) {
 // The chain seed of pixel (x, y) in frame frame_index (rtx_paths.h): what a
 // path query along a ray starts from to be that pixel of the ray's twin frame.
 float rtx_path_seed(uint32_t x, uint32_t y, uint32_t frame_index) { return rtx::path_seed(x, y, frame_index); }
+
+// The film records of a frame's listed pixels, and of the two camera models
+// that are no pinhole (rtx_film.h has the rules and the arithmetic).
+int rtx_film_from_frame(const rtx_frame *f, const uint32_t *xs, const uint32_t *ys, uint32_t n, uint32_t frame_index,
+                        void *host_queries, int lens, float *img_w, float *img_h) {
+    if (!f) return RTX_ERR_INVALID;
+    if (rtx::film_from_frame(f->origin, f->horizontal, f->vertical, f->lower_left, f->lens_u, f->lens_v, f->width,
+                             f->height, f->rng_mode, xs, ys, n, frame_index, host_queries, lens != 0) != rtx::kFilmFrameOk)
+        return RTX_ERR_INVALID;
+    if (img_w) *img_w = f->img_w;
+    if (img_h) *img_h = f->img_h;
+    return RTX_OK;
+}
+
+int rtx_film_camera(int model, const float from[3], const float at[3], const float vup[3], float fov_deg,
+                    uint32_t width, uint32_t height, uint32_t frame_index, rtx_film_query *host_queries) {
+    return rtx::film_camera(model, from, at, vup, fov_deg, width, height, frame_index, host_queries) == rtx::kFilmCameraOk
+               ? RTX_OK
+               : RTX_ERR_INVALID;
+}
 
 // WorldDef byte layout (DxCSApp.cpp:64-71): float4 sceneValues;
 // float4 spheres[512]; float4 matTypes[128] (4 per float4,

@@ -358,6 +358,18 @@ struct KPaths {
 // p.samples > 0, p.depth > 0.
 hipError_t launch_paths(const KPaths &p, const float4 *queries, const uint32_t *perm, float4 *results,
                         uint32_t *segments, hipStream_t stream);
+// Film queries (rtx_film.h; include/rtx.h rtx_trace_film). The parameter block
+// of k_film, its first kernel argument: k_paths' block plus the frame
+// dimensions every record of the call shares.
+struct KFilm {
+    KPaths p;
+    float img_w, img_h;
+};
+// k_film<lens>: k_paths' grid, lanes, results and segments on records of four
+// (lens: six) float4; every sample starts as start_sample does on the record's
+// values. f.p.n > 0, f.p.samples > 0, f.p.depth > 0.
+hipError_t launch_film(const KFilm &f, bool lens, const float4 *queries, const uint32_t *perm, float4 *results,
+                       uint32_t *segments, hipStream_t stream);
 // The cost order (rtx_trace_paths_keyed): k_paths_cost_keys, then k_cast_prefix
 // and k_cast_scatter as they stand: scratch.perm becomes the order of the n
 // words of src by non-increasing min(word, 65535), a permutation of 0 .. n-1.

@@ -33,6 +33,7 @@
 #include "rtx_device_math.h"
 #include "rtx_diag.h"
 #include "rtx_internal.h"
+#include "rtx_film.h"
 #include "rtx_paths.h"
 #include "rtx_prefilter.h"
 
@@ -4385,6 +4386,99 @@ __global__ void __launch_bounds__(kBlock) k_paths_add_segments(uint32_t *__restr
     segments[i] += probe_segs[i];
 }
 
+// ---- film queries: a pixel of a frame of its own (rtx_trace_film; rtx_film.h) --
+// k_paths with the sample start restated on the record's values: the same
+// exact grid, the same lane struct and per-lane loop, the same choice of scan
+// under `if (L.active)`, the same stores. What differs is film_begin_sample:
+// start_sample's arithmetic — two hash2 draws, u and v, get_ray, the thin lens —
+// on the record's (o, L, H, V, fx, fy) and the launch's img_w, img_h, read from
+// the by-value KFilm. Nothing here reads the kernel arguments by address
+// (kernarg_here and what is built on it: frame_vals, start_sample,
+// begin_sample, params_at<true>): this kernel's arguments begin with a KFilm.
+// The lane keeps its query index and reads the record again at each sample
+// start (a sample is several scans long and the record sits in L2) instead of
+// carrying 16 to 24 floats round the loop. kLens: records of six float4, whose
+// lens_r > 0 test is the lane's own (DESIGN.md §3k has the audit).
+template <bool kLens>
+__device__ __forceinline__ void film_begin_sample(PathLane &L, const float4 *rec, float wm1, float hm1) {
+    const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3];
+    float h0, h1, g0, g1;
+    hash2(L.seed, h0, h1);
+    const float u = (q2.w + h0 * 1.1f) / wm1;
+    hash2(L.seed, g0, g1);
+    const float v = (q3.w + g1 * 1.1f) / hm1;
+    f3 o = mk3(q0.x, q0.y, q0.z);
+    f3 d = ((mk3(q1.x, q1.y, q1.z) + u * mk3(q2.x, q2.y, q2.z)) + v * mk3(q3.x, q3.y, q3.z)) - o;  // get_ray
+    if constexpr (kLens) {
+        const float4 q4 = rec[4];
+        if (q4.w > 0.0f) {  // the thin lens, start_sample's
+            const float4 q5 = rec[5];
+            const f3 rd = q4.w * random_in_unit_disk(L.seed);
+            const f3 off = rd.x * mk3(q4.x, q4.y, q4.z) + rd.y * mk3(q5.x, q5.y, q5.z);
+            o = o + off;
+            d = d - off;
+        }
+    }
+    L.o = o;
+    L.d = d;
+    L.a = dir_len2(d);
+    L.inv_a = 1.0f / L.a;
+    L.col = mk3(1.0f, 1.0f, 1.0f);
+    L.bounce = 0;
+}
+template <bool kLens>
+__global__ void __launch_bounds__(kRB) k_film(const KFilm F, const float4 *queries, const uint32_t *__restrict__ perm,
+                                              float4 *results, uint32_t *__restrict__ segments) {
+    __shared__ uint32_t list[list_bytes<true>() > kListBytes ? list_bytes<true>() / sizeof(uint32_t)
+                                                             : kListBytes / sizeof(uint32_t)];
+    const KPaths &P = F.p;
+    const uint32_t g = blockIdx.x * kRB + threadIdx.x;
+    if (!paths_lane_live((uint64_t)blockIdx.x * kRB + threadIdx.x, P.n)) return;
+    const uint32_t i = paths_lane_query(g, perm != nullptr, perm ? perm[g] : 0u, P.n);
+    const float wm1 = F.img_w - 1.0f, hm1 = F.img_h - 1.0f;
+    PathLane L;
+    L.acc = mk3(0.0f, 0.0f, 0.0f);
+    if ((P.mode & kPathsContinue) != 0u) {  // from the record an earlier call left
+        const float4 r = results[i];
+        L.acc = mk3(r.x, r.y, r.z);
+        L.seed = r.w;
+    } else {
+        L.seed = queries[film_query_vec4(i, kLens)].w;
+    }
+    L.sample = 0;
+    L.segs = 0;
+    L.active = true;
+    film_begin_sample<kLens>(L, queries + film_query_vec4(i, kLens), wm1, hm1);
+    const KScene &S = P.scene;
+    const int last = (int)S.n - 1;
+    while (__ballot(L.active) != 0ull) {
+        if (L.active) {
+            float best = __uint_as_float(0x7f800000u);
+            // (an empty world is all sky: its scan would have nothing to clamp a list position to)
+            const int hit = S.n == 0u ? -1
+                            : min((S.cpre && S.n_pad > kScanPfMin)
+                                      ? hit_world_culled(S, L.o, L.d, L.a, L.inv_a, kTMin, best, list)
+                                  : S.n_pad > kScanPfMin ? hit_world_pre<true>(S, L.o, L.d, L.a, L.inv_a, kTMin, best, list)
+                                                         : hit_world_pre<false>(S, L.o, L.d, L.a, L.inv_a, kTMin, best, list),
+                                  last);
+            L.segs++;
+            f3 c = mk3(0.0f, 0.0f, 0.0f);
+            const int r = path_segment(P, L, hit, best, c);
+            if (r == kSegSky) L.acc = L.acc + c;  // shade's add; a black path adds nothing
+            if (r != kSegContinue) {
+                L.sample++;
+                if (L.sample >= P.samples) {
+                    results[i] = make_float4(L.acc.x, L.acc.y, L.acc.z, L.seed);
+                    if (segments) segments[i] = L.segs;
+                    L.active = false;
+                } else {
+                    film_begin_sample<kLens>(L, queries + film_query_vec4(i, kLens), wm1, hm1);
+                }
+            }
+        }
+    }
+}
+
 // rtx_mask_from_ids, two passes (rtx_features.h): which pixels are listed, then
 // the Chebyshev growth and the number of set pixels (one atomic per wave that
 // has any). The id list travels as a kernel argument.
@@ -5100,6 +5194,19 @@ hipError_t launch_paths(const KPaths &p, const float4 *queries, const uint32_t *
     if (p.n == 0) return hipSuccess;
     if (p.samples == 0 || p.depth == 0) return hipErrorInvalidValue;  // (the loop's end needs both)
     hipLaunchKernelGGL(k_paths, dim3(paths_blocks(p.n, kRB)), dim3(kRB), 0, stream, p, queries, perm, results, segments);
+    return hipGetLastError();
+}
+
+hipError_t launch_film(const KFilm &f, bool lens, const float4 *queries, const uint32_t *perm, float4 *results,
+                       uint32_t *segments, hipStream_t stream) {
+    if (f.p.n == 0) return hipSuccess;
+    if (f.p.samples == 0 || f.p.depth == 0) return hipErrorInvalidValue;  // (the loop's end needs both)
+    if (lens)
+        hipLaunchKernelGGL(k_film<true>, dim3(paths_blocks(f.p.n, kRB)), dim3(kRB), 0, stream, f, queries, perm, results,
+                           segments);
+    else
+        hipLaunchKernelGGL(k_film<false>, dim3(paths_blocks(f.p.n, kRB)), dim3(kRB), 0, stream, f, queries, perm, results,
+                           segments);
     return hipGetLastError();
 }
 

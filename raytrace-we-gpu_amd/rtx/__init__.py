@@ -62,6 +62,13 @@ PATH_QUERY_DTYPE = np.dtype([("o", "<f4", (3,)), ("seed", "<f4"), ("d", "<f4", (
 PATH_RESULT_DTYPE = np.dtype([("sum", "<f4", (3,)), ("seed", "<f4")])
 PATHS_LAMBERT_GUARD, PATHS_CONTINUE = 1, 2  # rtx_trace_paths flags (RTX_PATHS_*)
 PATHS_ORDER_COST = 3  # RTX_PATHS_ORDER_COST: rtx_paths_last_order after rtx_trace_paths_keyed sorted
+FILM_QUERY_DTYPE = np.dtype([("o", "<f4", (3,)), ("seed", "<f4"), ("lower_left", "<f4", (3,)), ("tag", "<u4"),
+                             ("horizontal", "<f4", (3,)), ("fx", "<f4"), ("vertical", "<f4", (3,)), ("fy", "<f4")])
+FILM_LENS_QUERY_DTYPE = np.dtype([("q", FILM_QUERY_DTYPE), ("lens_u", "<f4", (3,)), ("lens_r", "<f4"),
+                                  ("lens_v", "<f4", (3,)), ("reserved", "<u4")])
+FILM_LENS = 4  # rtx_trace_film flag (RTX_FILM_LENS): 96-byte records
+FILM_ORDERS = {"auto": 0, "given": 1, "coherent": 2, "cost": 3}  # rtx_trace_film's `order` ("coherent" is refused)
+FILM_CAMERAS = {"equirect": 0, "fisheye": 1}  # rtx_film_camera (RTX_FILM_*)
 GATHER_MODES = {"auto": 0, "rccl": 1, "copy": 2}  # rtx_group_create (RTX_GATHER_*)
 GROUP_MAX = 64  # RTX_GROUP_MAX
 
@@ -193,6 +200,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "rtx_paths_last_order": (C.c_int, [ctx]),
         "rtx_trace_paths_keyed": (C.c_int, [ctx, vp, u32, u32, u32, vp, u32, vp, vp]),
         "rtx_debug_paths_order": (C.c_int, [ctx, C.POINTER(u32), C.c_size_t]),
+        "rtx_trace_film": (C.c_int, [ctx, vp, u32, u32, C.c_float, C.c_float, u32, u32, vp, vp]),
+        "rtx_film_last_order": (C.c_int, [ctx]),
+        "rtx_film_from_frame": (C.c_int, [C.POINTER(rtx_frame), C.POINTER(u32), C.POINTER(u32), u32, u32, vp, C.c_int,
+                                          f, f]),
+        "rtx_film_camera": (C.c_int, [C.c_int, f, f, f, C.c_float, u32, u32, u32, vp]),
         "rtx_camera_set_aperture": (C.c_int, [C.POINTER(rtx_frame), C.c_float]),
         "rtx_part_rows": (u32, [u32, u32, u32, u32]),
         "rtx_deinterleave_rows": (C.c_int, [ctx, vp, u32, u32, u32, u32, vp]),
@@ -263,6 +275,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     optional |= {"rtx_path_seed"}                                # ... probe "rtx_path_seed"
     optional |= {"rtx_trace_paths", "rtx_paths_last_order"}      # ... probe "rtx_trace_paths"
     optional |= {"rtx_trace_paths_keyed", "rtx_debug_paths_order"}  # ... probe "rtx_trace_paths_keyed"
+    optional |= {"rtx_trace_film", "rtx_film_last_order", "rtx_film_from_frame", "rtx_film_camera"}  # ... "rtx_trace_film"
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -311,6 +324,44 @@ def path_queries(o, d, seeds, tags=None) -> np.ndarray:
     q["seed"] = seeds
     if tags is not None:
         q["tag"] = np.asarray(tags, np.uint32)
+    return q
+
+
+def film_from_frame(frame: "rtx_frame", xs, ys, frame_index: int = 0, lens: Optional[bool] = None):
+    """The film records of the listed pixels (xs[i], ys[i]) of a frame (rtx_film_from_frame; host, no
+    GPU): (queries, img_w, img_h), to be traced with Context.trace_film(queries, samples, img_w,
+    img_h). lens: True for FILM_LENS_QUERY_DTYPE records, False for FILM_QUERY_DTYPE (refused for a
+    frame with a lens), None: whichever the frame needs."""
+    lib = load_library()
+    if not hasattr(lib, "rtx_film_from_frame"):
+        raise RtxError("this librtx has no rtx_film_from_frame")
+    xs = np.ascontiguousarray(xs, np.uint32).reshape(-1)
+    ys = np.ascontiguousarray(ys, np.uint32).reshape(-1)
+    if xs.size != ys.size:
+        raise RtxError("film_from_frame: xs and ys differ in length")
+    if lens is None:
+        lens = frame.lens_u[3] > 0.0
+    q = np.zeros(xs.size, FILM_LENS_QUERY_DTYPE if lens else FILM_QUERY_DTYPE)
+    w, h = C.c_float(), C.c_float()
+    u32p = C.POINTER(C.c_uint32)
+    _check(lib.rtx_film_from_frame(C.byref(frame), xs.ctypes.data_as(u32p), ys.ctypes.data_as(u32p), xs.size,
+                                   frame_index, q.ctypes.data, 1 if lens else 0, C.byref(w), C.byref(h)),
+           "rtx_film_from_frame")
+    return q, np.float32(w.value), np.float32(h.value)
+
+
+def film_camera(model: str, width: int, height: int, look_from=(13.0, 2.0, 3.0), look_at=(0.0, 0.0, 0.0),
+                vup=(0.0, 1.0, 0.0), fov_deg: float = 180.0, frame_index: int = 0) -> np.ndarray:
+    """width * height unit-form FILM_QUERY_DTYPE records of an "equirect" or "fisheye" camera
+    (rtx_film_camera; host, no GPU), record y * width + x, row 0 at the bottom: trace them with
+    Context.trace_film(queries, samples, 2, 2)."""
+    lib = load_library()
+    if not hasattr(lib, "rtx_film_camera"):
+        raise RtxError("this librtx has no rtx_film_camera")
+    a = [np.ascontiguousarray(v, np.float32) for v in (look_from, look_at, vup)]
+    q = np.zeros(int(width) * int(height), FILM_QUERY_DTYPE)
+    _check(lib.rtx_film_camera(FILM_CAMERAS[model], _fptr(a[0]), _fptr(a[1]), _fptr(a[2]), fov_deg, width, height,
+                               frame_index, q.ctypes.data), "rtx_film_camera")
     return q
 
 
@@ -908,6 +959,131 @@ class Context:
                                          C.c_void_p(_dev_ptr(results)), C.c_void_p(_dev_ptr(d_seg))),
                "rtx_trace_paths", self._lib)
         return results, d_seg
+
+    def trace_film(self, queries, samples: int, img_w: float, img_h: float, flags: int = 0, order: str = "auto",
+                   results=None, segments=None, n: Optional[int] = None, cont: bool = False,
+                   lens: Optional[bool] = None):
+        """Path queries with a per-sample film footprint (rtx_trace_film): query
+        i is a pixel (fx, fy) of the frame its record states, `samples`
+        jittered samples each. Returns (results, segments), segments None when
+        not asked for.
+
+        queries: a numpy array — n FILM_QUERY_DTYPE or FILM_LENS_QUERY_DTYPE
+        records (film_from_frame, film_camera), or (n, 16) / (n, 24) float32
+        rows — is uploaded, and numpy arrays come back (n PATH_RESULT_DTYPE
+        records, n uint32), after a wait. A device pointer, a DeviceArray or a
+        torch tensor is used in place, asynchronously on the context's stream,
+        and the device buffers come back (`n`: the number of queries, when the
+        object has no shape). lens: whether the records are the 96-byte ones
+        (RTX_FILM_LENS; also as a bit of `flags`); None: what a numpy array's
+        dtype or row length says, and False for a device buffer. results,
+        segments (True / None or False / a device buffer), cont: as in
+        trace_paths. order: "auto", "given" or "cost" — a schedule, never a
+        different record."""
+        flags = int(flags) | (PATHS_CONTINUE if cont else 0)
+        if not hasattr(self._lib, "rtx_trace_film"):
+            raise RtxError("this librtx has no rtx_trace_film")
+        if segments is None:
+            segments = False
+        if isinstance(queries, np.ndarray):
+            host = np.ascontiguousarray(queries)
+            if host.dtype == FILM_LENS_QUERY_DTYPE:
+                rec_lens = True
+            elif host.dtype == FILM_QUERY_DTYPE:
+                rec_lens = False
+            else:
+                if host.ndim != 2 or host.shape[1] not in (16, 24):
+                    raise RtxError("Context.trace_film: float rows are (n, 16) or (n, 24)")
+                rec_lens = host.shape[1] == 24
+                host = np.ascontiguousarray(host, np.float32)
+            if (lens is not None and bool(lens) != rec_lens) or ((flags & FILM_LENS) and not rec_lens):
+                raise RtxError("Context.trace_film: lens does not match the records")
+            flags |= FILM_LENS if rec_lens else 0
+            dt = FILM_LENS_QUERY_DTYPE if rec_lens else FILM_QUERY_DTYPE
+            n = host.shape[0]
+            start = None
+            if flags & PATHS_CONTINUE:
+                if not isinstance(results, np.ndarray):
+                    raise RtxError("Context.trace_film: continuing numpy queries needs numpy results")
+                start = np.ascontiguousarray(results)
+                if start.dtype != PATH_RESULT_DTYPE:
+                    start = np.ascontiguousarray(start, np.float32).reshape(-1, 4)
+                if start.shape[0] != n:
+                    raise RtxError("Context.trace_film: results and queries differ in length")
+            elif results is not None:
+                raise RtxError("Context.trace_film: numpy queries take results only to continue from")
+            d_q = self.alloc((max(n, 1),), dt)
+            d_r = self.alloc((max(n, 1),), PATH_RESULT_DTYPE)
+            d_s = self.alloc((max(n, 1),), np.uint32) if segments is True else None
+            try:
+                if n:
+                    _check(self._lib.rtx_copy_to_device(self._h, C.c_void_p(d_q.ptr), host.ctypes.data,
+                                                        dt.itemsize * n), "rtx_copy_to_device", self._lib)
+                    if start is not None:
+                        _check(self._lib.rtx_copy_to_device(self._h, C.c_void_p(d_r.ptr), start.ctypes.data, 16 * n),
+                               "rtx_copy_to_device", self._lib)
+                self.trace_film(d_q, samples, img_w, img_h, flags, order, d_r,
+                                d_s if d_s is not None else segments, n)
+                return d_r.numpy()[:n], (d_s.numpy()[:n] if d_s is not None else (None if segments is False else segments))
+            finally:
+                d_q.free()
+                d_r.free()
+                if d_s is not None:
+                    d_s.free()
+        if lens:
+            flags |= FILM_LENS
+        elif lens is not None and (flags & FILM_LENS):
+            raise RtxError("Context.trace_film: lens does not match the flags")
+        if n is None:
+            if not hasattr(queries, "shape"):
+                raise RtxError("Context.trace_film: n is needed with a bare pointer")
+            n = int(queries.shape[0])
+        if results is None:
+            if flags & PATHS_CONTINUE:
+                raise RtxError("Context.trace_film: continuing needs the results to continue from")
+            results = self.alloc((max(n, 1),), PATH_RESULT_DTYPE)
+        d_seg = self.alloc((max(n, 1),), np.uint32) if segments is True else (None if segments is False else segments)
+        _check(self._lib.rtx_trace_film(self._h, C.c_void_p(_dev_ptr(queries)), n, samples, np.float32(img_w),
+                                        np.float32(img_h), flags, FILM_ORDERS[order], C.c_void_p(_dev_ptr(results)),
+                                        C.c_void_p(_dev_ptr(d_seg))), "rtx_trace_film", self._lib)
+        return results, d_seg
+
+    def film_last_order(self) -> str:
+        """"given" or "cost": what the last trace_film ran (rtx_film_last_order)."""
+        code = self._lib.rtx_film_last_order(self._h)
+        for name in ("given", "cost"):
+            if FILM_ORDERS[name] == code:
+                return name
+        raise RtxError(f"rtx_film_last_order returned {code}")
+
+    def film_image(self, results, samples: int, width: int, height: int) -> np.ndarray:
+        """The image of a film batch: (height, width, 4) float32, toGamma(sum /
+        samples) per record and alpha 1, record y * width + x (rtx_fold_frames
+        on a zeroed accumulator; a wait). results: width * height
+        PATH_RESULT_DTYPE records, numpy or a device buffer."""
+        npix = int(width) * int(height)
+        own = None
+        if isinstance(results, np.ndarray):
+            host = np.ascontiguousarray(results)
+            if host.dtype != PATH_RESULT_DTYPE:
+                host = np.ascontiguousarray(host, np.float32).reshape(-1, 4)
+            if host.shape[0] != npix:
+                raise RtxError("Context.film_image: results are not width * height records")
+            own = self.alloc((npix,), PATH_RESULT_DTYPE)
+            _check(self._lib.rtx_copy_to_device(self._h, C.c_void_p(own.ptr), host.ctypes.data, 16 * npix),
+                   "rtx_copy_to_device", self._lib)
+            results = own
+        acc = self.alloc((npix, 4), np.float32)
+        img = self.alloc((npix, 4), np.float32)
+        try:
+            acc.upload(np.zeros((npix, 4), np.float32))
+            self.fold_frames(acc.ptr, _dev_ptr(results), 1, npix, npix, samples, img.ptr)
+            return img.numpy().reshape(height, width, 4)
+        finally:
+            acc.free()
+            img.free()
+            if own is not None:
+                own.free()
 
     def paths_last_order(self) -> str:
         """"given" or "coherent": what the last trace_paths ran; "cost" after a
