@@ -11,7 +11,7 @@ BINDIR    := $(PKG)/bin
 HIPFLAGS  := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fvisibility=hidden -ffp-contract=off -Wall -Wno-unused-function
 LIB       := $(LIBDIR)/librtx.so
 CLI       := $(BINDIR)/rtx_cli
-HDRS      := include/rtx.h $(SRC)/rtx_internal.h $(SRC)/rtx_refine_keys.h $(SRC)/rtx_adaptive.h $(SRC)/rtx_features.h $(SRC)/rtx_cast.h $(SRC)/rtx_paths.h $(SRC)/rtx_film.h $(SRC)/rtx_device_math.h $(SRC)/rtx_prefilter.h $(SRC)/rtx_grid.h $(SRC)/rtx_layout.h
+HDRS      := include/rtx.h $(SRC)/rtx_internal.h $(SRC)/rtx_refine_keys.h $(SRC)/rtx_adaptive.h $(SRC)/rtx_features.h $(SRC)/rtx_cast.h $(SRC)/rtx_paths.h $(SRC)/rtx_film.h $(SRC)/rtx_device_math.h $(SRC)/rtx_prefilter.h $(SRC)/rtx_grid.h $(SRC)/rtx_layout.h $(SRC)/rtx_cull.h
 # Build provenance (rtx_build_info): the library records the hash of the
 # sources it was built from; bench.py compares it with the tree's
 # (tools/src_sha.py computes the same hash).

@@ -1368,7 +1368,9 @@ typedef struct rtx_scene_info {
     uint32_t map_in_lds;          /* the render reads the position map from LDS */
     uint32_t flat_lo, flat_hi;    /* blocks of the flat run the scan uses (positions when layout) */
     uint32_t grid, grid_nx, grid_nz; /* a layer grid is uploaded, its size */
-    uint32_t reserved[4];
+    uint32_t cull_positions;      /* kernels == 1: the culled layout's padded position count, else 0 */
+    uint32_t cull_flat_lo;        /* kernels == 1: the first block of its flat section (= positions / 8: none), else 0 */
+    uint32_t reserved[2];
 } rtx_scene_info;
 RTX_API int rtx_debug_scene_info(rtx_ctx *ctx, rtx_scene_info *out);
 

@@ -18,6 +18,7 @@
 
 #include "../../include/rtx.h"
 #include "rtx_internal.h"
+#include "rtx_cull.h"
 #include "rtx_layout.h"
 #include "rtx_film.h"
 #include "rtx_paths.h"
@@ -565,128 +566,6 @@ int rtx_get_schedule(rtx_ctx *c, rtx_schedule *out) {
     return RTX_OK;
 }
 
-// The culled layout (rtx_internal.h KScene, rtx_prefilter.h cull_bound):
-// sections of spheres — large ones (r > 8x the median), the other non-flat
-// ones, the flat ones (height flat_cy, when the scene has a flat run) — each
-// in Morton order of its centres (x, z for the flat section; x, y, z
-// otherwise) and padded to whole blocks with copies of its last sphere whose
-// prefilter R is -inf: never flagged (Q = -inf), except by a lane outside the
-// prefilter's safe region (thr = -inf flags everything), which then resolves
-// the copy to the same key as the sphere itself — no result changes either way.
-struct CullLayout {
-    std::vector<float> pre, bnd, bnd2, bnd3;
-    std::vector<uint32_t> perm;
-    std::vector<uint8_t> pad;  // position holds a padding copy
-    uint32_t flat_lo = 0;
-};
-static CullLayout build_cull(const rtx_world *w, const std::vector<float4> &pre4, bool has_flat, float flat_cy) {
-    const uint32_t n = w->count;
-    const float *S = w->spheres;
-    std::vector<float> rs(n);
-    for (uint32_t i = 0; i < n; ++i) rs[i] = std::fabs(S[4 * i + 3]);
-    std::nth_element(rs.begin(), rs.begin() + n / 2, rs.end());
-    const float big = 8.0f * rs[n / 2];
-    std::vector<uint32_t> sec[3];
-    for (uint32_t i = 0; i < n; ++i) {
-        const bool fl = has_flat && __builtin_bit_cast(uint32_t, S[4 * i + 1]) == __builtin_bit_cast(uint32_t, flat_cy);
-        sec[std::fabs(S[4 * i + 3]) > big ? 0 : fl ? 2 : 1].push_back(i);
-    }
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (uint32_t i = 0; i < n; ++i)
-        for (int k = 0; k < 3; ++k) lo[k] = std::min(lo[k], (double)S[4 * i + k]), hi[k] = std::max(hi[k], (double)S[4 * i + k]);
-    auto q = [&](uint32_t i, int k) -> uint64_t {
-        const double span = hi[k] - lo[k];
-        return span > 0.0 ? (uint64_t)std::min(1023.0, std::floor(((double)S[4 * i + k] - lo[k]) / span * 1024.0)) : 0;
-    };
-    auto morton = [&](uint32_t i, bool flat) {
-        uint64_t key = 0;
-        for (int bit = 0; bit < 10; ++bit) {
-            if (flat)
-                key |= ((q(i, 0) >> bit) & 1u) << (2 * bit) | ((q(i, 2) >> bit) & 1u) << (2 * bit + 1);
-            else
-                key |= ((q(i, 0) >> bit) & 1u) << (3 * bit) | ((q(i, 1) >> bit) & 1u) << (3 * bit + 1) |
-                       ((q(i, 2) >> bit) & 1u) << (3 * bit + 2);
-        }
-        return key;
-    };
-    CullLayout L;
-    for (int k = 0; k < 3; ++k) {
-        if (sec[k].empty()) continue;
-        std::stable_sort(sec[k].begin(), sec[k].end(),
-                         [&](uint32_t a, uint32_t b) { return morton(a, k == 2) < morton(b, k == 2); });
-        if (k == 2) {
-            // the flat section starts at a multiple of kCullAlign blocks, so
-            // that no bound test (8 entries of 1, 8 or 64 blocks) mixes flat
-            // and non-flat bounds; the padding blocks' bounds never pass (R = -inf)
-            while (!L.perm.empty() && (L.perm.size() / 8) % rtx::kCullAlign != 0) {
-                const uint32_t last = L.perm.back();
-                for (int i = 0; i < 8; ++i) L.perm.push_back(last), L.pad.push_back(1);
-            }
-            L.flat_lo = (uint32_t)L.perm.size() / 8;
-        }
-        for (uint32_t i : sec[k]) L.perm.push_back(i), L.pad.push_back(0);
-        while (L.perm.size() % 8) L.perm.push_back(sec[k].back()), L.pad.push_back(1);
-    }
-    if (sec[2].empty()) L.flat_lo = (uint32_t)L.perm.size() / 8;
-    const uint32_t np = (uint32_t)L.perm.size(), nblk = np / 8, ngrp = (nblk + 7) / 8;
-    // the bound of positions [p0, p1): over their spheres; R = -inf when they are all padding
-    auto bound_of = [&](uint32_t p0, uint32_t p1, bool fl) {
-        std::vector<const float *> sp;
-        bool all_pad = true;
-        for (uint32_t p = p0; p < std::min(p1, np); ++p) sp.push_back(&S[4 * (size_t)L.perm[p]]), all_pad &= L.pad[p] != 0;
-        rtx::CullBound cb = rtx::cull_bound(sp.data(), (int)sp.size(), fl, flat_cy, fl ? rtx::kCullSy : 1.0f);
-        if (all_pad) cb.R = -INFINITY;
-        return cb;
-    };
-    L.pre.assign(4 * (size_t)np, 0.0f);
-    for (uint32_t p = 0; p < np; ++p) {
-        const float4 v = pre4[L.perm[p]];
-        float *blk = &L.pre[32 * (size_t)(p / 8)];
-        blk[p % 8] = v.x, blk[8 + p % 8] = v.y, blk[16 + p % 8] = v.z, blk[24 + p % 8] = L.pad[p] ? -INFINITY : v.w;
-    }
-    L.bnd.assign(32 * (size_t)ngrp, 0.0f);
-    for (uint32_t g = 0; g < ngrp; ++g)
-        for (uint32_t j = 0; j < 8; ++j) {
-            const uint32_t b = 8 * g + j;
-            float *gb = &L.bnd[32 * (size_t)g];
-            if (b >= nblk) {  // past the last block: masked off by the kernel; flat height for a flat group
-                gb[8 + j] = 8 * g >= L.flat_lo ? rtx::kCullSy * flat_cy : 0.0f;
-                continue;
-            }
-            const rtx::CullBound cb = bound_of(8 * b, 8 * b + 8, b >= L.flat_lo);  // flat: stretched along y
-            gb[j] = cb.cx, gb[8 + j] = cb.cy, gb[16 + j] = cb.cz, gb[24 + j] = cb.R;
-        }
-    // the top level: one bound over each group's 64 spheres, 8 groups per super-group
-    const uint32_t nsg = (ngrp + 7) / 8;
-    L.bnd2.assign(32 * (size_t)nsg, 0.0f);
-    for (uint32_t s = 0; s < nsg; ++s)
-        for (uint32_t j = 0; j < 8; ++j) {
-            const uint32_t g = 8 * s + j;
-            float *gb = &L.bnd2[32 * (size_t)s];
-            if (g >= ngrp) {
-                gb[8 + j] = 64 * s >= L.flat_lo ? rtx::kCullSy * flat_cy : 0.0f;
-                continue;
-            }
-            const rtx::CullBound cb = bound_of(64 * g, 64 * g + 64, 8 * g >= L.flat_lo);
-            gb[j] = cb.cx, gb[8 + j] = cb.cy, gb[16 + j] = cb.cz, gb[24 + j] = cb.R;
-        }
-    // the third level: one bound over each super-group's 512 spheres, 8 per entry of bnd3
-    const uint32_t nhg = (nsg + 7) / 8;
-    L.bnd3.assign(32 * (size_t)nhg, 0.0f);
-    for (uint32_t h = 0; h < nhg; ++h)
-        for (uint32_t j = 0; j < 8; ++j) {
-            const uint32_t sg = 8 * h + j;
-            float *gb = &L.bnd3[32 * (size_t)h];
-            if (sg >= nsg) {
-                gb[8 + j] = 512 * h >= L.flat_lo ? rtx::kCullSy * flat_cy : 0.0f;
-                continue;
-            }
-            const rtx::CullBound cb = bound_of(512 * sg, 512 * sg + 512, 64 * sg >= L.flat_lo);
-            gb[j] = cb.cx, gb[8 + j] = cb.cy, gb[16 + j] = cb.cz, gb[24 + j] = cb.R;
-        }
-    return L;
-}
-
 int rtx_upload_world(rtx_ctx *c, const rtx_world *w) {
     if (!c || !w) return fail(RTX_ERR_INVALID, "rtx_upload_world: null argument");
     if (w->reserved != 0) return fail(RTX_ERR_INVALID, "rtx_upload_world: reserved must be 0");
@@ -769,10 +648,11 @@ int rtx_upload_world(rtx_ctx *c, const rtx_world *w) {
         mval[i] = make_float4(w->mat_values[4 * i + 0], w->mat_values[4 * i + 1],
                               w->mat_values[4 * i + 2], w->mat_values[4 * i + 3]);
     }
-    CullLayout cl;
+    rtx::CullLayout cl;  // the culled layout (rtx_cull.h)
     const bool linear = c->scan_mode == RTX_SCAN_LINEAR;  // every block of every segment: no grid, no culled copy
     const bool cull = !linear && n_pad > rtx::kScanPfMin;  // the large-scene (kPF) kernels scan it
-    if (cull) cl = build_cull(w, pre4, flat_hi > flat_lo, flat_cy);
+    static_assert(sizeof(float4) == 4 * sizeof(float), "pre4 is read as (cx, cy, cz, R) float records");
+    if (cull) cl = rtx::build_cull(w->spheres, n, reinterpret_cast<const float *>(pre4.data()), flat_hi > flat_lo, flat_cy);
     // the small-scene lane-mode scan's layer grid over the flat run (rtx_grid.h)
     rtx::LayerGrid grid{};
     std::vector<unsigned long long> gcell;
@@ -897,6 +777,8 @@ int rtx_debug_scene_info(rtx_ctx *c, rtx_scene_info *out) {
     out->grid = s.grid != nullptr;
     out->grid_nx = c->grid_nx;
     out->grid_nz = c->grid_nz;
+    out->cull_positions = k.kernels == 1 ? s.n_cpad : 0;
+    out->cull_flat_lo = k.kernels == 1 ? s.cflat_lo : 0;
     return RTX_OK;
 }
 

@@ -79,11 +79,7 @@ struct KScene {
 #ifndef RTX_LAYOUT  // A/B build: 0 = no spatial layout of small scenes (the scan visits the layer in scene order)
 #define RTX_LAYOUT 1
 #endif
-// The culled layout has three bound levels above the blocks (groups,
-// super-groups, 512-block ranges; two levels: 187.5 vs 128.8 ms, RESULTS R9zb),
-// and its flat section starts at a multiple of this many blocks: no bound test
-// (8 entries) mixes flat and non-flat bounds
-constexpr uint32_t kCullAlign = 512u;
+// (the culled layout's builder and its kCullAlign: rtx_cull.h)
 #ifndef RTX_SCAN_PF_MIN  // (A/B builds: 0 sends every scene to the kPF kernels)
 #define RTX_SCAN_PF_MIN 1024
 #endif

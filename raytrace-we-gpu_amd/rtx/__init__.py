@@ -123,7 +123,7 @@ class rtx_scene_info(C.Structure):
                 ("sphere_copy_lds", C.c_uint32), ("layout", C.c_uint32), ("layout_positions", C.c_uint32),
                 ("map_in_lds", C.c_uint32), ("flat_lo", C.c_uint32), ("flat_hi", C.c_uint32),
                 ("grid", C.c_uint32), ("grid_nx", C.c_uint32), ("grid_nz", C.c_uint32),
-                ("reserved", C.c_uint32 * 4)]
+                ("cull_positions", C.c_uint32), ("cull_flat_lo", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class rtx_hit(C.Structure):
@@ -1252,7 +1252,8 @@ class Context:
         """What upload_world built and which path the launches take for it
         (rtx_debug_scene_info): count, n_pad, kernels (0 small, 1 large culled,
         2 large linear), sphere_copy_lds, layout, layout_positions, map_in_lds,
-        flat_lo, flat_hi, grid, grid_nx, grid_nz. Nothing is launched."""
+        flat_lo, flat_hi, grid, grid_nx, grid_nz, and the culled layout's
+        cull_positions and cull_flat_lo (0 unless kernels == 1). Nothing is launched."""
         info = rtx_scene_info()
         _check(self._lib.rtx_debug_scene_info(self._h, C.byref(info)), "rtx_debug_scene_info", self._lib)
         return {name: int(getattr(info, name)) for name, _ in rtx_scene_info._fields_ if name != "reserved"}
